@@ -2,6 +2,14 @@
 """bench.py — throughput of the batched HIP 𝓗₂ SLS solve (the hot path of BASELINE.json's north_star).
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+          [--full] [--dump-outputs DIR]
+
+A plain run measures the headline figure only: setup, W warmup steps, K timed steps, the result line.  --full adds the
+measurements that take runs of their own: the one-shot drop-in call (config.oneshot_call, config.wall_clock_to_phi_ms),
+cpu_baseline (N=1) and the "strong" record (N>1, or one rank with --force-collective).
+--dump-outputs DIR writes what the last timed step computed — the mask-order Φ value array every rank holds after a step
+(Φx[t] then Φu[t], each in its mask's CSC order) — to DIR/phi_values.npy in float64.  Beyond 64 MB a fixed, seeded sample
+is written instead, its positions in DIR/phi_values_index.npy.  The inputs depend on the arguments only.
 
 Workload.  N=1 is BASELINE.json configs[1] exactly: the README chain (Nx=59, Nu=20, d=9, T=29, α=1.5; README.md:43-57),
 59 localized subproblems per step.  N>1 keeps the per-GPU work fixed (weak scaling of the sharded path): the same chain
@@ -15,8 +23,8 @@ index sets, masks, destination tables) are resident in HBM before the timed regi
 are setup (timed separately, reported in config).
 value = subproblems attempted by all ranks per second (whole job); solved_per_s counts only those that ended SLS_COL_OK
 (equal on the README chain; grid-32 and the random plants have infeasible columns as specified).  dtype f64.  vs_baseline
-null (the reference publishes no number).  N>1 adds a "strong" record to the same line: ONE fixed plant
-(chain Nx=4096, d=12, T=40) sharded over the N ranks — ms per pass, the all-gather alone, the cost imbalance of the cut.
+null (the reference publishes no number).  N>1 with --full adds a "strong" record to the same line: ONE fixed
+plant (chain Nx=4096, d=12, T=40) sharded over the N ranks — ms per pass, the all-gather alone, the cost imbalance of the cut.
 roofline: FP64 compute bound (≈146 flop/B ≫ ridge).  achieved = F_alg of this rank's shard ÷ average
 device time of the solve kernel (HIP events on the launch stream inside libsls); peak = 78.6 TFLOP/s, the public
 MI355X FP64 vector/matrix figure (the in-container microarch guide lists no FP64 rate).  bound = "mfma" when the
@@ -25,7 +33,7 @@ launch list contains the FP64-MFMA tile kernel (ñx > 64: grid-32, random10000),
 passes of this same command, committed under profiles/ (bench.py cannot read PMC counters itself): an OFFLINE measurement, the
 commit it was taken at is in the file.
 cpu_baseline: the oracle's C restatement (oracle/sls_oracle_c.c, canonical block-tridiagonal Cholesky) timed on this
-box's host cores on the same 59 README columns, repeated to fill a bounded sample ("port"; rank 0, N=1 only).
+box's host cores on the same 59 README columns, repeated to fill a bounded sample ("port"; rank 0, N=1, --full only).
 """
 import argparse
 import json
@@ -37,6 +45,22 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PEAK_FP64_TFLOPS = 78.6
+DUMP_MAX_BYTES = 64_000_000          # --dump-outputs: payload of all files together, .npy headers included
+
+
+def dump_outputs(out_dir, values):
+    """Writes the mask-order Φ value array of the last step (float64) to out_dir/phi_values.npy.  Above DUMP_MAX_BYTES a
+    fixed sample (seed 0, ascending positions) is written instead, with its positions as float64 in phi_values_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    v = values.detach().cpu().numpy().astype(np.float64, copy=False)
+    cap = (DUMP_MAX_BYTES - 2 * 4096) // 8
+    if v.size <= cap:
+        np.save(os.path.join(out_dir, "phi_values.npy"), v)
+        return
+    idx = np.sort(np.random.default_rng(0).choice(v.size, cap // 2, replace=False))
+    np.save(os.path.join(out_dir, "phi_values.npy"), v[idx])
+    np.save(os.path.join(out_dir, "phi_values_index.npy"), idx.astype(np.float64))
 
 
 def cpu_baseline(max_seconds=12.0):
@@ -73,13 +97,19 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="auto", help="auto = chain with Nx=59·gpus (README chain at 1 GPU); or a name from workloads.WORKLOADS")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure: one-shot drop-in call, cpu_baseline, strong record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the Φ values of the last timed step to DIR/phi_values.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--objective", default="h2", choices=["h2", "sum_of_norms"],
                     help="sum_of_norms = the column-separable 𝓗∞ bound (BASELINE configs[3] as named; an extension, no reference exists)")
-    ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the extra strong-scaling record (chain-4096 sharded over the ranks)")
+    ap.add_argument("--no-strong", action="store_true", help="--full, N > 1: skip the extra strong-scaling record (chain-4096 sharded over the ranks)")
     ap.add_argument("--force-collective", action="store_true",
                     help="one rank only: still create the RCCL process group and run the all-gather + unpack of the N>1 path")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -152,6 +182,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sh.values[: sh.n_values])      # every rank holds the whole array after a step
     kern_ms, n_launch = sh.local.plan.kernel_time_ms()
     st, rs, it = sh.local.plan.fetch_status()
     n_bad = int((st != 0).sum())
@@ -162,11 +194,11 @@ def main():
         n_bad_total = int(tb.item())
     info = sh.local.info
 
-    # N > 1: the informative sharding case next to the weak-scaling `value` — ONE fixed plant (chain Nx = 4096, d = 12, T = 40:
+    # --full, N > 1: the informative sharding case next to the weak-scaling `value` — ONE fixed plant (chain Nx = 4096, d = 12, T = 40:
     # BASELINE configs[3]'s plant under the 𝓗₂ objective) cut over the N ranks: time per pass of the sharded path (solve of
     # the shard + all-gather + unpack, max over ranks), the all-gather alone, and the predicted-cost imbalance of the cut
     strong = None
-    if (world > 1 or args.force_collective) and args.workload == "auto" and not args.no_strong:      # (one rank + --force-collective: rehearsal of this block on a single GPU)
+    if args.full and (world > 1 or args.force_collective) and args.workload == "auto" and not args.no_strong:      # (one rank + --force-collective: rehearsal of this block on a single GPU)
         try:
             Ps, Ss, ms = wl.make_workload("chain4096")
             shs = slc_amd.dist.ColumnShardedH2(Ps, Ss, None, device=device, objective="h2")
@@ -205,9 +237,9 @@ def main():
         except Exception as e:   # the extra record must never take the contract line down
             strong = {"error": str(e)}
 
-    # PCIe-inclusive one-shot drop-in call (symbolic pass + H2D + solve + D2H per call) — reported in config, never `value`
+    # PCIe-inclusive one-shot drop-in call (symbolic pass + H2D + solve + D2H per call) — --full only, reported in config, never `value`
     oneshot = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             octx = slc_amd.Context([local_rank])
             slc_amd.SLS_H2(P, S, ctx=octx, objective=args.objective, return_info=True)
@@ -287,6 +319,7 @@ def main():
                        "max_nx": int(info["max_nx"]), "max_nu": int(info["max_nu"]),
                        "phi_values": int(info["n_values"]),
                        # what a caller of the drop-in call waits for Φ: symbolic pass + H2D + solve + D2H inside the library
+                       # (--full; null in a plain run)
                        "wall_clock_to_phi_ms": oneshot_ms,
                        "resident_step_ms": round(1e3 * elapsed / args.steps, 5),
                        "setup_symbolic_upload_s": round(t_setup, 4), "mask_generation_s": round(t_gen, 4),
@@ -307,7 +340,7 @@ def main():
             # F_alg counts the 𝓗₂ solve (factor + one pass) once; the ADMM steps on top of it are not algorithmic flops of
             # anything the reference computes — the fraction is reported for the 𝓗₂ part only and says so
             out["roofline"]["note"] = "flops_alg is the H2 solve's (SURVEY §8d); the sum-of-norms loop runs max_refinement_passes ADMM steps on top"
-        if world == 1 and not args.no_cpu_baseline and args.objective == "h2":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.objective == "h2":
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as e:   # the checker must never take the measurement down

@@ -1160,7 +1160,7 @@ def test_bench_collective_path_and_strong_record_on_one_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29541", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3",
-                        "--force-collective", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=550)
+                        "--force-collective", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=550)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
