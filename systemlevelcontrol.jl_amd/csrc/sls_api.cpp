@@ -121,8 +121,8 @@ struct sls_plan {
   };
   std::vector<Launch> launches;
   hipEvent_t ev_fork = nullptr;
-  hipEvent_t ev_done = nullptr;         // recorded on the caller's stream at the end of every execute: what status reads and downloads wait for
-  bool ev_done_recorded = false;
+  hipEvent_t ev_done = nullptr;         // recorded on the caller's stream at the end of an execute that the event pool could not time
+  hipEvent_t last_done = nullptr;       // the end of the last execute: its ev_stop (timed) or ev_done (untimed); what status reads and downloads wait for
   // event timing
   hipEvent_t ev_start[kEventPool], ev_stop[kEventPool];
   int ev_used = 0;
@@ -332,8 +332,8 @@ int fold_events(sls_plan* pl, bool blocking = true) {
 // Host waits for the plan's last execute (and for nothing else on the device: a status read or a download must not stall on
 // a collective or on another plan running on some other stream).
 int wait_plan_done(sls_plan* pl) {
-  if (pl->ev_done_recorded) {
-    hipError_t e = hipEventSynchronize(pl->ev_done);
+  if (pl->last_done) {
+    hipError_t e = hipEventSynchronize(pl->last_done);
     if (e != hipSuccess) return hipfail(pl->ctx, e, "hipEventSynchronize (plan done)");
   }
   return 0;
@@ -1723,13 +1723,19 @@ int sls_plan_execute(sls_plan* plan, void* hip_stream, double* d_values, int pac
     int rc = sls_plan_execute(plan->refine, hip_stream, d_values, packed);
     if (rc) return rc;
   }
+  // The end of this execute on the caller's stream: a timed execute's stop event is that point already (two event records per
+  // execute, not three); only an untimed one records the dedicated event.  An event handle stays the same object when
+  // fold_events compacts the pool, and a stop event is recorded again only at the end of a later execute, which then points
+  // last_done at it.
   if (timed) {
     HIPCHK(plan->ctx, hipEventRecord(plan->ev_stop[ev], st));
     plan->ev_used = ev + 1;
+    plan->last_done = plan->ev_stop[ev];
+  } else {
+    if (!plan->ev_done) HIPCHK(plan->ctx, hipEventCreateWithFlags(&plan->ev_done, hipEventDisableTiming));
+    HIPCHK(plan->ctx, hipEventRecord(plan->ev_done, st));
+    plan->last_done = plan->ev_done;
   }
-  if (!plan->ev_done) HIPCHK(plan->ctx, hipEventCreateWithFlags(&plan->ev_done, hipEventDisableTiming));
-  HIPCHK(plan->ctx, hipEventRecord(plan->ev_done, st));
-  plan->ev_done_recorded = true;
   return 0;
 }
 

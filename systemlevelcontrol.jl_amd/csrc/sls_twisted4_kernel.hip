@@ -11,8 +11,8 @@
 // the next block is the Schur complement of the bordered matrix [[G, Xᵀ], [X, S]] on G = the block being inverted RIGHT NOW:
 // eliminating G's pivots from the border produces S − X G⁻¹ Xᵀ in place of S.  The chain wave inverts G by the same tiled
 // Gauss–Jordan as before and, per pivot, drops the pivot row (its pre-update values) and 1/pivot into LDS; the helper —
-// one or two pivots behind — applies that pivot to its own tiles of X and S (6 ds_swizzle + 6 ds_bpermute + 18 FMA, no
-// reciprocal chain, ≈250 cycles against the chain wave's ≈330).  When the chain wave has finished block k (store + fused
+// one or two pivots behind — applies that pivot to its own tiles of X and S (6 ds_swizzle, column p of X as a row through one
+// narrow LDS record, 18 FMA, no reciprocal chain).  When the chain wave has finished block k (store + fused
 // sweep), block k+1 is waiting for it in LDS in exactly the lane layout its Gauss–Jordan starts from.  Chain per block:
 // Gauss–Jordan + store + sweep; the sparse products are gone (the helper never forms P·anything: same flops as the explicit
 // products, but off the chain).  The middle block takes both helpers' contributions.
@@ -65,6 +65,19 @@ __device__ __forceinline__ void wait_flag(const int* f, int target) {
 // two DPP row_newbcast moves per 32-bit half, one per half of the 16-lane DPP row (bank masks 0x3 / 0xc).  ds_swizzle does the
 // same in one DS instruction per half.  Measured SLOWER (README launch 0.1174 → 0.1239 ms): the waves are bound by instruction
 // issue, and four VALU moves per value cost more issue slots than two ds_swizzle; kept as an A/B switch.
+// ISA markers for tools/isa_mix.py (-DSLS_ISA_MARKS=1, assembly listings only): an assembler comment at a point every pivot
+// already passes through a sched_barrier, so the listing is cut into one span per pivot without moving anything across it.
+#if defined(SLS_ISA_MARKS) && SLS_ISA_MARKS
+#define SLS_ISA_MARK(name) asm volatile("; isa-mark " name)
+#else
+#define SLS_ISA_MARK(name) ((void)0)
+#endif
+
+// Per-pivot phase stamps (SLS_PHASE_TIMERS = 2 / 3: chain waves' / helper waves' shares, tools/t4_phases.py) are compiled in only
+// with -DSLS_T4_PHASES=1: the shipped kernel carries no s_memtime pair around the helper's wait and no dbg_level branch per block.
+#ifndef SLS_T4_PHASES
+#define SLS_T4_PHASES 0
+#endif
 #ifndef SLS_T4_SAME
 #define SLS_T4_SAME 1          // reuse of the static part of a block while the masks repeat (0: always rebuilt; diagnostics)
 #endif
@@ -135,6 +148,24 @@ __device__ __forceinline__ void store_col8_4(unsigned addr, double v0, double v1
                :: [a] "v"(addr), [v0] "v"(v0), [v1] "v"(v1), [v2] "v"(v2), [v3] "v"(v3), [o0] "n"(O0), [o1] "n"(O0 + 64), [o2] "n"(O0 + 128), [o3] "n"(O0 + 192) : "memory");
 }
 
+// Lanes QA, QA + 8, … QA + 56 (column QA of the lane grid): TR doubles to addr + O0 (one 32-byte record per lane-grid row)
+template <int QA, int O0>
+__device__ __forceinline__ void store_xcol8_3(unsigned addr, double v0, double v1, double v2) {
+  const d2_t q0 = {v0, v1};
+  asm volatile("s_mov_b32 exec_lo, %[m]\n\ts_mov_b32 exec_hi, %[m]\n\t"
+               "ds_write_b128 %[a], %[q0] offset:%[o0]\n\tds_write_b64 %[a], %[v2] offset:%[o1]\n\t"
+               "s_mov_b64 exec, -1"
+               :: [m] "n"((int)(0x01010101u << QA)), [a] "v"(addr), [q0] "v"(q0), [v2] "v"(v2), [o0] "n"(O0), [o1] "n"(O0 + 16) : "memory");
+}
+template <int QA, int O0>
+__device__ __forceinline__ void store_xcol8_4(unsigned addr, double v0, double v1, double v2, double v3) {
+  const d2_t q0 = {v0, v1}, q1 = {v2, v3};
+  asm volatile("s_mov_b32 exec_lo, %[m]\n\ts_mov_b32 exec_hi, %[m]\n\t"
+               "ds_write_b128 %[a], %[q0] offset:%[o0]\n\tds_write_b128 %[a], %[q1] offset:%[o1]\n\t"
+               "s_mov_b64 exec, -1"
+               :: [m] "n"((int)(0x01010101u << QA)), [a] "v"(addr), [q0] "v"(q0), [q1] "v"(q1), [o0] "n"(O0), [o1] "n"(O0 + 16) : "memory");
+}
+
 // Tiled Gauss–Jordan of the chain wave on the 8×8 lane grid (lane (a, b) holds {rows a + 8·ri} × {columns b + 8·cj}), in place
 // on the tiles, publishing every pivot's row and reciprocal for the helper wave: rowbuf[pv] = eight packed records (RS doubles per pivot, see store_row8_*), then *flag = seqbase + pv + 1.
 template <int NP, int TR, int RS>
@@ -189,6 +220,7 @@ __device__ __forceinline__ void gj_tiles_publish(double (&Tt)[TR * TR], const in
         tfix[cj] = (cj == ps && tb == pa) ? (1.0 + d) : tj[cj];
       }
       __builtin_amdgcn_sched_barrier(0);
+      SLS_ISA_MARK("chain-pivot");
 #pragma unroll
       for (int ri = 0; ri < TR; ++ri) {
 #pragma unroll
@@ -224,19 +256,25 @@ __device__ __forceinline__ void gj_tiles_publish(double (&Tt)[TR * TR], const in
 }
 
 // The helper wave's side of the same elimination: X ← X − X[:,p]·(d·g[p,:]),  S ← S − (X[:,p]·d)·X[:,p]ᵀ for every pivot p the chain
-// wave has published (same lane grid; column p of X by ds_swizzle inside the 8-lane group, the same column as a row by
-// ds_bpermute from lane (b, p mod 8)).  Columns ≤ p of X are dead after pivot p and are left to whatever the update makes of them.
+// wave has published (same lane grid; column p of X by ds_swizzle inside the 8-lane group, the same column as a row through the
+// LDS record `xbuf`).  Columns ≤ p of X are dead after pivot p and are left to whatever the update makes of them.
 template <int NP, int TR, int RS>
 __device__ __forceinline__ void helper_eliminate(double (&Xw)[TR * TR], double (&Sw)[TR * TR], const int lane, const int n,
-                                                 const double* rowbuf, const int* flag, const int seqbase, unsigned long long& wait_cycles) {
+                                                 const double* rowbuf, const int* flag, const int seqbase, double* xbuf,
+                                                 unsigned long long& wait_cycles) {
   int ta = lane >> 3, tb = lane & 7, nn = __builtin_amdgcn_readfirstlane(n);
   asm volatile("" : "+v"(ta), "+v"(tb), "+s"(nn));
-  (void)ta;
   int ready = 0;
   // Column q of X in both index forms, fetched one pivot ahead (as the chain wave does with its pivot row and column): only the
   // entries of the NEXT pivot's column slot have to be up to date before its cross-lane reads issue, the other FMAs of the
   // step run in their shadow.  Two register sets, alternating by pivot parity (no copies).
+  // Row form: the eight lanes that hold column q (b = q mod 8) write their TR entries as one 32-byte record per lane-grid row a,
+  // every lane reads back record b (rows b + 8·cj): two DS writes by eight lanes + two reads instead of 2·TR ds_bpermute.  The
+  // slot is reused by the next pivot without a wait: DS operations of one wave execute in program order, the read of pivot q is
+  // done before the write of pivot q + 1.  Only the S update (phase B) uses the row form, off the step's dependent chain.
   double xc[2][TR], xrw[2][TR];
+  const unsigned xw_addr = lds_addr(xbuf + 4 * ta);
+  const double* xr_rec = xbuf + 4 * tb;
   auto fetchX = [&](auto q_c) {
     constexpr int q = decltype(q_c)::value;
     constexpr int qa = q % 8, qs = q / 8, par = q & 1;
@@ -244,13 +282,13 @@ __device__ __forceinline__ void helper_eliminate(double (&Xw)[TR * TR], double (
     for (int ri = 0; ri < TR; ++ri) {
       xc[par][ri] = bcast8<qa>(Xw[ri * TR + qs]);
     }
-    const int src = (tb * 8 + qa) << 2;
-#pragma unroll
-    for (int cj = 0; cj < TR; ++cj) {
-      const double v = Xw[cj * TR + qs];
-      xrw[par][cj] = (SLS_T4_EXP == 2 || SLS_T4_EXP == 3) ? v : __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(v)),
-                                                                                    __builtin_amdgcn_ds_bpermute(src, __double2loint(v)));
-    }
+    static_assert(TR == 3 || TR == 4, "store_xcol8_* are written for three or four tile rows");
+    if constexpr (TR == 3) store_xcol8_3<qa, 0>(xw_addr, Xw[qs], Xw[TR + qs], Xw[2 * TR + qs]);
+    else store_xcol8_4<qa, 0>(xw_addr, Xw[qs], Xw[TR + qs], Xw[2 * TR + qs], Xw[3 * TR + qs]);
+    const d2_t r0 = *reinterpret_cast<const d2_t*>(xr_rec);
+    xrw[par][0] = r0[0]; xrw[par][1] = r0[1];
+    if constexpr (TR == 3) xrw[par][2] = xr_rec[2];
+    else { const d2_t r1 = *reinterpret_cast<const d2_t*>(xr_rec + 2); xrw[par][2] = r1[0]; xrw[par][3] = r1[1]; }
   };
   fetchX(std::integral_constant<int, 0>{});
   // The published row of the NEXT pivot is read speculatively one step ahead, flag first (DS operations execute in order: a
@@ -282,12 +320,13 @@ __device__ __forceinline__ void helper_eliminate(double (&Xw)[TR * TR], double (
       const int target = seqbase + pv + 1;
       ready = max(ready, __builtin_amdgcn_readfirstlane(fnext));
       if (ready < target) {
-        const unsigned long long w0 = __builtin_amdgcn_s_memtime();
+        unsigned long long w0 = 0;
+        if constexpr (SLS_T4_PHASES != 0) w0 = __builtin_amdgcn_s_memtime();
         while (ready < target) {
           ready = flag_load(flag);
           if (ready < target) __builtin_amdgcn_s_sleep(1);
         }
-        wait_cycles += __builtin_amdgcn_s_memtime() - w0;
+        if constexpr (SLS_T4_PHASES != 0) wait_cycles += __builtin_amdgcn_s_memtime() - w0;
         asm volatile("" ::: "memory");
         read_row(pv, par);
       }
@@ -296,6 +335,7 @@ __device__ __forceinline__ void helper_eliminate(double (&Xw)[TR * TR], double (
       double m[TR];
       const double (&grow)[TR] = gn[par];
       __builtin_amdgcn_sched_barrier(0);
+      SLS_ISA_MARK("helper-pivot");
       // phase A: the next pivot's column slot of X
 #pragma unroll
       for (int ri = 0; ri < TR; ++ri) Xw[ri * TR + ns] = __builtin_fma(-xc[par][ri], grow[ns], Xw[ri * TR + ns]);
@@ -313,6 +353,11 @@ __device__ __forceinline__ void helper_eliminate(double (&Xw)[TR * TR], double (
           if (ri <= cj) Sw[ri * TR + cj] = __builtin_fma(-m[ri], xrw[par][cj], Sw[ri * TR + cj]);
         }
       }
+      // Every tile is updated at this pivot, not later: without the pin the compiler sinks the updates of column slots whose
+      // pivots are still 8–16 steps away into one batch there, keeps every postponed pivot's column and row alive until then and
+      // spills them to AGPRs (≈ 290 accvgpr copies over the <32,12> helper loop; 28 with the pin, tools/isa_mix.py).
+#pragma unroll
+      for (int q = 0; q < TR * TR; ++q) asm volatile("" : "+v"(Xw[q]), "+v"(Sw[q]));
     }
   });
 }
@@ -326,7 +371,7 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
   constexpr int LDT = 40;                                 // leading dimension of the tile images (8·a + b: no bank conflict)
   constexpr int RS = (TR == 3) ? 32 : 48;                 // doubles per published pivot: eight packed records (store_row8_*)
   constexpr int PRIVC = NR * LDT + 2 * NPL;               // chain wave: mat, tmp, tmp2
-  constexpr int PRIVH = 0;                                // (helper waves keep nothing private in LDS)
+  constexpr int PRIVH = 32;                               // helper wave: the row form of column p of X (eight 32-byte records)
   constexpr int DIRSZ = NR * RS + NR * LDT + 2;           // per direction: published rows, hand-off tiles, two flags
   const int wv = threadIdx.x >> 6;                        // 0/1: chain waves (up / down), 2/3: their helpers
   const int dir = wv & 1, helper = wv >> 1;
@@ -342,7 +387,7 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
   double* dp = reinterpret_cast<double*>(lds_raw);
   double* privc = dp + dir * PRIVC; dp += 2 * PRIVC;
   double* mat = privc; double* tmp = mat + NR * LDT; double* tmp2 = tmp + NPL;
-  dp += 2 * PRIVH;
+  double* xbuf = dp + dir * PRIVH; dp += 2 * PRIVH;
   double* dirb = dp + dir * DIRSZ;
   double* dirb_other = dp + (1 - dir) * DIRSZ; dp += 2 * DIRSZ;
   double* rowbuf = dirb; double* hand = rowbuf + NR * RS;
@@ -701,7 +746,7 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
       for (int s = 1; s <= s_end; ++s) {
         const int k = (dir == 0) ? s : T - s + 1;
         const bool mid = (dir == 0) && (s == c);
-        unsigned long long q0 = __builtin_amdgcn_s_memtime();
+        unsigned long long q0 = (SLS_T4_PHASES != 0) ? __builtin_amdgcn_s_memtime() : 0;
         wait_flag(flagB, s);
         // the helper hands over the stored half (tiles ri ≤ cj of every lane); the other half is read at the mirror position
         double Tt[TT];
@@ -720,9 +765,9 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
               Tt[ri * TR + cj] += (ri <= cj) ? hand_other[(ta + 8 * ri) * LDT + tb + 8 * cj] : hand_other[(tb + 8 * cj) * LDT + ta + 8 * ri];
           }
         }
-        if (p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[0] += q1 - q0; q0 = q1; }
+        if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[0] += q1 - q0; q0 = q1; }
         gj_tiles_publish<NP, TR, RS>(Tt, lane, n, rowbuf, flagA, s * 64, mat);
-        if (p.dbg_level >= 2) { __builtin_amdgcn_sched_barrier(0); asm volatile("" :: "v"(Tt[0])); const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[1] += q1 - q0; q0 = q1; }
+        if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { __builtin_amdgcn_sched_barrier(0); asm volatile("" :: "v"(Tt[0])); const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[1] += q1 - q0; q0 = q1; }
         // tiles → column layout (lane (h, j): rows HS·r + h of column j) through the private image
 #pragma unroll
         for (int ri = 0; ri < TR; ++ri) {
@@ -735,7 +780,7 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
         WSYNC();
         store_P(k, M);
         if (!mid) { if (dir == 0) elim_up(k, M, wx_of(k)); else elim_down(k, M, wx_of(k)); }
-        if (p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[2] += q1 - q0; q0 = q1; }
+        if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[2] += q1 - q0; q0 = q1; }
       }
     } else {
       // =================== helper wave: static part S_k, border X, elimination behind the chain wave's pivots ===================
@@ -778,7 +823,7 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
       double Xn[TT];
       if (s_end >= 2) load_border((dir == 0) ? 2 : T - 1, Xn);
       for (int s = 1; s <= s_end; ++s) {
-        unsigned long long q0 = __builtin_amdgcn_s_memtime();
+        unsigned long long q0 = (SLS_T4_PHASES != 0) ? __builtin_amdgcn_s_memtime() : 0;
         const int k = (dir == 0) ? s : T - s + 1;           // block being produced (downward helper's last step: k = c, the middle)
         const bool mid_down = (dir == 1) && (k == c);
         const bool same = have_S && !mid_down && k < 64 && ((samebits >> k) & 1ull) && !(dir == 0 && s == 2);
@@ -854,9 +899,9 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
 #pragma unroll
           for (int q = 0; q < TT; ++q) Xw[q] = Xn[q];
           if (s + 1 <= s_end) load_border((dir == 0) ? s + 1 : T - s, Xn);      // next step's border: its loads fly during this elimination
-          if (p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[0] += q1 - q0; q0 = q1; }
-          if (SLS_T4_EXP != 1 && SLS_T4_EXP != 4) helper_eliminate<NP, TR, RS>(Xw, Sw, lane, n, rowbuf, flagA, (s - 1) * 64, ph[2]);
-          if (p.dbg_level >= 2) { __builtin_amdgcn_sched_barrier(0); asm volatile("" :: "v"(Sw[0])); const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[1] += q1 - q0; q0 = q1; }
+          if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[0] += q1 - q0; q0 = q1; }
+          if (SLS_T4_EXP != 1 && SLS_T4_EXP != 4) helper_eliminate<NP, TR, RS>(Xw, Sw, lane, n, rowbuf, flagA, (s - 1) * 64, xbuf, ph[2]);
+          if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { __builtin_amdgcn_sched_barrier(0); asm volatile("" :: "v"(Sw[0])); const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[1] += q1 - q0; q0 = q1; }
         }
 #pragma unroll
         for (int ri = 0; ri < TR; ++ri) {

@@ -1,4 +1,5 @@
-"""Phase shares inside the four-wave twisted kernel's factor half (SLS_PHASE_TIMERS=1: laps; 2: chain waves; 3: helper waves)."""
+"""Phase shares inside the four-wave twisted kernel's factor half (SLS_PHASE_TIMERS=1: laps; 2: chain waves; 3: helper waves).
+Levels 2 and 3 need the per-pivot stamps compiled in: make -C systemlevelcontrol.jl_amd/csrc -B EXTRA=-DSLS_T4_PHASES=1."""
 import ctypes as C, os, sys
 os.environ.setdefault("SLS_LAB", "1")      # diagnostic knobs are honoured in lab mode only
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
