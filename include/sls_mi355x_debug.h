@@ -39,6 +39,13 @@ int sls_debug_plan_tables(sls_ctx* ctx, int dev_slot, const sls_dims* dims, cons
 int sls_debug_plan_tables_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, int64_t d, double alpha,
                                     int64_t* md_total, uint8_t* mask_out, int32_t* dest_out, int64_t* n_idx, int32_t* idx_out);
 
+/* The text sls_plan_describe gives for the plan sls_h2_sf_plan would build from these inputs on a device with `ncu` compute
+ * units: the host symbolic pass and kernel selection only — no context, no device (tests/test_host.py compares it with the
+ * launch lists recorded in tests/golden/launch_lists.json). */
+int sls_debug_describe_launches(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                                int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, int64_t group_begin,
+                                int64_t group_end, int ncu, char* buf, int64_t buflen);
+
 #ifdef __cplusplus
 }
 #endif

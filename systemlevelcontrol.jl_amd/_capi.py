@@ -185,6 +185,8 @@ def load_library(path: str | None = None):
     lib.sls_debug_plan_tables_localized.argtypes = [vp, C.c_int, C.POINTER(sls_dims), C.POINTER(sls_plant), C.c_int64, C.c_double,
                                                     C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
                                                     C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.sls_debug_describe_launches.restype = C.c_int
+    lib.sls_debug_describe_launches.argtypes = common + [C.c_int64, C.c_int64, C.c_int, C.c_char_p, C.c_int64]
     if lib.sls_abi_version() != SLS_ABI_VERSION:
         raise ImportError(f"ABI mismatch: library {lib.sls_abi_version()} vs binding {SLS_ABI_VERSION}")
     if path is None:

@@ -24,6 +24,7 @@
 #include "../../include/sls_mi355x_debug.h"
 #include "sls_device.h"
 #include "sls_internal.h"
+#include "sls_routing.h"
 #include "sls_symbolic.h"
 
 namespace sls {
@@ -75,7 +76,6 @@ namespace {
 double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
-constexpr int kMaxLds = 160 * 1024;
 constexpr int kEventPool = 64;
 }  // namespace
 
@@ -99,25 +99,10 @@ struct sls_plan {
   int32_t* d_counters = nullptr;      // one work-queue counter per launch (tile kernel)
   unsigned char* d_big = nullptr;     // big tile launches: their carve buffers (inside the scratch workspace)
   bool has_tile = false;
-  struct Launch {
-    int kind, cls, order_off, nsub, grid, per_cu;
-    size_t lds;
-    int64_t fac_stride, vec_stride, fac_off, vec_off;
-    hipStream_t stream = nullptr;                    // aux stream (launch 0 runs on the caller's stream)
+  struct Launch : LaunchSpec {         // what kernel selection decided + what the launch runs on
+    explicit Launch(const LaunchSpec& spec) : LaunchSpec(spec) {}
+    hipStream_t stream = nullptr;      // aux stream (launch 0 runs on the caller's stream)
     hipEvent_t done = nullptr;
-    int mcap, nm_max, pl_off;                        // wave kernels
-    int nmax, mmax, nnzA_cap, nnzB_cap, vec_in_lds;   // general kernel
-    bool wide = false;                                // general kernel, ñx 97..144: Ã·Q image in the global workspace
-    bool mlds = false;                                // tile kernel (kind 5): block being inverted lives in LDS
-    int oth_rows = 16;                                // tile kernel: rows of the Ã·Q image of the block build held in LDS
-    bool two_per_cu = false;                          // tile kernel: 4-waves-per-SIMD build, two workgroups per CU
-    bool gw = false;                                  // tile kernel: the build with the projected-CG loop (dense cost Hessians)
-    bool four = false;                                // twisted kernel (kind 3): four waves per column (chain + helper wave per direction)
-    size_t lds_two = 0;                               // … LDS of the two-wave kernel for the same launch (used when the plan has other launches)
-    bool big = false;                                 // tile kernel: the carve (panels, lists, staging) in a global per-workgroup buffer, not LDS
-    int64_t big_stride = 0, big_off = 0;              // … bytes per workgroup / offset of the launch's region
-    double work = 0.0;                                // Σ ñx³ over the launch's columns (submission order)
-    int n_longest = 0;                                // largest ñx of the launch: its longest column
   };
   std::vector<Launch> launches;
   hipEvent_t ev_fork = nullptr;
@@ -844,415 +829,19 @@ static int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_pla
   if (const char* e = sls_knob("SLS_TOL")) kp.tol = std::atof(e);
   if (const char* e = sls_knob("SLS_DELTA_REL")) kp.delta_rel = std::atof(e);
   const int ncu = ctx->ncu[dev_slot];
-  const bool force_general = opt.force_tile || (sls_knob("SLS_FORCE_GENERAL") && sls_knob("SLS_FORCE_GENERAL")[0] == '1');
 
-  // ---- kernel selection: bin the subproblems by size class, build the launch list ----
-  // small wave classes (0..5) → ONE multi-class launch; mid classes (6..8) → one launch each;
-  // everything else (ñx > 64, ñu > 64, or LDS over budget) → the general workgroup kernel.
+  // kernel selection (sls_routing.cpp): the launch list in submission order, its workspace layout, S.order launch by launch
+  RoutingResult route;
   {
-    const int capA = S.max_row_A, capAc = S.max_row_At, capB = S.max_row_B, capBc = S.max_row_Bt;
-    std::vector<int32_t> bins[kNumWaveClasses + 1];   // [c] wave class c, [kNumWaveClasses] general
-    std::vector<int32_t> too_large;                   // beyond the LDS budget of every kernel of this build
-    std::vector<int32_t> wide_bin;                    // general kernel, wide variant
-    // Latency regime (the whole batch fits in one wave of workgroups, e.g. the README chain's 59 columns): the
-    // launch lasts as long as its slowest column whatever class the small ones run in, so use ONE class — the
-    // largest needed — and skip the multi-stream fork/join (≈0.1 ms per step measured with four classes).
-    int merge_cls = -1;
-    if (!force_general && (int64_t)S.subs.size() <= 4LL * ncu) {
-      const char* w64 = sls_knob("SLS_WAVE64");
-      const bool keep64 = w64 && w64[0] == '1';
-      for (const SubDesc& sd : S.subs)
-        if (keep64 || sd.cls < kNumSmallWaveClasses) merge_cls = std::max(merge_cls, sd.cls);   // (64-lane columns go to the tile kernel)
-    }
-    // Every subproblem outside the wave classes (ñx > 64 or ñu > 64) runs on the MFMA tile kernel.  SLS_TILE (experiments and
-    // the tests of the round-1 kernels): "0" = never (round-1 launch list: workgroup kernel up to ñx = 144, beyond that
-    // SLS_COL_UNSUPPORTED), "large" = only what the workgroup kernel cannot hold.
-    const char* tile_env = sls_knob("SLS_TILE");
-    const bool tile_off = tile_env && tile_env[0] == '0' && !opt.force_tile;
-    const bool tile_all = !tile_off && !(tile_env && tile_env[0] == 'l');
-    std::vector<int32_t> tile_lds_bin, tile_lds_small_bin, tile_glb_bin;   // small: ≤ 6 tile rows (two workgroups per CU)
-    std::vector<int32_t> tile_glb_small_bin;                                // block in the workspace, two panels fit twice in a CU
-    std::vector<int32_t> tile_gw_lds_bin, tile_gw_glb_bin;                  // dense cost Hessian: the build with the CG loop
-    std::vector<int32_t> tile_big_bin, tile_gw_big_bin;                     // carve beyond LDS: the big variant (global carve buffer)
-    const char* big_env = sls_knob("SLS_TILE_BIG");
-    const bool big_off = big_env && big_env[0] == '0';                      // experiments: restore SLS_COL_UNSUPPORTED beyond LDS
-    const bool big_all = big_env && big_env[0] == 'a';                      // tests: every tile column through the big variant
-    auto tile_need = [&](const SubDesc& sd, bool mlds) {
-      return tile_kernel_lds_bytes(sd.n, std::max(sd.m, 1), std::max(sd.nnzA, 1), std::max(sd.nnzB, 1), mlds);
-    };
-    auto to_tile = [&](int32_t q) {
-      const SubDesc& sd = S.subs[q];
-      if (tile_off) { too_large.push_back(q); return; }
-      const bool no_mlds = sls_knob("SLS_TILE_GLOBAL") && sls_knob("SLS_TILE_GLOBAL")[0] == '1';   // experiments
-      const int lds_maxnt = sls_knob("SLS_TILE_LDS_MAXNT") ? std::atoi(sls_knob("SLS_TILE_LDS_MAXNT")) : 6;   // beyond 6 tile rows the LDS-resident
-      // block leaves room for one workgroup per CU only; in the workspace two share the CU (random10000_d2: 69 → 65 ms)
-      auto beyond_lds = [&](std::vector<int32_t>& bigbin) { if (big_off) too_large.push_back(q); else bigbin.push_back(q); };
-      if (sd.has_w >= 2 || kp.objective == 1) {
-        if (big_all) tile_gw_big_bin.push_back(q);
-        else if (!no_mlds && tile_nt(sd.n) <= lds_maxnt && tile_need(sd, true) <= kMaxLds) tile_gw_lds_bin.push_back(q);
-        else if (tile_need(sd, false) <= kMaxLds) tile_gw_glb_bin.push_back(q);
-        else beyond_lds(tile_gw_big_bin);
-        return;
-      }
-      if (big_all) tile_big_bin.push_back(q);
-      else if (!no_mlds && tile_nt(sd.n) <= 6 && tile_need(sd, true) <= kMaxLds / 2) tile_lds_small_bin.push_back(q);
-      else if (!no_mlds && tile_nt(sd.n) <= lds_maxnt && tile_need(sd, true) <= kMaxLds) tile_lds_bin.push_back(q);
-      else if (tile_need(sd, false) <= kMaxLds / 2) tile_glb_small_bin.push_back(q);
-      else if (tile_need(sd, false) <= kMaxLds) tile_glb_bin.push_back(q);
-      else beyond_lds(tile_big_bin);         // panels / lists beyond LDS (ñx ≳ 250): the carve moves to a global buffer
-    };
-    // sum-of-norms objective: columns of the light wave classes (ñx ≤ 32) run the ADMM loop inside the one-wave kernel (its own
-    // solve as the projection, 8× the tile kernel's rate on chain-4096); everything else on the tile kernel's CG / ADMM build
-    const bool son_tile_only = sls_knob("SLS_SON_TILE") && sls_knob("SLS_SON_TILE")[0] == '1';
-    if (kp.objective == 1) merge_cls = -1;
-    const bool wave64 = sls_knob("SLS_WAVE64") && sls_knob("SLS_WAVE64")[0] == '1';
-    std::vector<int32_t> mid_cols;                           // ñx 33…64: tile kernel or 64-lane one-wave class, see below
-    for (int32_t q : S.order) {
-      SubDesc& sd = S.subs[q];
-      if (sd.has_w == 4) { sd.cls = -1; continue; }                   // member of a coupled group: solved by the group's first column
-      const bool son_wave = kp.objective == 1 && !son_tile_only && !force_general && sd.has_w < 2 && sd.cls >= 0 && sd.cls < kNumSmallWaveClasses;
-      const bool cg_build = sd.has_w >= 2 || (kp.objective == 1 && !son_wave);      // dense cost Hessian / coupled group / sum-of-norms: tile kernel, CG build
-      int cls = (force_general || cg_build) ? -1 : sd.cls;
-      // ñx 33…64: the 64-lane one-wave classes hold a whole SIMD's registers and 57–117 KiB of LDS per column for ONE wave; the
-      // tile kernel (512 threads, MFMA tiles) is faster on every workload measured — chain ñx = 43: 2.96 → 2.16 ms, ñx = 59:
-      // 7.09 → 3.70 ms, grid-32 (its 252 boundary columns next to the tile launch): 5.45 → 4.19 ms — and converges to smaller
-      // residuals.  SLS_WAVE64=1 restores the round-1 routing (tests of those classes, experiments).
-      if (cls >= kNumSmallWaveClasses && tile_all && !wave64) { mid_cols.push_back(q); continue; }      // decided after the loop
-      if (cls >= 0 && merge_cls >= 0 && cls <= merge_cls) cls = merge_cls;      // (never down: merge_cls leaves the 64-lane classes out)
-      if (cls >= 0) {
-        const int64_t need = wave_kernel_lds_bytes(cls, kp.T, std::max(sd.m, 1), capA, capAc, capB, capBc, sd.n + sd.m);
-        if (need > kMaxLds) cls = -1;
-      }
-      sd.cls = cls;
-      if (cls < 0) {
-        if (tile_all || cg_build) { to_tile(q); continue; }
-        const int64_t need = general_kernel_lds_bytes(sd.n, std::max(sd.m, 1), std::max(sd.nnzA, 1), std::max(sd.nnzB, 1), kp.T, false);
-        if (need > kMaxLds || sd.n > 96) {
-          const int64_t needw = general_kernel_lds_bytes(sd.n, std::max(sd.m, 1), std::max(sd.nnzA, 1), std::max(sd.nnzB, 1), kp.T, false, true);
-          if (needw <= kMaxLds && sd.n <= 144) wide_bin.push_back(q);
-          else to_tile(q);
-          continue;
-        }
-      }
-      bins[cls < 0 ? kNumWaveClasses : cls].push_back(q);
-    }
-    if (!mid_cols.empty()) {
-      // The tile kernel wins on these columns (see above) — unless putting them into the launch of the LDS-resident blocks
-      // costs every column of that launch LDS: a launch is sized by the maxima over its bin, and a wide ñu or long sparse
-      // rows among the ñx ≤ 64 columns shrink the Ã·Q strip (or the workgroups per CU) of all of them (random10000_d2:
-      // 145 such columns next to 5013: 64 → 70 ms).  Then they keep their one-wave classes.
-      auto plan_of = [&](const std::vector<int32_t>& a, const std::vector<int32_t>* b2) {
-        int nmax = 1, mmax = 1, na = 1, nb = 1;
-        auto acc = [&](const std::vector<int32_t>& v) {
-          for (int32_t q : v) { const SubDesc& sd = S.subs[q]; nmax = std::max(nmax, sd.n); mmax = std::max(mmax, sd.m); na = std::max(na, sd.nnzA); nb = std::max(nb, sd.nnzB); }
-        };
-        acc(a); if (b2) acc(*b2);
-        int per_cu = 1;
-        if (tile_kernel_lds_bytes(nmax, mmax, na, nb, true, 16) <= kMaxLds / 2) per_cu = 2;
-        int rows = 16;
-        const int npadL = 16 * tile_nt(nmax);
-        while (rows < npadL && tile_kernel_lds_bytes(nmax, mmax, na, nb, true, rows + 16) <= kMaxLds / per_cu) rows += 16;
-        return std::make_pair(per_cu, rows);
-      };
-      bool to_tile_ok = true;
-      if (!tile_lds_small_bin.empty()) to_tile_ok = plan_of(tile_lds_small_bin, &mid_cols) == plan_of(tile_lds_small_bin, nullptr);
-      // … and unless they are a sliver of that launch anyway: a few per cent of extra columns at the END of its queue (it is
-      // ordered by descending ñx) only lengthen its tail, while their own one-wave launches run beside it from t = 0
-      // (random10000_d2: 145 next to 5013 — 64.0 ms in their one-wave classes, 69.2 ms on the tile queue; grid-32: 252 next
-      // to 772 — 5.45 ms against 4.19 ms)
-      if (to_tile_ok && mid_cols.size() * 10 < tile_lds_small_bin.size()) to_tile_ok = false;
-      for (int32_t q : mid_cols) {
-        SubDesc& sd = S.subs[q];
-        if (to_tile_ok) { sd.cls = -1; to_tile(q); }
-        else {
-          const int64_t need = wave_kernel_lds_bytes(sd.cls, kp.T, std::max(sd.m, 1), capA, capAc, capB, capBc, sd.n + sd.m);
-          if (need > kMaxLds) { sd.cls = -1; to_tile(q); } else bins[sd.cls].push_back(q);
-        }
-      }
-    }
-    // A sliver of a small one-wave class — under 2 % of the columns of the most populated larger class (chain-4096: 22 edge columns
-    // in three classes next to 4074 interior ones) — runs in that class's launch: a launch of its own saves those few columns
-    // some registers and costs every step a stream fork and join (rocprof: kernel 1.55 ms, step 1.67 ms with four launches).
-    // Larger classes hold every smaller column (the latency regime above merges the same way).  SLS_ABSORB=0: off.
-    {
-      const char* ab = sls_knob("SLS_ABSORB");
-      if (kp.objective == 0 && !(ab && ab[0] == '0')) {
-        for (int c = 0; c < kNumSmallWaveClasses; ++c) {
-          if (bins[c].empty()) continue;
-          int big = -1;
-          for (int c2 = c + 1; c2 < kNumSmallWaveClasses; ++c2)
-            if (!bins[c2].empty() && (big < 0 || bins[c2].size() > bins[big].size())) big = c2;
-          if (big < 0 || bins[c].size() * 50 > bins[big].size()) continue;
-          // … as long as it does not raise that launch's LDS plan (a launch is sized by the maxima over its bin)
-          auto need_in_big = [&](const SubDesc& sd) { return wave_kernel_lds_bytes(big, kp.T, std::max(sd.m, 1), capA, capAc, capB, capBc, sd.n + sd.m); };
-          int64_t big_need = 0;
-          for (int32_t q : bins[big]) big_need = std::max(big_need, need_in_big(S.subs[q]));
-          std::vector<int32_t> stay;
-          for (int32_t q : bins[c]) {
-            SubDesc& sd = S.subs[q];
-            if (need_in_big(sd) <= big_need) { sd.cls = big; bins[big].push_back(q); }
-            else stay.push_back(q);
-          }
-          bins[c].swap(stay);
-          std::stable_sort(bins[big].begin(), bins[big].end(), [&](int32_t a, int32_t b) { return S.subs[a].n > S.subs[b].n; });
-        }
-      }
-    }
-    // a workgroup launch is sized by the maxima over its bin (ñx, ñu, nnz separately): move the widest on until the combination fits
-    // kind: 2 general, 4 general wide, 5 tile (block in LDS), 6 tile (block in the global workspace)
-    auto need_kind = [&](int kind, int n, int m, int a, int b) -> int64_t {
-      if (kind == 5 || kind == 6) return tile_kernel_lds_bytes(n, m, a, b, kind == 5);
-      return general_kernel_lds_bytes(n, m, a, b, kp.T, false, kind == 4);
-    };
-    auto shrink = [&](std::vector<int32_t>& gb, int kind, std::vector<int32_t>& overflow, int64_t limit = kMaxLds) {
-      auto need_of = [&](const SubDesc& sd) { return need_kind(kind, sd.n, std::max(sd.m, 1), std::max(sd.nnzA, 1), std::max(sd.nnzB, 1)); };
-      auto combined = [&]() {
-        int nmax = 1, mmax = 1, a = 1, b = 1;
-        for (int32_t q : gb) { const SubDesc& sd = S.subs[q]; nmax = std::max(nmax, sd.n); mmax = std::max(mmax, sd.m); a = std::max(a, sd.nnzA); b = std::max(b, sd.nnzB); }
-        return need_kind(kind, nmax, mmax, a, b);
-      };
-      while (!gb.empty() && combined() > limit) {
-        size_t worst = 0; int64_t wneed = -1;
-        for (size_t i = 0; i < gb.size(); ++i) { const int64_t nd = need_of(S.subs[gb[i]]); if (nd > wneed) { wneed = nd; worst = i; } }
-        overflow.push_back(gb[worst]);
-        gb.erase(gb.begin() + worst);
-      }
-    };
-    {
-      std::vector<int32_t> spill, spill2;
-      shrink(bins[kNumWaveClasses], 2, spill);
-      for (int32_t q : spill) {             // did not fit next to the others: try the wide variant
-        const SubDesc& sd = S.subs[q];
-        if (general_kernel_lds_bytes(sd.n, std::max(sd.m, 1), std::max(sd.nnzA, 1), std::max(sd.nnzB, 1), kp.T, false, true) <= kMaxLds && sd.n <= 144) wide_bin.push_back(q);
-        else to_tile(q);
-      }
-      shrink(wide_bin, 4, spill2);
-      for (int32_t q : spill2) to_tile(q);
-      std::vector<int32_t> spill3, spill4;
-      shrink(tile_lds_small_bin, 5, spill4, kMaxLds / 2);
-      for (int32_t q : spill4) tile_lds_bin.push_back(q);
-      shrink(tile_lds_bin, 5, spill3);
-      for (int32_t q : spill3) { if (tile_need(S.subs[q], false) <= kMaxLds) tile_glb_bin.push_back(q); else if (big_off) too_large.push_back(q); else tile_big_bin.push_back(q); }
-      std::vector<int32_t> spill6;
-      shrink(tile_glb_small_bin, 6, spill6, kMaxLds / 2);
-      for (int32_t q : spill6) tile_glb_bin.push_back(q);
-      shrink(tile_glb_bin, 6, big_off ? too_large : tile_big_bin);
-      std::vector<int32_t> spill5;
-      shrink(tile_gw_lds_bin, 5, spill5);
-      for (int32_t q : spill5) { if (tile_need(S.subs[q], false) <= kMaxLds) tile_gw_glb_bin.push_back(q); else if (big_off) too_large.push_back(q); else tile_gw_big_bin.push_back(q); }
-      shrink(tile_gw_glb_bin, 6, big_off ? too_large : tile_gw_big_bin);
-      // launches walk their bin in descending ñx (S.order is sorted that way; spilled entries were appended out of order)
-      auto by_n = [&](int32_t a, int32_t b) { return S.subs[a].n > S.subs[b].n; };
-      std::stable_sort(wide_bin.begin(), wide_bin.end(), by_n);
-      std::stable_sort(tile_lds_bin.begin(), tile_lds_bin.end(), by_n);
-      std::stable_sort(tile_lds_small_bin.begin(), tile_lds_small_bin.end(), by_n);
-      std::stable_sort(tile_gw_lds_bin.begin(), tile_gw_lds_bin.end(), by_n);
-      std::stable_sort(tile_gw_glb_bin.begin(), tile_gw_glb_bin.end(), by_n);
-      std::stable_sort(tile_glb_bin.begin(), tile_glb_bin.end(), by_n);
-      std::stable_sort(tile_glb_small_bin.begin(), tile_glb_small_bin.end(), by_n);
-      std::stable_sort(tile_big_bin.begin(), tile_big_bin.end(), by_n);
-      std::stable_sort(tile_gw_big_bin.begin(), tile_gw_big_bin.end(), by_n);
-    }
-    std::vector<int32_t> order2;
-    auto add_launch = [&](int kind, int cls, const std::vector<int32_t>& v) {
-      if (v.empty()) return;
-      sls_plan::Launch L{};
-      L.kind = kind; L.cls = cls; L.order_off = (int)order2.size(); L.nsub = (int)v.size();
-      int mcap = 1, nm_max = 1, nmax = 1, mmax = 1, nnzA = 1, nnzB = 1; int64_t lds = 0;
-      for (int32_t q : v) {
-        const SubDesc& sd = S.subs[q];
-        L.work += (double)sd.n * sd.n * sd.n; L.n_longest = std::max(L.n_longest, sd.n);
-        mcap = std::max(mcap, sd.m); nm_max = std::max(nm_max, sd.n + sd.m);
-        nmax = std::max(nmax, sd.n); mmax = std::max(mmax, sd.m);
-        nnzA = std::max(nnzA, sd.nnzA); nnzB = std::max(nnzB, sd.nnzB);
-      }
-      if (kind == 5 || kind == 6 || kind == 7) {
-        pl->has_tile = true;
-        L.kind = 5; L.mlds = kind == 5; L.big = kind == 7;
-        L.nmax = nmax; L.mmax = mmax; L.nnzA_cap = nnzA; L.nnzB_cap = nnzB;
-        // LDS plan: two workgroups per CU (80 KiB each) when the block, the lists and a 16-row strip of the Ã·Q image fit —
-        // the serial pivot-tile factorisation of one column then overlaps the other column's work; else one per CU.  The
-        // Ã·Q image gets as many rows (multiples of 16) as the chosen budget leaves.
-        const int npadL = 16 * tile_nt(nmax);
-        const bool no2 = sls_knob("SLS_TILE_ONE_PER_CU") && sls_knob("SLS_TILE_ONE_PER_CU")[0] == '1';   // experiments
-        bool any_general = false;
-        int ncol_max = 1;                                   // columns of the largest coupled group of the launch
-        for (int32_t q : v) {
-          any_general = any_general || S.subs[q].has_w >= 2 || kp.objective == 1;
-          if (S.subs[q].has_w == 3) ncol_max = std::max(ncol_max, S.subs[q].pad_);
-        }
-        L.gw = any_general;
-        // the CG / ADMM build needs 256 VGPRs (one 512-thread workgroup per CU); the sum-of-norms loop is thousands of
-        // latency-bound steps per column, where two workgroups of the 128-VGPR build per CU win (chain-4096: 25.7 → 19.6 s)
-        const char* gw2_env = sls_knob("SLS_GW_TWO");
-        const bool gw2 = any_general && L.mlds && (gw2_env ? gw2_env[0] == '1' : kp.objective == 1);
-        const int max_wg = (L.big || no2 || (any_general && !gw2)) ? 1 : (kTileThreads == 256 ? 4 : 2);
-        L.per_cu = 1;
-        for (int wg = max_wg; wg > 1; wg /= 2)
-          if (tile_kernel_lds_bytes(nmax, mmax, nnzA, nnzB, L.mlds, 16) <= kMaxLds / wg) { L.per_cu = wg; break; }
-        L.two_per_cu = L.per_cu * kTileWaves > 8;          // more than two waves per SIMD: the 128-VGPR build
-        const int64_t budget = kMaxLds / L.per_cu;
-        L.oth_rows = 16;
-        while (!L.big && L.oth_rows < npadL && tile_kernel_lds_bytes(nmax, mmax, nnzA, nnzB, L.mlds, L.oth_rows + 16) <= budget) L.oth_rows += 16;
-        lds = tile_kernel_lds_bytes(nmax, mmax, nnzA, nnzB, L.mlds, L.oth_rows);
-        if (L.big) {                                       // the carve goes to global memory; LDS only holds the block-reduction words
-          L.big_stride = (lds + 255) / 256 * 256;
-          lds = 256;
-        }
-        L.vec_in_lds = 0;
-        L.fac_stride = tile_kernel_fac_doubles(nmax, kp.T);
-        L.vec_stride = 3LL * (kp.T + 1) * nmax + 2LL * kp.T * (nmax + mmax);   // Δλ, r, r′; the primal iterate and its trial point
-        if (any_general) L.vec_stride += 5LL * kp.T * (nmax + mmax);            // CG on a dense Hessian: iterate, gradient, direction, G·direction (+ one temporary for coupled groups)
-        L.fac_stride *= ncol_max; L.vec_stride *= ncol_max;                     // a coupled group keeps every column's factor and vectors
-        if (kp.objective == 1) L.vec_stride += 26LL * kp.T * (nmax + mmax);      // sum-of-norms: warm-start vector + Anderson history (see the kernel)
-      } else if (kind == 2 || kind == 4) {
-        const bool wide = kind == 4;
-        L.kind = 2; L.wide = wide;
-        L.nmax = nmax; L.mmax = mmax; L.nnzA_cap = nnzA; L.nnzB_cap = nnzB;
-        lds = general_kernel_lds_bytes(nmax, mmax, nnzA, nnzB, kp.T, true, wide);
-        L.vec_in_lds = 1;
-        if (lds > kMaxLds) { lds = general_kernel_lds_bytes(nmax, mmax, nnzA, nnzB, kp.T, false, wide); L.vec_in_lds = 0; }
-        L.fac_stride = (int64_t)(kp.T + 1 + (wide ? 1 : 0)) * nmax * nmax + (wide ? (int64_t)nmax * mmax : 0);   // wide: + Ã·Q image + dense B̃
-        L.vec_stride = 3LL * (kp.T + 1) * nmax;
-        L.per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(8, kMaxLds / std::max<int64_t>(lds, 1)));
-      } else {
-        int rpl_max = 0;
-        // throughput regime (more columns than fit at once): the two T-sized vectors go to a global workspace so that
-        // twice as many waves are resident; the latency regime keeps them in LDS
-        const bool force_vg = sls_knob("SLS_VEC_GLOBAL") && sls_knob("SLS_VEC_GLOBAL")[0] == '1';   // tests / experiments
-        const bool vg = cls < kNumSmallWaveClasses && (force_vg || kp.objective == 1 || (merge_cls < 0 && !(sls_knob("SLS_VEC_LDS") && sls_knob("SLS_VEC_LDS")[0] == '1')));
-        L.vec_in_lds = vg ? 0 : 1;
-        L.vec_stride = vg ? 2LL * (kp.T + 1) * wave_class(cls).npl : 0;
-        if (kp.objective == 1) L.vec_stride += 30LL * kp.T * nm_max;            // sum-of-norms: linear term, y, u, v per (t, variable) + Anderson history (g, F, g of the last step, 2·5 differences; each 2 vectors)
-        for (int32_t q : v) {
-          const int c = S.subs[q].cls;
-          lds = std::max(lds, wave_kernel_lds_bytes(c, kp.T, mcap, capA, capAc, capB, capBc, nm_max, vg));
-          rpl_max = std::max(rpl_max, wave_class(c).rpl);
-        }
-        L.mcap = mcap; L.nm_max = nm_max;
-        L.fac_stride = (int64_t)(kp.T + 1) * rpl_max * 64;
-        // latency regime: two waves per column (twisted factorisation) when there are far fewer columns than SIMDs
-        const bool no_tw = sls_knob("SLS_NO_TWISTED") && sls_knob("SLS_NO_TWISTED")[0] == '1';
-        if (!no_tw && !vg && merge_cls >= 0 && cls == merge_cls && cls < kNumSmallWaveClasses && kp.T >= 3 &&
-            (int64_t)v.size() <= 2LL * ncu) {
-          const int64_t tl = twisted_kernel_lds_bytes(cls, kp.T, mcap, capA, capAc, capB, capBc, nm_max);
-          if (tl <= kMaxLds) {
-            L.kind = 3; lds = tl;
-            // Opt-in (SLS_P_LDS=1): keep the pivot blocks in LDS when the whole column fits in the CU.  It removes the P_k
-            // workspace traffic (README: 23.8 MB → ≈0.7 MB per launch) but measured 6 % SLOWER (0.171 vs 0.161 ms): the
-            // P_k reads then queue on the same LDS pipe / lgkmcnt as the gathers of the step instead of overlapping on
-            // the VMEM path, and 150 GB/s of workspace traffic is far from any HBM limit.  Default = the faster one.
-            const int64_t pl_bytes = (int64_t)(kp.T + 1) * nmax * nmax * 8;
-            const bool want_pl = sls_knob("SLS_P_LDS") && sls_knob("SLS_P_LDS")[0] == '1';
-            if (want_pl && tl + pl_bytes <= kMaxLds) { L.pl_off = (int)tl; lds = tl + pl_bytes; }
-            // Round 3: at most one column per CU → FOUR waves per column (sls_twisted4_kernel.hip): each direction's chain wave
-            // keeps only Gauss–Jordan + store + sweep, a helper wave on another SIMD builds the next block behind its pivots.
-            // NPL = 32 classes (the 8×8 lane grid); SLS_TWISTED4=0 restores the two-wave kernel.
-            const char* t4 = sls_knob("SLS_TWISTED4");
-            // OPEN DEFECT of the four-wave kernel, fenced off here (found by the end-of-round fuzz, tools/t4_vs_t2_scan.py,
-            // tools/t4_small_T.py): on short horizons (T ≤ 6) columns with small index sets (ñx ≤ 12: members of the 16-lane classes
-            // that a one-launch latency plan merges into its 32-lane class) come out with residuals of 1e-8…1e-6 that do not
-            // contract, where the two-wave kernel reaches 1e-16 on the same launch (fuzz seeds 11, 65, 290, 297; the same
-            // plant and columns are clean from T = 7 on, and the README chain's edge columns — ñx = 11 at T = 29 — always were).
-            // Traced (tools/t4_dump_P.py): one diagonal entry of block c+1 whose Schur complement cancels to zero — the
-            // elimination form resolves it to δ exactly where the explicit products land on ±1e-6, and the 1/δ entry amplifies the
-            // residual's rounding noise into a floor of 1e-7.  Until such a direction is damped, a launch that combines a horizon
-            // below 7 with an index set below 13 takes the two-wave kernel.  470 fuzz seeds: no status or value difference between the two kernels with the fence.
-            int n_least = 1 << 30;
-            for (int32_t q : v) n_least = std::min(n_least, S.subs[q].n);
-            const int n_floor = sls_knob("SLS_T4_NMIN") ? std::atoi(sls_knob("SLS_T4_NMIN")) : 13;
-            const int t_floor = sls_knob("SLS_T4_TMIN") ? std::atoi(sls_knob("SLS_T4_TMIN")) : 7;
-            if (!L.pl_off && wave_class(cls).npl == 32 && (int64_t)v.size() <= (int64_t)ncu && !(t4 && t4[0] == '0') && (n_least >= n_floor || kp.T >= t_floor)) {
-              const int64_t t4l = twisted4_kernel_lds_bytes(cls, kp.T, mcap, capA, capAc, capB, capBc, nm_max);
-              if (t4l <= kMaxLds) { L.four = true; L.lds_two = (size_t)lds; lds = t4l; }
-            }
-          }
-        }
-        L.per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(cls < kNumSmallWaveClasses ? 16 : 8, kMaxLds / std::max<int64_t>(lds, 1)));
-        if (L.four) L.per_cu = 1;
-        // whole waves per SIMD: a ninth wave on a CU puts three on one SIMD, and a round lasts as long as its slowest wave
-        // (chain Nx = 65 536: 29 rounds of 2260 waves 34.2 ms, 32 rounds of 2048 waves → see DESIGN §6)
-        if (L.per_cu > 8 && !sls_knob("SLS_PER_CU_ANY")) L.per_cu -= L.per_cu % 4;      // (below two per SIMD every wave counts)
-      }
-      L.lds = (size_t)lds;
-      if (const char* e = sls_knob("SLS_MAX_PER_CU")) L.per_cu = std::max(1, std::min(L.per_cu, std::atoi(e)));   // experiments
-      L.grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)L.nsub, (int64_t)ncu * L.per_cu));
-      // Static round-robin kernels (one wave per column): every wave of a full grid does ⌈nsub/grid⌉ columns whether or not
-      // the last round is full, so the launch lasts that many rounds anyway — give each wave exactly that many and keep the
-      // fewest waves resident (chain-4096: 4074 columns on 2304 slots = 2 rounds; 2037 waves, 8 per CU instead of 9, each
-      // SIMD holds 2 waves instead of up to 3).  The tile kernel takes work from a queue and keeps its full grid.
-      if (L.big) {
-        // a big column's factor slots are tens of MB (ñx = 1024, T = 25: 119 MB): the resident workgroups are capped by memory, the
-        // work queue feeds them the rest
-        const double per_wg = 8.0 * ((double)L.fac_stride + (double)L.vec_stride) + (double)L.big_stride;
-        const int64_t cap = (int64_t)std::max(1.0, (48.0 * 1024 * 1024 * 1024) / per_wg);
-        L.grid = (int)std::max<int64_t>(1, std::min<int64_t>(L.grid, cap));
-      }
-      if (kind == 1 && kp.objective == 1) pl->has_tile = true;          // sum-of-norms: the one-wave kernel draws columns from a queue too
-      if (kind == 1 && kp.objective != 1 && !sls_knob("SLS_FULL_GRID")) {
-        const int64_t rounds = ((int64_t)L.nsub + L.grid - 1) / L.grid;
-        L.grid = (int)(((int64_t)L.nsub + rounds - 1) / rounds);
-      }
-      order2.insert(order2.end(), v.begin(), v.end());
-      pl->launches.push_back(L);
-    };
-    for (int c = kNumWaveClasses - 1; c >= 0; --c) add_launch(1, c, bins[c]);     // largest (longest) class first
-    add_launch(2, -1, bins[kNumWaveClasses]);
-    add_launch(4, -1, wide_bin);
-    add_launch(6, -1, tile_glb_bin);
-    add_launch(6, -1, tile_glb_small_bin);
-    add_launch(5, -1, tile_lds_bin);
-    add_launch(5, -1, tile_lds_small_bin);
-    add_launch(6, -1, tile_gw_glb_bin);
-    add_launch(5, -1, tile_gw_lds_bin);
-    add_launch(7, -1, tile_big_bin);
-    add_launch(7, -1, tile_gw_big_bin);
-    S.order.swap(order2);
-    pl->too_large_subs = too_large;
-    pl->info_unsupported = (int64_t)too_large.size();
-    // A CU-saturating persistent launch leaves no LDS for the workgroups of the other size classes, which could then only
-    // start in its tail.  Keep that many workgroup slots free: the small launches run beside it whenever they are dispatched.
-    // Submission order: launches of a handful of workgroups (edge classes of a chain: 6–8 columns) go first.  Behind a launch
-    // that fills every LDS slot they would wait for its first round to drain and then run alone as the tail of the pass
-    // (chain-4096: the three edge classes ended 0.35 ms after the 4074-column launch); submitted first they start at t = 0
-    // and the big launch fills in around them.
-    // Submission order = critical path first: the launch that outlasts the others takes its slots first and the shorter ones run
-    // in the slots its last round leaves idle.  grid-32: the tile kernel (772 columns on 512 slots: its second round uses half of them)
-    // alone 4.05 ms, the 252 one-wave columns alone 1.60 ms; submitted wave-first the wave workgroups' 84 KiB of LDS kept
-    // every CU at ONE tile workgroup for those 1.6 ms and the pass took the sum, 5.47 ms.
-    if (pl->launches.size() > 1 && !sls_knob("SLS_NO_TINY_FIRST")) {
-      std::stable_sort(pl->launches.begin(), pl->launches.end(), [&](const sls_plan::Launch& a, const sls_plan::Launch& b) {
-        // the launch holding the longest columns first (random10000_d2: 119 columns of ñx up to 322 take ≈25 ms each — started
-        // third they were the tail of the pass: 78 ms against 62), then by total work
-        if (a.n_longest != b.n_longest) return a.n_longest > b.n_longest;
-        return a.work > b.work;
-      });
-      if (sls_knob("SLS_TINY_FIRST"))
-        std::stable_partition(pl->launches.begin(), pl->launches.end(),
-                              [&](const sls_plan::Launch& L) { return (int64_t)L.grid * 16 <= ncu; });
-    }
-    if (pl->launches.size() > 1) {
-      auto& L0 = pl->launches[0];
-      int64_t others = 0; bool fit = true;
-      for (size_t li = 1; li < pl->launches.size(); ++li) { others += pl->launches[li].grid; fit = fit && pl->launches[li].lds <= L0.lds; }
-      if (fit && L0.kind == 1 && (int64_t)L0.grid == (int64_t)ncu * L0.per_cu && others < L0.grid / 4) L0.grid -= (int)others;
-    }
-    // The four-wave twisted kernel owns a whole CU (256 threads at up to 512 registers): beside another launch — grid-32's four
-    // corner columns next to the tile kernel's persistent workgroups — it can only start once a CU has drained completely
-    // (rocprof: dispatched at t = 0, finished with the pass).  It is the pure latency regime's kernel: plans with one launch.
-    if (pl->launches.size() > 1)
-      for (auto& L : pl->launches)
-        if (L.four) {
-          L.four = false; L.lds = L.lds_two;
-          L.per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(16, kMaxLds / std::max<int64_t>((int64_t)L.lds, 1)));
-          L.grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)L.nsub, (int64_t)ncu * L.per_cu));
-        }
-    kp.w_nzA = capA; kp.w_nzAc = capAc; kp.w_nzB = capB; kp.w_nzBc = capBc;
-    for (const auto& L : pl->launches) {
-      if (L.lds > (size_t)kMaxLds)
-        return bail(fail(ctx, SLS_EUNSUPPORTED, "internal: a launch needs " + std::to_string(L.lds) + " B of LDS (160 KiB available)"));
-    }
+    std::string msg;
+    rc = build_launch_list(S, kp.T, kp.objective, ncu, opt.force_tile, RoutingKnobs::from_env(), route, msg);
+    if (rc) return bail(fail(ctx, rc, msg));
   }
+  pl->launches = std::vector<sls_plan::Launch>(route.launches.begin(), route.launches.end());
+  pl->has_tile = route.has_tile;
+  pl->too_large_subs = route.too_large;
+  pl->info_unsupported = (int64_t)route.too_large.size();
+  kp.w_nzA = S.max_row_A; kp.w_nzAc = S.max_row_At; kp.w_nzB = S.max_row_B; kp.w_nzBc = S.max_row_Bt;
 
 #define UP(vec, field)                                         \
   do { int rc__ = upload(pl, vec, &kp.field); if (rc__) return bail(rc__); } while (0)
@@ -1278,14 +867,7 @@ static int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_pla
 #undef UP
   if (want_packed && (rc = upload(pl, S.pdest_pool, &pl->d_pdest))) return bail(rc);
   {
-    size_t fac_need = 0, vec_need = 0, big_need = 0;     // launches of one execute run CONCURRENTLY: disjoint workspace regions
-    for (auto& L : pl->launches) {
-      L.fac_stride = (L.fac_stride + 31) / 32 * 32;        // every workgroup's region starts on a 256-B boundary
-      L.vec_stride = (L.vec_stride + 31) / 32 * 32;
-      L.fac_off = (int64_t)fac_need; fac_need += (size_t)L.fac_stride * L.grid;
-      if (!L.vec_in_lds) { L.vec_off = (int64_t)vec_need; vec_need += (size_t)L.vec_stride * L.grid; }
-      if (L.big) { L.big_off = (int64_t)big_need; big_need += (size_t)L.big_stride * L.grid; }
-    }
+    const size_t fac_need = route.fac_doubles, vec_need = route.vec_doubles, big_need = route.big_bytes;
     // the two big scratch workspaces (never initialised, never read before written) come from the context's cache
     const size_t need = (std::max<size_t>(fac_need, 1) + vec_need + 32) * sizeof(double) + 512 + big_need + 256;
     sls_ctx::Slot& sl = ctx->slots[dev_slot];
@@ -1697,20 +1279,19 @@ int sls_plan_execute(sls_plan* plan, void* hip_stream, double* d_values, int pac
     q.order_off = L.order_off; q.nsub = L.nsub; q.fac_stride = L.fac_stride;
     q.fac_ws = kp.fac_ws + L.fac_off;
     hipError_t e;
-    if (L.kind == 2 || L.kind == 5) {
+    const bool tile = L.kind == LaunchKind::Tile;
+    if (tile || L.kind == LaunchKind::Workgroup) {
       q.nmax = L.nmax; q.mmax = L.mmax; q.nnzA_cap = L.nnzA_cap; q.nnzB_cap = L.nnzB_cap;
       q.vec_in_lds = L.vec_in_lds; q.vec_stride = L.vec_stride; q.vec_ws = kp.vec_ws ? kp.vec_ws + L.vec_off : nullptr;
       q.tile_oth_rows = L.oth_rows;
-      q.work_counter = (L.kind == 5) ? plan->d_counters + li : nullptr;
-      bool wpe4 = L.two_per_cu;
-      if (const char* ev = sls_knob("SLS_TILE_WPE")) wpe4 = ev[0] == '4';      // experiments: compile variant independent of the grid
+      q.work_counter = tile ? plan->d_counters + li : nullptr;
       q.big_ws = L.big ? plan->d_big + L.big_off : nullptr; q.big_stride = L.big_stride;
-      e = (L.kind == 5) ? launch_tile(q, L.grid, L.lds, ls, L.mlds, wpe4, L.gw, L.big) : launch_general(q, L.grid, L.lds, ls, L.wide);
+      e = tile ? launch_tile(q, L.grid, L.lds, ls, L.mlds, L.two_per_cu, L.gw, L.big) : launch_general(q, L.grid, L.lds, ls, L.wide);
     } else {
       q.w_mcap = L.mcap; q.w_nm_max = L.nm_max; q.w_pl_off = L.pl_off;
-      q.work_counter = (kp.objective == 1 && L.kind == 1) ? plan->d_counters + li : nullptr;
+      q.work_counter = (kp.objective == 1 && L.kind == LaunchKind::OneWave) ? plan->d_counters + li : nullptr;
       q.vec_in_lds = L.vec_in_lds; q.vec_stride = L.vec_stride; q.vec_ws = kp.vec_ws ? kp.vec_ws + L.vec_off : nullptr;
-      e = (L.kind == 3) ? (L.four ? launch_twisted4(L.cls, q, L.grid, L.lds, ls) : launch_twisted(L.cls, q, L.grid, L.lds, ls))
+      e = (L.kind == LaunchKind::Twisted) ? (L.four ? launch_twisted4(L.cls, q, L.grid, L.lds, ls) : launch_twisted(L.cls, q, L.grid, L.lds, ls))
                         : launch_wave(L.cls, q, L.grid, L.lds, ls);
     }
     if (e != hipSuccess) return hipfail(plan->ctx, e, "kernel launch");
@@ -1839,23 +1420,29 @@ static int fetch_status_raw(sls_plan* plan, int32_t* col_status, double* residua
 int sls_plan_describe(const sls_plan* plan, char* buf, int64_t buflen) {
   if (!plan || !buf || buflen <= 0) return fail(nullptr, SLS_EINVAL, "null argument");
   std::string d;
-  for (const auto& L : plan->launches) {
-    char line[256];
-    if (L.kind == 5)
-      std::snprintf(line, sizeof line, "h2_column_tile_kernel<%s%s%s> nsub=%d grid=%d block=512 lds=%zu nmax=%d per_cu=%d;", L.mlds ? "block_in_LDS" : "block_in_workspace", L.big ? ",carve_in_workspace" : "", L.gw ? ",dense_hessian_cg" : "", L.nsub, L.grid, L.lds, L.nmax, L.per_cu);
-    else if (L.kind == 2)
-      std::snprintf(line, sizeof line, "h2_column_general_kernel%s nsub=%d grid=%d block=256 lds=%zu;", L.wide ? "<wide>" : "", L.nsub, L.grid, L.lds);
-    else if (L.kind == 3 && L.four)
-      std::snprintf(line, sizeof line, "h2_column_twisted4_kernel<%d,%d> nsub=%d grid=%d block=256 lds=%zu;", wave_class(L.cls).npl,
-                    wave_class(L.cls).rpl, L.nsub, L.grid, L.lds);
-    else if (L.kind == 3)
-      std::snprintf(line, sizeof line, "h2_column_twisted_kernel<%d,%d,%s> nsub=%d grid=%d block=128 lds=%zu;", wave_class(L.cls).npl,
-                    wave_class(L.cls).rpl, L.pl_off ? "P_in_LDS" : "P_in_workspace", L.nsub, L.grid, L.lds);
-    else
-      std::snprintf(line, sizeof line, "h2_column_wave_kernel<%d,%d> nsub=%d grid=%d block=64 lds=%zu;", wave_class(L.cls).npl,
-                    wave_class(L.cls).rpl, L.nsub, L.grid, L.lds);
-    d += line;
-  }
+  for (const auto& L : plan->launches) d += describe_launch(L);
+  std::snprintf(buf, (size_t)buflen, "%s", d.c_str());
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): the launch list sls_plan_describe would print for a plan of these inputs on a
+ * device with `ncu` compute units — symbolic pass + kernel selection on the host, no context, no device */
+int sls_debug_describe_launches(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                                int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, int64_t group_begin,
+                                int64_t group_end, int ncu, char* buf, int64_t buflen) {
+  if (!buf || buflen <= 0 || ncu <= 0) return fail(nullptr, SLS_EINVAL, "bad argument");
+  Inputs in{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
+  std::string msg;
+  int rc = validate_inputs(in, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  Symbolic S;
+  rc = build_symbolic(in, group_begin, group_end, S, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  RoutingResult route;
+  rc = build_launch_list(S, (int)S.T, (dims->flags & SLS_SOLVE_SUM_OF_NORMS) ? 1 : 0, ncu, false, RoutingKnobs::from_env(), route, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  std::string d;
+  for (const LaunchSpec& L : route.launches) d += describe_launch(L);
   std::snprintf(buf, (size_t)buflen, "%s", d.c_str());
   return 0;
 }
@@ -2062,7 +1649,7 @@ static int attach_refinement(sls_plan* pl, const sls_dims* dims, const sls_plant
   if (pl->refine) { *n_refined = pl->refine->info.n_subproblems; return sls_plan_fetch_status(pl, stt.data(), res.data(), its.data()); }
   int rc = fetch_status_raw(pl, stt.data(), res.data(), its.data());
   if (rc) return rc;
-  const bool all_tile = pl->launches.size() == 1 && pl->launches[0].kind == 5;
+  const bool all_tile = pl->launches.size() == 1 && pl->launches[0].kind == LaunchKind::Tile;
   if (all_tile) return 0;
   std::vector<int64_t> gptr_all, gcols_all;
   Inputs in0{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
@@ -2077,7 +1664,7 @@ static int attach_refinement(sls_plan* pl, const sls_dims* dims, const sls_plant
   // a column they flag infeasible gets the tile kernel's verdict
   std::vector<char> on_twisted((size_t)ns, 0);
   for (const auto& L : pl->launches)
-    if (L.kind == 3)
+    if (L.kind == LaunchKind::Twisted)
       for (int i = 0; i < L.nsub; ++i) {
         const int64_t q = pl->sym.order[(size_t)L.order_off + i];
         if (q >= 0 && q < ns) on_twisted[(size_t)q] = 1;

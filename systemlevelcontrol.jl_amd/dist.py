@@ -66,6 +66,18 @@ def packed_layout(P, S, groups, group_range, index_base=0):
     return dest[: npk.value], nval.value, info.asdict()
 
 
+def describe_launches(P, S, groups, group_range, ncu, objective="h2", index_base=0):
+    """Host-only view of a shard's launch list (sls_debug_describe_launches): the text `Plan.describe()` gives for the same
+    inputs on a device with `ncu` compute units, from the symbolic pass and kernel selection alone."""
+    from .synthesis import _objective_flags
+    lib = _capi.load_library()
+    m = _capi.Marshalled(P, S[0], S[1], groups, index_base=index_base, flags=_objective_flags(objective))
+    gb, ge = (0, m.ngroups if groups is not None else P.Nx) if group_range is None else group_range
+    buf = C.create_string_buffer(4096)
+    _capi.check(lib.sls_debug_describe_launches(*m.common_args(), gb, ge, int(ncu), buf, len(buf)))
+    return buf.value.decode()
+
+
 class HipLocalSolver:
     """The product's local solver: a device plan over this rank's shard."""
 

@@ -2,7 +2,8 @@
 // built and run by tests/test_host.py::test_symbolic_pass_under_sanitizers with g++ -fsanitize=address,undefined.  Drives every
 // host-only entry the C ABI forwards to — mask recipe, validation, index sets, the full symbolic pass in its four table layouts
 // (explicit / compact × packed / mask order), shard ranges, caller groups (decoupled and coupled), cost model, the inputs of
-// the two device passes, the closed-loop FIR operator — on a chain, a 2-D grid and a random plant, in both index bases, plus
+// the two device passes, the closed-loop FIR operator, kernel selection (csrc/sls_routing.cpp: the launch list of every shard for
+// 1, 8 and 256 CUs, both objectives, with and without force_tile) — on a chain, a 2-D grid and a random plant, in both index bases, plus
 // malformed inputs that must be refused without touching memory out of bounds.  Exit code 0 = clean.
 #include <cstdio>
 #include <cstdlib>
@@ -10,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "../../systemlevelcontrol.jl_amd/csrc/sls_routing.h"
 #include "../../systemlevelcontrol.jl_amd/csrc/sls_symbolic.h"
 
 namespace {
@@ -107,6 +109,38 @@ Masks make_masks(const Plant& P, int64_t d, int64_t T, double alpha, int base) {
   return M;
 }
 
+// Kernel selection on a finished symbolic pass.  Invariants only (the launch lists themselves: tests/golden/launch_lists.json):
+// every column that is neither too large nor a member of a coupled group sits in exactly one launch's slice of S.order,
+// grid ≥ 1, LDS within 160 KiB, the launches' workspace regions disjoint and inside the reported totals.
+void check_routing(const sls::Symbolic& S0) {
+  for (int ncu : {1, 8, 256})
+    for (int objective = 0; objective < 2; ++objective)
+      for (int force_tile = 0; force_tile < 2; ++force_tile) {
+        sls::Symbolic S = S0;
+        sls::RoutingResult R;
+        std::string msg;
+        const int rc = sls::build_launch_list(S, (int)S.T, objective, ncu, force_tile != 0, sls::RoutingKnobs{}, R, msg);
+        if (rc == SLS_EUNSUPPORTED) continue;
+        EXPECT(rc == 0, "build_launch_list");
+        std::vector<int> seen(S.subs.size(), 0);
+        for (int32_t q : R.too_large) seen[(size_t)q] -= 1 << 20;
+        int64_t fac_end = 0, vec_end = 0, big_end = 0;       // offsets ascend in submission order: disjoint iff each starts at the last end
+        for (const sls::LaunchSpec& L : R.launches) {
+          EXPECT(L.grid >= 1 && L.nsub >= 1 && L.lds <= (size_t)sls::kMaxLds, "launch grid / LDS");
+          EXPECT(L.order_off >= 0 && (size_t)L.order_off + (size_t)L.nsub <= S.order.size(), "launch slice of S.order");
+          for (int i = 0; i < L.nsub; ++i) seen[(size_t)S.order[(size_t)L.order_off + i]] += 1;
+          EXPECT(L.fac_off >= fac_end, "factor workspace regions overlap"); fac_end = L.fac_off + L.fac_stride * L.grid;
+          if (!L.vec_in_lds) { EXPECT(L.vec_off >= vec_end, "vector workspace regions overlap"); vec_end = L.vec_off + L.vec_stride * L.grid; }
+          if (L.big) { EXPECT(L.big_off >= big_end, "carve workspace regions overlap"); big_end = L.big_off + L.big_stride * L.grid; }
+        }
+        EXPECT((size_t)fac_end <= R.fac_doubles && (size_t)vec_end <= R.vec_doubles && (size_t)big_end <= R.big_bytes, "workspace totals");
+        for (size_t q = 0; q < S.subs.size(); ++q) {
+          const bool member = S0.subs[q].has_w == 4;
+          EXPECT(seen[q] == (member ? 0 : 1) || (seen[q] == -(1 << 20) && !member), "column not in exactly one launch");
+        }
+      }
+}
+
 void exercise(const Plant& P, int64_t d, int64_t T, int base, bool irregular, const char* name) {
   Masks M = make_masks(P, d, T, 1.5, base);
   if (irregular) {                                    // a stored-false entry: forces the explicit tables (no compact layout)
@@ -146,6 +180,7 @@ void exercise(const Plant& P, int64_t d, int64_t T, int base, bool irregular, co
           EXPECT(rc == 0, "build_symbolic");
           if (rc) { std::fprintf(stderr, "  %s: %s\n", name, msg.c_str()); continue; }
           total_packed += S.n_packed;
+          check_routing(S);
           EXPECT(nvals < 0 || nvals == S.n_values, "n_values differs between shards");
           nvals = S.n_values;
           if (packed) {

@@ -268,3 +268,16 @@ def test_device_resident_route_solves_like_the_mask_route(slc, gpu_ctx, golden_r
     with pytest.raises(slc.SLSError) as ei:
         slc.SLS_H2_localized(Pn, 4, 10, 1.5, ctx=gpu_ctx)
     assert ei.value.code == slc._capi.SLS_EUNSUPPORTED
+
+
+def test_live_plan_describes_itself_like_the_host_only_view(slc, gpu_ctx):
+    """The two entry points to kernel selection cannot drift: `Plan.describe()` of a live plan equals the host-only
+    sls_debug_describe_launches computed with this device's own CU count (README chain, grid-32, chain-4096)."""
+    import torch
+    ncu = int(torch.cuda.get_device_properties(gpu_ctx.devices[0]).multi_processor_count)
+    for name in ("readme_chain", "grid32", "chain4096"):
+        P, S, _ = slc.workloads.make_workload(name)
+        plan = slc.Plan(gpu_ctx, P, S)
+        live = plan.describe()
+        plan.close()
+        assert live and live == slc.dist.describe_launches(P, S, None, None, ncu), name

@@ -250,7 +250,7 @@ def test_symbolic_pass_survives_fork(slc):
 
 
 def test_symbolic_pass_under_sanitizers(tmp_path):
-    """The host symbolic pass (csrc/sls_symbolic.cpp: plain C++, no HIP) compiled by g++ with AddressSanitizer and
+    """The host symbolic pass and kernel selection (csrc/sls_symbolic.cpp, csrc/sls_routing.cpp: plain C++, no HIP) compiled by g++ with AddressSanitizer and
     UndefinedBehaviorSanitizer and driven by tests/host_sanitize/sanitize_symbolic.cpp over chain / grid / random plants, both
     index bases, all four table layouts, shard ranges with an empty shard, caller groups, the device passes' input builders, the
     closed-loop operator and malformed inputs.  (GPU sanitizers are not available on this pool; this is the CPU build.)"""
@@ -259,8 +259,9 @@ def test_symbolic_pass_under_sanitizers(tmp_path):
     if shutil.which("g++") is None:
         pytest.skip("g++ not available")
     here = os.path.dirname(os.path.abspath(__file__))
-    src = [os.path.join(here, "host_sanitize", "sanitize_symbolic.cpp"),
-           os.path.join(here, "..", "systemlevelcontrol.jl_amd", "csrc", "sls_symbolic.cpp")]
+    csrc = os.path.join(here, "..", "systemlevelcontrol.jl_amd", "csrc")
+    src = [os.path.join(here, "host_sanitize", "sanitize_symbolic.cpp"), os.path.join(csrc, "sls_symbolic.cpp"),
+           os.path.join(csrc, "sls_routing.cpp")]
     exe = str(tmp_path / "sanitize_symbolic")
     # sls_device.h marks a few size helpers __host__ __device__ for hipcc; g++ sees plain functions
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-D__host__=", "-D__device__=", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
@@ -271,6 +272,35 @@ def test_symbolic_pass_under_sanitizers(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     assert "sanitize_symbolic: clean" in r.stdout and "runtime error" not in r.stderr
+
+
+def _launch_list_cases():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden_launch_lists", os.path.join(GOLDEN, "make_golden_launch_lists.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_host_launch_lists_match_the_recorded_plans(slc):
+    """Kernel selection (csrc/sls_routing.cpp) without a device: for every case of tests/golden/make_golden_launch_lists.py,
+    sls_debug_describe_launches with the CU count of the recording device gives, character for character, the string that
+    `Plan.describe()` gave for the live plan on the MI355X (tests/golden/launch_lists.json).  A routing change shows up here;
+    an intended one regenerates the golden file on the GPU box."""
+    gen = _launch_list_cases()
+    with open(os.path.join(GOLDEN, "launch_lists.json")) as f:
+        golden = json.load(f)
+    cases = gen.cases(slc)
+    assert {c["name"] for c in cases} == set(golden["cases"])
+    wrong = {}
+    for case in cases:
+        P, S, groups = gen.problem(slc, case["plant"])
+        with gen.knobs(case["env"]):
+            got = slc.dist.describe_launches(P, S, groups, gen.group_range(slc, case, P, S, groups), golden["ncu"],
+                                             objective=case["objective"])
+        if got != golden["cases"][case["name"]]:
+            wrong[case["name"]] = (got, golden["cases"][case["name"]])
+    assert not wrong, wrong
 
 
 def test_graft_entry_build_runs():
