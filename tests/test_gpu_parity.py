@@ -12,9 +12,9 @@ import pytest
 import scipy.sparse as sp
 
 from conftest import GOLDEN, flat_phi, split_vals
+from oracle_c import TOL, c_oracle_flat as _c_oracle_flat
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-8
 
 
 def _flat(slc, P, S, I=None, ctx=None):
@@ -333,15 +333,6 @@ def test_rccl_all_gather_path_single_rank():
     p_.join(60)
     assert p_.exitcode == 0 and backend == "nccl"
     assert e_sync < TOL and e_pipe < TOL
-
-
-def _c_oracle_flat(slc, P, S, cols):
-    """Φ values of the given columns from the C restatement, in mask order (zeros elsewhere) + per-column status."""
-    import sls_oracle as o
-    import sls_oracle_cport as cp
-    Po = o.OraclePlant(P.A, P.B1, P.B2)
-    ox, ou, info = cp.SLS_H2(Po, S, cols=cols, nthreads=8)
-    return np.concatenate([flat_phi(ox, S[0]), flat_phi(ou, S[1])]), info
 
 
 @pytest.mark.parametrize("four", ["1", "0"])
