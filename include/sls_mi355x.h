@@ -264,6 +264,34 @@ int  sls_plan_refine(sls_plan* plan, const sls_dims* dims, const sls_plant* P,
                      const sls_csc_bool* Sx, const sls_csc_bool* Su,
                      int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols,
                      void* hip_stream, double* d_values, int packed, int64_t* n_refined);
+/* ---- objective value of every column, evaluated on the device from the written Φ ------------------------------------------
+ * The number the reference's JuMP model calls objective_value(problem) (src/synthesis.jl:52): per subproblem the cost it
+ * minimised, at the point that was written — Σₜ‖[C̃1 D̃12]Φ̃[t]B̃1 + D̃11‖²_F for the 𝓗₂ objective (the ridge term of
+ * sls_set_ridge included: it is part of what the column minimised), Σₜ‖[C̃1 D̃12]Φ̃[t]B̃1‖₂ for SLS_SOLVE_SUM_OF_NORMS — and
+ * their sum, the squared 𝓗₂ norm of the closed loop.  A pass of its own over the value array (csrc/sls_objective.hip), so it
+ * reports whatever was written last, an attached refinement included.  Conventions:
+ *  - a coupled group (non-diagonal B1[c_j,c_j]) has ONE joint value: its first column carries it, its other columns report
+ *    0.0, so the array always sums to the total;
+ *  - columns that are not SLS_COL_OK are evaluated like any other, at the least-squares point that was written;
+ *    SLS_COL_TRIVIAL gives the constant T·‖D̃11[:,c]‖²;
+ *  - a column with B1[c,c] = 0 has a constant cost; the engine returns its minimum-norm point and reports that norm
+ *    (Σz²) plus the constant — the objective it minimised;
+ *  - bit-identical from call to call and between the two layouts (fixed summation order, no floating-point atomics).
+ * sls_plan_objective: enqueue on hip_stream after the execute that wrote d_values (layout `packed` as in sls_plan_execute);
+ *   DEVICE outputs d_col_objective[n_subproblems] and d_total[1], either may be NULL.  Asynchronous like sls_plan_execute.
+ * sls_plan_fetch_objective: the same on the plan's stream (which first waits for the plan's last execute) into plan-owned
+ *   buffers, waits, copies to the HOST arrays col_objective[n_subproblems] / total (each nullable).                        */
+int  sls_plan_objective(sls_plan* plan, void* hip_stream, const double* d_values, int packed,
+                        double* d_col_objective, double* d_total);
+int  sls_plan_fetch_objective(sls_plan* plan, const double* d_values, int packed, double* col_objective, double* total);
+/* One-shot calls: opt in per context (default off: the one-shot calls do exactly what they do today).  With the option on,
+ * sls_h2_sf_solve, sls_h2_sf_solve_batch (composite order: plant 0's columns, then plant 1's, …) and
+ * sls_h2_sf_solve_localized evaluate on each device after the last launch (refinement included) and before the download.
+ * sls_ctx_last_objective returns the values of the last such call in col_status order (n = its number of subproblems;
+ * col_objective nullable).  SLS_EUNSUPPORTED after a call whose group list had overlapping groups (that Φ is a sum of
+ * layers: no single objective belongs to a column); SLS_EINVAL when no solve has run with the option on, or n is wrong.   */
+int  sls_ctx_want_objective(sls_ctx* ctx, int on);
+int  sls_ctx_last_objective(sls_ctx* ctx, double* col_objective, int64_t n, double* total);
 /* average device time of the solve kernel over the launches since the last call, from
  * HIP events recorded on the launch stream around every sls_plan_execute.             */
 int  sls_plan_kernel_time_ms(sls_plan* plan, double* avg_ms, int64_t* n_launches);

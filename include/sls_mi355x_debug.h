@@ -46,6 +46,16 @@ int sls_debug_describe_launches(const sls_dims* dims, const sls_plant* P, const 
                                 int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, int64_t group_begin,
                                 int64_t group_end, int ncu, char* buf, int64_t buflen);
 
+/* Host twin of sls_plan_objective (csrc/sls_objective.cpp): the host symbolic pass with explicit tables over all groups, then
+ * the same formulas from HOST value arrays (phix_vals[t] / phiu_vals[t] as sls_h2_sf_solve fills them) in one serial loop.
+ * Needs no device.  ridge_x / ridge_u: the weights of sls_set_ridge (Nx / Nu, NULL = none).  Outputs, each nullable:
+ * col_objective[n_subproblems] in col_status order, *total, and per column the number of products its value sums
+ * (col_terms) and the sum of their absolute values (col_abs) — what a bound on the summation order needs. */
+int sls_debug_objective_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                             int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, const double* ridge_x,
+                             const double* ridge_u, const double* const* phix_vals, const double* const* phiu_vals,
+                             double* col_objective, double* total, int64_t* col_terms, double* col_abs);
+
 #ifdef __cplusplus
 }
 #endif

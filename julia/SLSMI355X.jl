@@ -11,7 +11,7 @@
 module SLSMI355X
 
 using SparseArrays
-export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!
+export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective
 
 const LIB = get(ENV, "SLS_MI355X_LIB", "libsls_mi355x.so")
 
@@ -72,7 +72,38 @@ function sls_ridge!(ctx::Ptr{Cvoid}, rₓ::Vector{Float64}, rᵤ::Vector{Float64
 end
 
 """
-    Φₓ,Φᵤ = SLS_𝓗₂_mi355x(ctx, P, [𝓢ₓ,𝓢ᵤ]; 𝓘=nothing, objective=:h2)
+    J, total = objective_values(plan, d_values, nsub; packed=false)
+
+`sls_plan_fetch_objective` on a resident plan (a `Ptr{Cvoid}` from `sls_h2_sf_plan`, `nsub` = its `n_subproblems`): the objective
+value every subproblem achieved, evaluated on the device from the value array an execute wrote, and their sum — the
+reference's `objective_value(problem)` (src/synthesis.jl:52) per column.  A coupled group's joint value sits on its first column.
+"""
+function objective_values(plan::Ptr{Cvoid}, d_values::Ptr{Cvoid}, nsub::Integer; packed::Bool=false)
+    J = zeros(Float64, nsub);  total = Ref{Float64}(0.0)
+    rc = ccall((:sls_plan_fetch_objective, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ref{Float64}),
+               plan, d_values, packed ? 1 : 0, J, total)
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    return J, total[]
+end
+
+"""
+    J, total = last_objective(ctx, nsub)
+
+`sls_ctx_last_objective`: the values of the last one-shot solve on `ctx` that ran with `return_objective = true`
+(`sls_ctx_want_objective`), in the order of `status`.
+"""
+function last_objective(ctx::Ptr{Cvoid}, nsub::Integer)
+    J = zeros(Float64, nsub);  total = Ref{Float64}(0.0)
+    rc = ccall((:sls_ctx_last_objective, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Float64}), ctx, J, nsub, total)
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx)))
+    return J, total[]
+end
+
+"""
+    Φₓ,Φᵤ = SLS_𝓗₂_mi355x(ctx, P, [𝓢ₓ,𝓢ᵤ]; 𝓘=nothing, objective=:h2, return_objective=false)
+
+`return_objective = true` returns `Φₓ, Φᵤ, J, total` instead: `J[k]` is the objective value of subproblem k (the order of
+`status`), evaluated on the device before the download, `total` their sum (the squared 𝓗₂ norm of the closed loop).
 
 `objective = :sum_of_norms` minimises, per column, `Σₜ‖[C̃₁ D̃₁₂]Φ̃[t]B̃₁‖₂` instead (the column-separable bound of the 𝓗∞ norm;
 `SLS_SOLVE_SUM_OF_NORMS` — not in the reference, which has no 𝓗∞ synthesis).
@@ -82,7 +113,7 @@ fields (`A,B₁,B₂,C₁,D₁₁,D₁₂,Nx,Nu,Nz,Nw`); anything else returns `
 """
 SLS_𝓗₂_mi355x(P, 𝓢::AbstractVector; kw...) = SLS_𝓗₂_mi355x(default_ctx(), P, 𝓢; kw...)
 function SLS_𝓗₂_mi355x(ctx::Ptr{Cvoid}, P, 𝓢::AbstractVector; 𝓘=nothing, status::Union{Nothing,Vector{Int32}}=nothing,
-                        objective::Symbol=:h2)
+                        objective::Symbol=:h2, return_objective::Bool=false)
     hasproperty(P, :C₂) && size(P.D₂₁, 1) == 0 || return nothing          # StateFeedback only
     𝓢ₓ, 𝓢ᵤ = 𝓢
     T = length(𝓢ₓ)
@@ -107,10 +138,12 @@ function SLS_𝓗₂_mi355x(ctx::Ptr{Cvoid}, P, 𝓢::AbstractVector; 𝓘=nothi
         pm = pointer(mats)
         plant = Ref(PlantPtrs(pm, pm + sizeof(CscF64), pm + 2sizeof(CscF64), pm + 3sizeof(CscF64),
                               pm + 4sizeof(CscF64), pm + 5sizeof(CscF64)))
+        return_objective && ccall((:sls_ctx_want_objective, LIB), Cint, (Ptr{Cvoid}, Cint), ctx, 1)
         rc = ccall((:sls_h2_sf_solve, LIB), Cint,
                    (Ptr{Cvoid}, Ref{Dims}, Ref{PlantPtrs}, Ptr{CscBool}, Ptr{CscBool}, Int64, Ptr{Int64}, Ptr{Int64},
                     Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Int32}, Ptr{Cvoid}),
                    ctx, dims, plant, sx, su, ng, gptr, gcols, px, pu, st, C_NULL)
+        return_objective && ccall((:sls_ctx_want_objective, LIB), Cint, (Ptr{Cvoid}, Cint), ctx, 0)
         rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx)))
         rc > 0 && @warn "SLS_𝓗₂: $rc column(s) not solved to tolerance (see `status`; the reference never checks Ipopt's status)"
     end
@@ -118,6 +151,7 @@ function SLS_𝓗₂_mi355x(ctx::Ptr{Cvoid}, P, 𝓢::AbstractVector; 𝓘=nothi
     # the reference's sparse `+` accumulation does to numerical zeros (src/synthesis.jl:65-67)
     Φₓ = [dropzeros!(SparseMatrixCSC(P.Nx, P.Nx, copy(S.colptr), copy(S.rowval), v)) for (S, v) in zip(Sx, vx)]
     Φᵤ = [dropzeros!(SparseMatrixCSC(P.Nu, P.Nx, copy(S.colptr), copy(S.rowval), v)) for (S, v) in zip(Su, vu)]
+    return_objective && return (Φₓ, Φᵤ, last_objective(ctx, nsub)...)
     return Φₓ, Φᵤ
 end
 

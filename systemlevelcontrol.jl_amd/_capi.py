@@ -86,6 +86,7 @@ EXPORTS = [
     "sls_index_sets_device", "sls_h2_sf_plan_localized", "sls_h2_sf_solve_localized",
     "sls_closed_loop_plan", "sls_closed_loop_run", "sls_closed_loop_run_host", "sls_closed_loop_last_ms",
     "sls_closed_loop_entries", "sls_closed_loop_destroy",
+    "sls_plan_objective", "sls_plan_fetch_objective", "sls_ctx_want_objective", "sls_ctx_last_objective",
 ]
 
 _lib = None
@@ -174,7 +175,13 @@ def load_library(path: str | None = None):
     lib.sls_closed_loop_destroy.restype = None; lib.sls_closed_loop_destroy.argtypes = [vp]
     lib.sls_plan_execute_batch.restype = C.c_int
     lib.sls_plan_execute_batch.argtypes = [C.POINTER(vp), C.c_int, vp, C.POINTER(vp), C.c_int]
+    lib.sls_plan_objective.restype = C.c_int; lib.sls_plan_objective.argtypes = [vp, vp, vp, C.c_int, vp, vp]
+    lib.sls_plan_fetch_objective.restype = C.c_int; lib.sls_plan_fetch_objective.argtypes = [vp, vp, C.c_int, dp, dp]
+    lib.sls_ctx_want_objective.restype = C.c_int; lib.sls_ctx_want_objective.argtypes = [vp, C.c_int]
+    lib.sls_ctx_last_objective.restype = C.c_int; lib.sls_ctx_last_objective.argtypes = [vp, dp, C.c_int64, dp]
     # diagnostics outside the public header
+    lib.sls_debug_objective_host.restype = C.c_int
+    lib.sls_debug_objective_host.argtypes = common + [dp, dp, dpp, dpp, dp, dp, i64p, dp]
     lib.sls_debug_tile_invert.restype = C.c_int; lib.sls_debug_tile_invert.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_int]
     lib.sls_plan_debug_read_workspace.restype = C.c_int; lib.sls_plan_debug_read_workspace.argtypes = [vp, C.c_int64, C.c_int64, dp]
     lib.sls_debug_plan_tables.restype = C.c_int

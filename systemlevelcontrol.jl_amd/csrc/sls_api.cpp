@@ -24,6 +24,7 @@
 #include "../../include/sls_mi355x_debug.h"
 #include "sls_device.h"
 #include "sls_internal.h"
+#include "sls_objective.h"
 #include "sls_routing.h"
 #include "sls_symbolic.h"
 
@@ -42,6 +43,7 @@ hipError_t launch_index_sets(const IndexSetParams& p, bool fill, int grid, size_
 hipError_t launch_column_tables(const ColumnTableParams& p, bool fill, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t launch_level_prefix(const int32_t* cntx, const int32_t* cntu, int Nx, int K1, int64_t* prex, int64_t* preu, int64_t* totx,
                                int64_t* totu, hipStream_t stream);
+hipError_t launch_objective(const ObjectiveParams& p, int lds_doubles, double* d_total, hipStream_t stream);
 hipError_t launch_tile_invert(const double* d_A, int n, double* d_ws, double* d_out, bool mlds, hipStream_t stream);
 }  // namespace sls
 
@@ -121,6 +123,13 @@ struct sls_plan {
   sls_plan* refine = nullptr;           // sls_plan_refine: the near-singular groups once more on the tile kernel, run after every execute
   std::vector<int64_t> refine_dst;      // subproblem of this plan each subproblem of `refine` replaces
   int64_t info_unsupported = 0;
+  // objective evaluation (sls_plan_objective): the records of Symbolic::obj_pool, the work list of the general build and the
+  // plan-owned result buffer of sls_plan_fetch_objective (n_subproblems values, then the total)
+  const double* d_obj = nullptr;
+  const int32_t* d_gen = nullptr;
+  double* d_colobj = nullptr;
+  std::vector<int32_t> obj_gen;
+  int obj_lds_doubles = 0;
 };
 
 namespace {
@@ -921,6 +930,20 @@ static int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_pla
   if ((rc = dalloc(pl, (size_t)std::max(kp.nsub, 1), &kp.resid))) return bail(rc);
   if ((rc = dalloc(pl, (size_t)std::max(kp.nsub, 1), &kp.iters))) return bail(rc);
   if ((rc = dalloc(pl, (size_t)std::max<size_t>(pl->launches.size(), 1), &pl->d_counters))) return bail(rc);   // tile kernel work queues
+  {
+    // objective evaluation: dense columns and coupled groups go to the general build, one workgroup each; their z_t is staged
+    // in LDS when the largest of them fits 48 KiB
+    int64_t need = 0;
+    for (size_t q = 0; q < S.subs.size(); ++q) {
+      const SubDesc& sd = S.subs[q];
+      if (sd.has_w != 2 && sd.has_w != 3) continue;
+      pl->obj_gen.push_back((int32_t)q);
+      need = std::max<int64_t>(need, (int64_t)(sd.has_w == 3 ? sd.pad_ : 1) * (sd.n + sd.m));
+    }
+    pl->obj_lds_doubles = (int)std::min<int64_t>(need, 6144);
+    if ((rc = upload(pl, S.obj_pool, &pl->d_obj)) || (rc = upload(pl, pl->obj_gen, &pl->d_gen))) return bail(rc);
+    if ((rc = dalloc(pl, (size_t)std::max(kp.nsub, 1) + 1, &pl->d_colobj))) return bail(rc);
+  }
   if (const char* lv = sls_knob("SLS_PHASE_TIMERS")) {
     if ((rc = dalloc(pl, (size_t)std::max(kp.nsub, 1) * 8, &kp.dbg))) return bail(rc);
     kp.dbg_level = std::max(1, std::atoi(lv));
@@ -1104,6 +1127,16 @@ static int plan_create_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dim
     S.bytes_alg += 12.0 * (ci[3] + ci[4]) + 4.0 * (n + m) + dT * (n + m) / 8.0 + 8.0 * dnf;
   }
   S.md_total = md_tot; S.n_packed = S.pk_base[(size_t)Nx];
+  // objective records: this route only takes the default cost, so the constant is 0 and the scale is B1[c,c]² (1 for the
+  // minimum-norm point of a b = 0 column), as the host pass leaves them
+  S.obj_pool.resize(2 * (size_t)Nx);
+  const int64_t b1 = dims->index_base;
+  for (int64_t c = 0; c < Nx; ++c) {
+    double bd = 0.0;
+    for (int64_t k = P->B1->colptr[c] - b1; k < P->B1->colptr[c + 1] - b1; ++k)
+      if (P->B1->rowval[k] - b1 == c) bd = P->B1->nzval ? P->B1->nzval[k] : 1.0;
+    S.obj_pool[2 * (size_t)c] = bd != 0.0 ? bd * bd : 1.0; S.obj_pool[2 * (size_t)c + 1] = 0.0;
+  }
   tick("host: offsets + descriptors");
   S.order.resize((size_t)Nx);
   for (int64_t c = 0; c < Nx; ++c) S.order[(size_t)c] = (int32_t)c;
@@ -1192,6 +1225,13 @@ int sls_h2_sf_solve_localized(sls_ctx* ctx, const sls_dims* dims, const sls_plan
   if (rc) { cleanup(); return rc; }
   const double t1 = now_s();
   st.t_solve_s = t1 - t0;
+  if (ctx->want_objective) {
+    ctx->obj_state = 0;
+    ctx->last_objective.assign((size_t)pl->info.n_subproblems, 0.0);
+    rc = sls_plan_fetch_objective(pl, dv, 0, ctx->last_objective.data(), &ctx->last_total);
+    if (rc) { cleanup(); return rc; }
+    ctx->obj_state = 1;
+  }
   rc = sls_plan_download(pl, dv, phix_vals, phiu_vals);
   if (rc) { cleanup(); return rc; }
   const int64_t ns = pl->info.n_subproblems;
@@ -1414,6 +1454,97 @@ static int fetch_status_raw(sls_plan* plan, int32_t* col_status, double* residua
   if (col_status) HIPCHK(plan->ctx, hipMemcpy(col_status, plan->kp.status, n * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (residual) HIPCHK(plan->ctx, hipMemcpy(residual, plan->kp.resid, n * sizeof(double), hipMemcpyDeviceToHost));
   if (iters) HIPCHK(plan->ctx, hipMemcpy(iters, plan->kp.iters, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int sls_plan_objective(sls_plan* plan, void* hip_stream, const double* d_values, int packed, double* d_col_objective, double* d_total) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  if (!d_values && plan->info.n_packed > 0) return fail(plan->ctx, SLS_EINVAL, "null device value pointer");
+  if (packed && !plan->d_pdest) return fail(plan->ctx, SLS_EINVAL, "this plan was built without the packed layout");
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  if (plan->kp.nsub == 0) {
+    if (d_total) HIPCHK(plan->ctx, hipMemsetAsync(d_total, 0, sizeof(double), st));
+    return 0;
+  }
+  ObjectiveParams op{};
+  op.subs = plan->kp.subs; op.nsub = plan->kp.nsub; op.T = plan->kp.T; op.objective = plan->kp.objective;
+  op.ngen = (int32_t)plan->obj_gen.size(); op.gen_list = plan->d_gen;
+  op.mask_pool = plan->kp.mask_pool; op.dest = packed ? plan->d_pdest : plan->d_dest;
+  op.w_pool = plan->kp.w_pool; op.obj_pool = plan->d_obj; op.values = d_values;
+  op.col_objective = d_col_objective ? d_col_objective : plan->d_colobj;
+  hipError_t e = launch_objective(op, plan->obj_lds_doubles, d_total, st);
+  if (e != hipSuccess) return hipfail(plan->ctx, e, "launch objective kernels");
+  return 0;
+}
+
+int sls_plan_fetch_objective(sls_plan* plan, const double* d_values, int packed, double* col_objective, double* total) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  const size_t n = (size_t)plan->kp.nsub;
+  if (n == 0) { if (total) *total = 0.0; return 0; }
+  hipStream_t st = plan->stream;
+  // the execute that wrote d_values may have run on another stream: the plan's stream waits for its end first
+  if (plan->last_done) HIPCHK(plan->ctx, hipStreamWaitEvent(st, plan->last_done, 0));
+  if (int rc = sls_plan_objective(plan, st, d_values, packed, plan->d_colobj, plan->d_colobj + n)) return rc;
+  const size_t bytes = (n + 1) * sizeof(double);
+  if (unsigned char* pin = slot_pinned(plan->ctx, plan->slot, bytes)) {
+    HIPCHK(plan->ctx, hipMemcpyAsync(pin, plan->d_colobj, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(plan->ctx, hipStreamSynchronize(st));
+    if (col_objective) std::memcpy(col_objective, pin, n * sizeof(double));
+    if (total) std::memcpy(total, pin + n * sizeof(double), sizeof(double));
+    return 0;
+  }
+  HIPCHK(plan->ctx, hipStreamSynchronize(st));
+  if (col_objective) HIPCHK(plan->ctx, hipMemcpy(col_objective, plan->d_colobj, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (total) HIPCHK(plan->ctx, hipMemcpy(total, plan->d_colobj + n, sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int sls_ctx_want_objective(sls_ctx* ctx, int on) {
+  if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
+  ctx->want_objective = on != 0;
+  return 0;
+}
+
+int sls_ctx_last_objective(sls_ctx* ctx, double* col_objective, int64_t n, double* total) {
+  if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
+  if (ctx->obj_state == 2)
+    return fail(ctx, SLS_EUNSUPPORTED, "the last solve summed layers of overlapping groups: no single objective belongs to a column there");
+  if (ctx->obj_state != 1) return fail(ctx, SLS_EINVAL, "no solve has run on this context with sls_ctx_want_objective on");
+  if (n != (int64_t)ctx->last_objective.size()) return fail(ctx, SLS_EINVAL, "sls_ctx_last_objective: n is not the number of subproblems of the last solve");
+  if (col_objective) std::copy(ctx->last_objective.begin(), ctx->last_objective.end(), col_objective);
+  if (total) *total = ctx->last_total;
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): the host twin of the device evaluation — symbolic pass with explicit tables, then
+   the same formulas from host arrays in one serial loop (csrc/sls_objective.cpp).  Needs no device. */
+int sls_debug_objective_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                             int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, const double* ridge_x,
+                             const double* ridge_u, const double* const* phix_vals, const double* const* phiu_vals,
+                             double* col_objective, double* total, int64_t* col_terms, double* col_abs) {
+  Inputs in{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
+  std::string msg;
+  int rc = validate_inputs(in, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  if (!phix_vals || !phiu_vals) return fail(nullptr, SLS_EINVAL, "null value arrays");
+  in.reg_x = ridge_x; in.reg_u = ridge_u;
+  Symbolic S;
+  S.want_packed = false; S.compact = false;
+  std::vector<int64_t> gptr, gcols;
+  normalise_groups(in, gptr, gcols);
+  rc = build_symbolic(in, 0, (int64_t)gptr.size() - 1, S, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  std::vector<double> vals((size_t)std::max<int64_t>(S.n_values, 1), 0.0);
+  for (int64_t t = 0; t < S.T; ++t) {
+    const int64_t nx = S.off_x[t + 1] - S.off_x[t], nu = S.off_u[t + 1] - S.off_u[t];
+    if ((nx > 0 && !phix_vals[t]) || (nu > 0 && !phiu_vals[t])) return fail(nullptr, SLS_EINVAL, "null phix_vals[t]/phiu_vals[t]");
+    if (nx > 0) std::copy(phix_vals[t], phix_vals[t] + nx, vals.begin() + S.off_x[t]);
+    if (nu > 0) std::copy(phiu_vals[t], phiu_vals[t] + nu, vals.begin() + S.off_u[t]);
+  }
+  rc = objective_host(S, (dims->flags & SLS_SOLVE_SUM_OF_NORMS) ? 1 : 0, vals.data(), col_objective, total, col_terms, col_abs, msg);
+  if (rc) return fail(nullptr, rc, msg);
   return 0;
 }
 
@@ -1793,7 +1924,10 @@ int sls_h2_sf_solve(sls_ctx* ctx, const sls_dims* dims, const sls_plant* P, cons
   if (!phix_vals || !phiu_vals) return fail(ctx, SLS_EINVAL, "null output arrays");
   {
     const int lrc = solve_overlapping_groups(ctx, dims, P, Sx, Su, ngroups, group_ptr, group_cols, phix_vals, phiu_vals, col_status, stats);
-    if (lrc != -1000) return lrc;
+    if (lrc != -1000) {
+      if (ctx->want_objective) { ctx->obj_state = lrc >= 0 ? 2 : 0; ctx->last_objective.clear(); }   // a sum of layers: no per-column objective
+      return lrc;
+    }
   }
   const int ndev = (int)ctx->devs.size();
   std::vector<int64_t> cuts(ndev + 1, 0);
@@ -1858,6 +1992,19 @@ int sls_h2_sf_solve(sls_ctx* ctx, const sls_dims* dims, const sls_plant* P, cons
   }
   const double t1 = now_s();
   st.t_solve_s = t1 - t0;
+  if (ctx->want_objective) {
+    // after the last launch (refinement included), before the download: every device evaluates its shard, in col_status order
+    ctx->obj_state = 0;
+    ctx->last_objective.assign((size_t)S0.n_total_subproblems, 0.0);
+    double tot = 0.0;
+    for (int i = 0; i < ndev; ++i) {
+      double ti = 0.0;
+      rc = sls_plan_fetch_objective(plans[i], dvals[i], ndev == 1 ? 0 : 1, ctx->last_objective.data() + plans[i]->sym.first_sub_index, &ti);
+      if (rc) { cleanup(); return rc; }
+      tot += ti;
+    }
+    ctx->last_total = tot; ctx->obj_state = 1;
+  }
   // D2H of each shard's packed values + host scatter into the per-t arrays
   st.n_values_x = S0.off_x[T]; st.n_values_u = S0.n_values - S0.off_x[T];
   std::vector<double> stage;

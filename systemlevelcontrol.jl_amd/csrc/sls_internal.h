@@ -13,6 +13,11 @@ struct sls_ctx {
   std::string err;
   uint32_t flags = 0;
   std::vector<double> ridge_x, ridge_u;   // sls_set_ridge (empty = none)
+  // sls_ctx_want_objective: the one-shot calls evaluate every column's objective before their download and leave it here
+  bool want_objective = false;
+  int obj_state = 0;                      // 0: nothing to report, 1: last_objective / last_total valid, 2: the last call summed layers
+  std::vector<double> last_objective;     // col_status order
+  double last_total = 0.0;
   // Per device slot: streams and the big scratch workspace are created once and lent to plans (hipStreamCreate costs
   // ≈4 ms and a GB-sized hipMalloc ≈10 ms on this stack — more than a whole README solve).  One context is used by one
   // thread at a time (header), so a simple "in use" flag is enough; a second concurrent plan gets its own.

@@ -810,6 +810,26 @@ static int fill_range(const Inputs& in, const std::vector<int64_t>& gptr, const 
         for (int32_t i = 0; i < m; ++i) map_u[gs.su[i]] = -1;
         return SLS_EUNSUPPORTED;
       }
+      {
+        // objective record (Symbolic::obj_pool): the scale of an unweighted column and the constant ‖D̃11‖² term
+        double scale = 1.0, cst = 0.0;
+        if (sd.has_w == 0) {
+          if (!use_w) { if (bdiag[q] != 0.0) scale = bdiag[q] * bdiag[q]; }
+          else if (!coupled && bdiag[q] != 0.0) scale = bdiag[q] * bdiag[q] * (n ? hdx[0] : (m ? hdu[0] : 1.0));
+        }
+        if (in.P->D11 && (!coupled || q == 0)) {
+          for (int64_t w2 = 0; w2 < (coupled ? nc : 1); ++w2) {
+            const int64_t cw = coupled ? cols[w2] : c;
+            for (int64_t k = in.P->D11->colptr[cw] - base; k < in.P->D11->colptr[cw + 1] - base; ++k) {
+              const int64_t z = in.P->D11->rowval[k] - base;
+              const double v = in.P->D11->nzval ? in.P->D11->nzval[k] : 1.0;
+              if (z < Nx ? map_x[z] >= 0 : map_u[z - Nx] >= 0) cst += v * v;
+            }
+          }
+          cst *= (double)T;
+        }
+        S.obj_pool[2 * sd.out_index] = scale; S.obj_pool[2 * sd.out_index + 1] = cst;
+      }
       S.subs[sd.out_index] = sd;
       S.sub_col[sd.out_index] = (int32_t)c;
       // algorithmic work, SURVEY §8d
@@ -898,7 +918,7 @@ int build_symbolic(const Inputs& in, int64_t gbeg, int64_t gend, Symbolic& S, st
   S.md_total = md_tot;
   if (S.want_packed) S.compact = false;
   S.idx_pool.resize(idx_tot);
-  S.subs.resize(sub_tot); S.sub_col.resize(sub_tot);
+  S.subs.resize(sub_tot); S.sub_col.resize(sub_tot); S.obj_pool.resize(2 * sub_tot);
   std::vector<int32_t> nfree_of((size_t)sub_tot, 0);
   auto pass_b = [&]() -> int {
     if (S.compact) { S.cmask.resize(cw_tot); S.cbase.resize(2 * T * sub_tot); S.coff.resize(sub_tot); }

@@ -75,6 +75,11 @@ struct Symbolic {
   pool_vec<int32_t> pdest_pool;         // destinations in the packed array
   pool_vec<int64_t> packed_to_final;    // n_packed
   pool_vec<double> w_pool;
+  // What the solve kernels never needed, because it does not move the minimiser (sls_objective.hip / sls_objective.cpp read
+  // it): two doubles per subproblem, indexed by out_index.  [0] obj_scale: the weight of Σz² when has_w = 0 — b²·h for uniform
+  // weights h and b = B1[c,c], 1 for the minimum-norm point of a b = 0 column.  [1] obj_const: T·‖D̃11[[s_x; Nx+s_u], c]‖²
+  // (src/reduction.jl:15 keeps only those z-rows); a coupled group's Σ_w over its columns sits on its first column.
+  pool_vec<double> obj_pool;
   pool_vec<int32_t> sub_col;            // global column of each subproblem
   int64_t n_packed = 0;
   std::vector<int64_t> pk_base;         // n_subs+1: first packed index of each subproblem (its free variables are contiguous)

@@ -138,6 +138,10 @@ class ColumnShardedH2:
             self.ctx = ctx
             self.local = local_solver_factory(rng)
         self.n_groups = ng
+        # subproblems per rank (objective_values: sizes of the per-rank pieces follow from the cuts)
+        glen = np.ones(ng, dtype=np.int64) if groups is None else np.asarray([len(g) for g in groups], dtype=np.int64)
+        gcum = np.concatenate([[0], np.cumsum(glen)])
+        self.sub_counts = np.diff(gcum[np.asarray(self.cuts, dtype=np.int64)])
         # --- static layout exchange (setup, not part of a step) ---
         n_local = int(self.local.n_packed)
         dest_local = np.asarray(self.local.dest(), dtype=np.int64)
@@ -254,6 +258,36 @@ class ColumnShardedH2:
             n = self.local.refine(self.packed, packed=True)
         self.step()
         return int(n)
+
+    def objective_values(self):
+        """(col_objective ndarray over ALL subproblems in group order, total float) of the last `step`: every rank evaluates
+        its own shard on the device, from the array its solve wrote and before anything is gathered (Plan.objective_values_async).
+        The total is one all_reduce(SUM) of one double; the per-column array is one all_gather of the per-rank pieces, whose
+        sizes follow from the cuts.  After `step_async`, call `flush()` first."""
+        torch = self.torch
+        if not hasattr(self.local, "plan"):
+            raise RuntimeError("objective_values needs the HIP local solver (a device plan)")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self._direct():
+            col, tot = self.local.plan.objective_values_async(self.values.data_ptr(), packed=False, stream=stream)
+        else:
+            src = self.packed if self._pipe is None else self._pipe["packed"][(self._pipe["k"] - 1) & 1]
+            col, tot = self.local.plan.objective_values_async(src.data_ptr(), packed=True, stream=stream)
+        if self.world > 1:
+            if self.dist.get_backend(self.pg) == "gloo":          # tests only: a gloo group cannot move device memory
+                torch.cuda.current_stream(self.device).synchronize()
+                ht = tot.cpu(); self.dist.all_reduce(ht, group=self.pg); tot = ht
+            else:
+                self.dist.all_reduce(tot, group=self.pg)
+            nmax = max(int(self.sub_counts.max()), 1)
+            pad = torch.zeros(nmax, dtype=torch.float64, device=self.device)
+            pad[: col.numel()] = col
+            allc = torch.empty(self.world * nmax, dtype=torch.float64, device=self.device)
+            self._all_gather(allc, pad)
+            allc = allc.cpu().numpy()
+            colv = np.concatenate([allc[r * nmax: r * nmax + int(self.sub_counts[r])] for r in range(self.world)])
+            return colv, float(tot.item())
+        return col.cpu().numpy(), float(tot.item())
 
     def flush(self):
         """Make the current stream wait for everything `step_async` has in flight."""

@@ -45,6 +45,20 @@ class Context:
         _capi.check(self._lib.sls_set_ridge(self.handle, rx.size, rx.ctypes.data_as(dp) if rx.size else None,
                                             ru.size, ru.ctypes.data_as(dp) if ru.size else None), self.handle)
 
+    def want_objective(self, on=True):
+        """sls_ctx_want_objective: later one-shot solves on this context (SLS_H2, SLS_H2_batch, SLS_H2_localized) also evaluate
+        every column's objective value on the device, before their download; `last_objective` reads it."""
+        _capi.check(self._lib.sls_ctx_want_objective(self.handle, int(bool(on))), self.handle)
+
+    def last_objective(self, n):
+        """sls_ctx_last_objective: (per-subproblem objective values in col_status order, their total) of the last one-shot solve
+        that ran with `want_objective` on; n = its number of subproblems."""
+        col = np.zeros(max(int(n), 1), dtype=np.float64)
+        tot = C.c_double()
+        _capi.check(self._lib.sls_ctx_last_objective(self.handle, col.ctypes.data_as(C.POINTER(C.c_double)), int(n), C.byref(tot)),
+                    self.handle)
+        return col[: int(n)], tot.value
+
     def close(self):
         if getattr(self, "handle", None):
             self._lib.sls_destroy(self.handle)
@@ -158,6 +172,33 @@ class Plan:
                                                     it.ctypes.data_as(C.POINTER(C.c_int32))), self.ctx.handle)
         return st[:n], rs[:n], it[:n]
 
+    def objective_values(self, d_values, packed=False, stream=None):
+        """(col_objective ndarray, total float): the objective value every subproblem of this plan achieved, evaluated on the
+        device from the value array an execute wrote (sls_plan_fetch_objective; layout `packed` as in `execute`).  A coupled
+        group's joint value sits on its first column, the others report 0.0.  With `stream` the evaluation is enqueued there
+        (after the execute the caller put on it) and that stream is waited for."""
+        n = self.info["n_subproblems"]
+        if stream is not None:
+            col, tot = self.objective_values_async(d_values, packed=packed, stream=stream)
+            self.synchronize(stream)
+            return col.cpu().numpy(), float(tot.item())
+        col = np.zeros(max(n, 1), dtype=np.float64)
+        tot = C.c_double()
+        _capi.check(self._lib.sls_plan_fetch_objective(self.handle, d_values, int(packed), col.ctypes.data_as(C.POINTER(C.c_double)),
+                                                       C.byref(tot)), self.ctx.handle)
+        return col[:n], tot.value
+
+    def objective_values_async(self, d_values, packed=False, stream=None):
+        """sls_plan_objective into fresh torch tensors on the plan's device: (col_objective[n_subproblems], total[1]), enqueued
+        on `stream` (None = the null stream) after the execute that wrote `d_values`; nothing waits for the device."""
+        import torch
+        dev = torch.device("cuda", self.info["device"])
+        col = torch.empty(max(self.info["n_subproblems"], 1), dtype=torch.float64, device=dev)
+        tot = torch.empty(1, dtype=torch.float64, device=dev)          # written by the call (zeroed there when the plan is empty)
+        _capi.check(self._lib.sls_plan_objective(self.handle, stream, d_values, int(packed), col.data_ptr(), tot.data_ptr()),
+                    self.ctx.handle)
+        return col[: self.info["n_subproblems"]], tot
+
     def describe(self):
         buf = C.create_string_buffer(4096)
         _capi.check(self._lib.sls_plan_describe(self.handle, buf, len(buf)))
@@ -193,6 +234,59 @@ class Plan:
             pass
 
 
+class _WantObjective:
+    """Turns the context's objective option on for one call and restores `off` afterwards (the option is off by default and
+    these wrappers leave it as they found it: only calls that ask for the values pay for the evaluation)."""
+
+    def __init__(self, ctx, on):
+        self.ctx, self.on = ctx, bool(on)
+
+    def __enter__(self):
+        if self.on:
+            self.ctx.want_objective(True)
+        return self
+
+    def __exit__(self, *a):
+        if self.on:
+            self.ctx.want_objective(False)
+
+    def into(self, info, n):
+        if self.on:
+            info["col_objective"], info["objective_total"] = self.ctx.last_objective(n)
+
+
+def objective_values_host(P, S, vals_x, vals_u, I=None, *, ridge=None, objective="h2", index_base=0, return_bound=False):
+    """Host twin of `Plan.objective_values` (sls_debug_objective_host; needs no device): the host symbolic pass over all groups,
+    then the same formulas from host value arrays — vals_x[t] / vals_u[t] in the masks' CSC order, as the C ABI fills them.
+    ridge = (rx, ru) as `Context.set_ridge` takes them.  Returns (col_objective, total); with return_bound also, per column,
+    the number N of products its value sums and the sum S of their absolute values (a summation in another order differs
+    by at most 2·N·2⁻⁵³·S)."""
+    lib = _capi.load_library()
+    Sx, Su = S
+    m = _capi.Marshalled(P, Sx, Su, None if I is None else [list(g) for g in I], index_base=index_base, flags=_objective_flags(objective))
+    T = len(Sx)
+    dp = C.POINTER(C.c_double)
+    vx = [np.ascontiguousarray(v, dtype=np.float64) for v in vals_x]
+    vu = [np.ascontiguousarray(v, dtype=np.float64) for v in vals_u]
+    if [v.size for v in vx] != m.nnz_x or [v.size for v in vu] != m.nnz_u:
+        raise ValueError("value arrays do not match the masks' nnz")
+    pad = np.zeros(1)
+    px = (dp * T)(*[(a if a.size else pad).ctypes.data_as(dp) for a in vx])
+    pu = (dp * T)(*[(a if a.size else pad).ctypes.data_as(dp) for a in vu])
+    rx, ru = (None, None) if ridge is None else ridge
+    rx = None if rx is None else np.ascontiguousarray(rx, dtype=np.float64)
+    ru = None if ru is None else np.ascontiguousarray(ru, dtype=np.float64)
+    n = m.n_sub
+    col = np.zeros(max(n, 1)); cabs = np.zeros(max(n, 1)); cn = np.zeros(max(n, 1), dtype=np.int64)
+    tot = C.c_double()
+    _capi.check(lib.sls_debug_objective_host(*m.common_args(), None if rx is None else rx.ctypes.data_as(dp),
+                                             None if ru is None else ru.ctypes.data_as(dp), px, pu, col.ctypes.data_as(dp),
+                                             C.byref(tot), cn.ctypes.data_as(C.POINTER(C.c_int64)), cabs.ctypes.data_as(dp)))
+    if return_bound:
+        return col[:n], tot.value, cn[:n], cabs[:n]
+    return col[:n], tot.value
+
+
 def assemble_phi(Sx, Su, vals_x, vals_u, dropzeros=True):
     """Φx[t] = SparseMatrixCSC(Nx,Nx, 𝓢x[t].colptr, 𝓢x[t].rowval, vals) (+ dropzeros!, which is what the
     reference's sparse `+` accumulation does to numerical zeros: src/synthesis.jl:65-67)."""
@@ -220,7 +314,8 @@ def execute_batch(plans, d_values, packed=False, stream=None):
     _capi.check(plans[0]._lib.sls_plan_execute_batch(hp, n, stream, dv, int(packed)), plans[0].ctx.handle)
 
 
-def SLS_H2_batch(plants, masks, *, ctx: Context | None = None, return_info=False, dropzeros=True, objective="h2", index_base=0):
+def SLS_H2_batch(plants, masks, *, ctx: Context | None = None, return_info=False, dropzeros=True, objective="h2", index_base=0,
+                 return_objective=False):
     """[(Φx, Φu) for each plant] = one sls_h2_sf_solve_batch call over independent plants that share T: a loop of reference
     `SLS_𝓗₂(P, 𝓢)` calls (src/synthesis.jl:11) run as ONE set of kernel launches (the block-diagonal composite plant)."""
     n = len(plants)
@@ -248,8 +343,11 @@ def SLS_H2_batch(plants, masks, *, ctx: Context | None = None, return_info=False
         pxs[i] = C.cast(px, dpp); pus[i] = C.cast(pu, dpp); sts[i] = st.ctypes.data_as(i32p)
         vals.append((vx, vu)); status.append(st)
     stats = _capi.sls_stats()
-    rc = lib.sls_h2_sf_solve_batch(ctx.handle, n, dims, pl, sx, su, pxs, pus, sts, C.byref(stats))
-    _capi.check(rc, ctx.handle)
+    with _WantObjective(ctx, return_objective) as wo:
+        rc = lib.sls_h2_sf_solve_batch(ctx.handle, n, dims, pl, sx, su, pxs, pus, sts, C.byref(stats))
+        _capi.check(rc, ctx.handle)
+        obj = {}
+        wo.into(obj, sum(m.n_sub for m in ms))
     out = []
     for m, S, (vx, vu) in zip(ms, masks, vals):
         out.append(assemble_phi(S[0], S[1], [a[:k] for a, k in zip(vx, m.nnz_x)], [a[:k] for a, k in zip(vu, m.nnz_u)],
@@ -258,6 +356,10 @@ def SLS_H2_batch(plants, masks, *, ctx: Context | None = None, return_info=False
         info = stats.asdict()
         info["col_status"] = [st[: m.n_sub].copy() for st, m in zip(status, ms)]
         info["n_unsolved"] = rc
+        if return_objective:          # composite order cut back into one array per plant
+            cuts = np.cumsum([0] + [m.n_sub for m in ms])
+            info["col_objective"] = [obj["col_objective"][a:b].copy() for a, b in zip(cuts[:-1], cuts[1:])]
+            info["objective_total"] = obj["objective_total"]
         return out, info
     if rc > 0:
         warnings.warn(f"SLS_H2_batch: {rc} subproblems not solved — pass return_info=True for the per-column status",
@@ -265,7 +367,8 @@ def SLS_H2_batch(plants, masks, *, ctx: Context | None = None, return_info=False
     return out
 
 
-def SLS_H2_localized(P, d, T, alpha, *, ctx: Context | None = None, return_info=False, dropzeros=True, objective="h2", index_base=0):
+def SLS_H2_localized(P, d, T, alpha, *, ctx: Context | None = None, return_info=False, dropzeros=True, objective="h2", index_base=0,
+                     return_objective=False):
     """Φx, Φu = SLS_𝓗₂(P, [𝓢x, 𝓢u]) for the README's own masks (README.md:52-54), given as (d, T, α) instead of 2T sparse
     matrices: sls_h2_sf_solve_localized builds index sets, mask slices and destinations on the device.  The patterns needed to
     return Φ as sparse matrices are fetched with the device mask recipe (row indices only come down)."""
@@ -285,10 +388,12 @@ def SLS_H2_localized(P, d, T, alpha, *, ctx: Context | None = None, return_info=
     pu = (C.POINTER(C.c_double) * T)(*[a.ctypes.data_as(C.POINTER(C.c_double)) for a in vu])
     status = np.zeros(max(P.Nx, 1), dtype=np.int32)
     stats = _capi.sls_stats()
-    rc = lib.sls_h2_sf_solve_localized(ctx.handle, C.byref(m.dims), C.byref(m.plant), int(d), float(alpha), px, pu,
-                                       status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(stats))
-    _capi.check(rc, ctx.handle)
-    st = stats.asdict()
+    with _WantObjective(ctx, return_objective) as wo:
+        rc = lib.sls_h2_sf_solve_localized(ctx.handle, C.byref(m.dims), C.byref(m.plant), int(d), float(alpha), px, pu,
+                                           status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(stats))
+        _capi.check(rc, ctx.handle)
+        st = stats.asdict()
+        wo.into(st, P.Nx)
     if st["n_values_x"] != sum(nnz_x) or st["n_values_u"] != sum(nnz_u):
         raise RuntimeError("device symbolic route and device mask recipe disagree on the pattern sizes")
     Phix, Phiu = assemble_phi(Sx, Su, [a[:n] for a, n in zip(vx, nnz_x)], [a[:n] for a, n in zip(vu, nnz_u)], dropzeros=dropzeros)
@@ -317,7 +422,8 @@ def SLS_Hinf_bound(P, S, I=None, **kw):
     return SLS_H2(P, S, I, objective="sum_of_norms", **kw)
 
 
-def SLS_H2(P, S, I=None, *, ctx: Context | None = None, return_info=False, dropzeros=True, index_base=0, objective="h2"):
+def SLS_H2(P, S, I=None, *, ctx: Context | None = None, return_info=False, dropzeros=True, index_base=0, objective="h2",
+           return_objective=False):
     """Φx, Φu = SLS_𝓗₂(P, [𝓢x, 𝓢u]; 𝓘)   — drop-in for reference src/synthesis.jl:11.
 
     P : GeneralizedPlant (state feedback).  Any other feedback structure returns None,
@@ -325,6 +431,9 @@ def SLS_H2(P, S, I=None, *, ctx: Context | None = None, return_info=False, dropz
     S : [𝓢x, 𝓢u], two length-T lists of boolean sparse matrices (Nx×Nx, Nu×Nx).
     I : optional list of column groups (0-based column indices, ascending inside a group).
     index_base : 0, or 1 to marshal every index array the way Julia stores it (what the `ccall` binding hands over).
+    return_objective : with return_info, `info` also carries `col_objective` (the objective value every subproblem achieved,
+        in col_status order, evaluated on the device before the download) and `objective_total` (their sum: the squared 𝓗₂
+        norm of the closed loop).  Not defined for a group list with overlapping groups (SLS_EUNSUPPORTED).
     Returns two length-T lists of scipy CSC matrices (Φx[t] Nx×Nx, Φu[t] Nu×Nx).
     """
     if not isinstance(P, GeneralizedPlant) or P.Ts is not StateFeedback:
@@ -341,15 +450,19 @@ def SLS_H2(P, S, I=None, *, ctx: Context | None = None, return_info=False, dropz
     pu = (C.POINTER(C.c_double) * T)(*[a.ctypes.data_as(C.POINTER(C.c_double)) for a in vu])
     status = np.zeros(max(m.n_sub, 1), dtype=np.int32)
     stats = _capi.sls_stats()
-    rc = lib.sls_h2_sf_solve(ctx.handle, *m.common_args(), px, pu,
-                             status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(stats))
-    _capi.check(rc, ctx.handle)
+    obj = {}
+    with _WantObjective(ctx, return_objective) as wo:
+        rc = lib.sls_h2_sf_solve(ctx.handle, *m.common_args(), px, pu,
+                                 status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(stats))
+        _capi.check(rc, ctx.handle)
+        wo.into(obj, m.n_sub)
     Phix, Phiu = assemble_phi(Sx, Su, [a[:n] for a, n in zip(vx, m.nnz_x)],
                               [a[:n] for a, n in zip(vu, m.nnz_u)], dropzeros=dropzeros)
     if return_info:
         info = stats.asdict()
         info["col_status"] = status[: m.n_sub].copy()
         info["n_unsolved"] = rc
+        info.update(obj)
         return Phix, Phiu, info
     if rc > 0:
         # the reference never checks Ipopt's status (src/synthesis.jl:62-65); a caller that does not ask for the per-column
