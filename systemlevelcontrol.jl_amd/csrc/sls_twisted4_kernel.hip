@@ -36,8 +36,9 @@ namespace sls {
 #define SLS_T4_EXP 0          // timing experiments (WRONG results on purpose): 1 = helper does not eliminate, 2 = helper without cross-lane traffic, 3 = without ds_bpermute
 #endif
 
-// meeting block.  The upward side carries the mask ramp (its helper recomputes the static part for every block while the
-// masks still grow, the downward side's masks repeat) and the middle block's own inversion: it gets the shorter half.
+// meeting block.  The upward side carries the mask ramp (its helper rebuilds the static part for every block while the
+// masks still grow — in the three-tile classes from Ã / B̃ values gathered once per column into registers, so a rebuild reads
+// weights only — the downward side's masks repeat) and the middle block's own inversion: it gets the shorter half.
 #ifndef SLS_T4_MIDDLE_SHIFT
 #define SLS_T4_MIDDLE_SHIFT 0
 #endif
@@ -796,6 +797,29 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
 #pragma unroll
         for (int e = 0; e < KB; ++e) { const bool ok = e < capB; hbc[ri][e] = ok ? brow_c[e * NPL + i] : 0; hbv[ri][e] = ok ? brow_v[e * NPL + i] : 0.0; }
       }
+      // The three-tile classes also keep, for the whole column, what the static build gathers through those lists — Ã[b + 8·cj, hac]
+      // and B̃[b + 8·cj, hbc] for the stored half cj ≥ ri — and the nine Ã values of this direction's border: addresses and values
+      // do not depend on the block, only the weights do.  A rebuild is then weight reads + FMAs, no dependent LDS address chain.
+      // The four-tile classes have no registers to spare (they spill already) and gather from LDS per block as before.
+      constexpr bool HOIST = (TR == 3);
+      double GA[KH][TR][TR], GB[KB][TR][TR], XA[TT];
+      if constexpr (HOIST) {
+#pragma unroll
+        for (int ri = 0; ri < TR; ++ri) {
+#pragma unroll
+          for (int cj = ri; cj < TR; ++cj) {
+#pragma unroll
+            for (int e = 0; e < KH; ++e) GA[e][ri][cj] = Ad[(tb + 8 * cj) * LDT + hac[ri][e]];
+#pragma unroll
+            for (int e = 0; e < KB; ++e) GB[e][ri][cj] = Bd[(tb + 8 * cj) * MC + hbc[ri][e]];
+          }
+#pragma unroll
+          for (int cj = 0; cj < TR; ++cj) {
+            const int i = ta + 8 * ri, l = tb + 8 * cj;
+            XA[ri * TR + cj] = (dir == 0) ? Ad[i * LDT + l] : Ad[l * LDT + i];
+          }
+        }
+      }
       // which blocks can reuse the previous step's static part: masks of (k, k−1) equal those of the block produced before
       // (upward: k−1; downward: k+1 — never block T, whose Wx is 0).  One ballot per block, all loads independent.
       unsigned long long samebits = 0;
@@ -810,13 +834,24 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
       const int s_end = (dir == 0) ? c : T - c + 1;
       auto load_border = [&](int k, double (&Xn)[TT]) {     // X of block k: upward Ã·Wx_{k−1}, downward Wx_k·Ãᵀ
         const double* wrow = wxt + ((dir == 0) ? k - 1 : k) * NPL;
+        if constexpr (HOIST) {                              // three weights of this lane's tile columns (rows), nine multiplies
+          double wr[TR];
 #pragma unroll
-        for (int ri = 0; ri < TR; ++ri) {
-          const int i = ta + 8 * ri;
+          for (int q = 0; q < TR; ++q) wr[q] = wrow[((dir == 0) ? tb : ta) + 8 * q];
 #pragma unroll
-          for (int cj = 0; cj < TR; ++cj) {
-            const int l = tb + 8 * cj;
-            Xn[ri * TR + cj] = (dir == 0) ? Ad[i * LDT + l] * wrow[l] : wrow[i] * Ad[l * LDT + i];
+          for (int ri = 0; ri < TR; ++ri) {
+#pragma unroll
+            for (int cj = 0; cj < TR; ++cj) Xn[ri * TR + cj] = (dir == 0) ? XA[ri * TR + cj] * wr[cj] : wr[ri] * XA[ri * TR + cj];
+          }
+        } else {
+#pragma unroll
+          for (int ri = 0; ri < TR; ++ri) {
+            const int i = ta + 8 * ri;
+#pragma unroll
+            for (int cj = 0; cj < TR; ++cj) {
+              const int l = tb + 8 * cj;
+              Xn[ri * TR + cj] = (dir == 0) ? Ad[i * LDT + l] * wrow[l] : wrow[i] * Ad[l * LDT + i];
+            }
           }
         }
       };
@@ -854,7 +889,11 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
               const double w0 = wp_[cc];
               const double v = hav[ri][e] * (fold0 ? delta * w0 / (delta + w0) : w0);
 #pragma unroll
-              for (int cj = ri; cj < TR; ++cj) Sw[ri * TR + cj] = __builtin_fma(v, Ad[(tb + 8 * cj) * LDT + cc], Sw[ri * TR + cj]);
+              for (int cj = ri; cj < TR; ++cj) {
+                double g;
+                if constexpr (HOIST) g = GA[e][ri][cj]; else g = Ad[(tb + 8 * cj) * LDT + cc];
+                Sw[ri * TR + cj] = __builtin_fma(v, g, Sw[ri * TR + cj]);
+              }
             }
           }
           for (int e = KH; e < nzA; ++e) {
@@ -875,7 +914,11 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
               const int cc = hbc[ri][e];
               const double v = hbv[ri][e] * wu_[cc];
 #pragma unroll
-              for (int cj = ri; cj < TR; ++cj) Sw[ri * TR + cj] = __builtin_fma(v, Bd[(tb + 8 * cj) * MC + cc], Sw[ri * TR + cj]);
+              for (int cj = ri; cj < TR; ++cj) {
+                double g;
+                if constexpr (HOIST) g = GB[e][ri][cj]; else g = Bd[(tb + 8 * cj) * MC + cc];
+                Sw[ri * TR + cj] = __builtin_fma(v, g, Sw[ri * TR + cj]);
+              }
             }
           }
           for (int e = KB; e < nzB; ++e) {
