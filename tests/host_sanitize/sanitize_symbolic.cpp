@@ -2,9 +2,10 @@
 // built and run by tests/test_host.py::test_symbolic_pass_under_sanitizers with g++ -fsanitize=address,undefined.  Drives every
 // host-only entry the C ABI forwards to — mask recipe, validation, index sets, the full symbolic pass in its four table layouts
 // (explicit / compact × packed / mask order), shard ranges, caller groups (decoupled and coupled), cost model, the inputs of
-// the two device passes, the closed-loop FIR operator, kernel selection (csrc/sls_routing.cpp: the launch list of every shard for
+// the two device passes, the closed-loop FIR operator (restated exactly from the masks: check_fir), kernel selection (csrc/sls_routing.cpp: the launch list of every shard for
 // 1, 8 and 256 CUs, both objectives, with and without force_tile) — on a chain, a 2-D grid and a random plant, in both index bases, plus
 // malformed inputs that must be refused without touching memory out of bounds.  Exit code 0 = clean.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -141,6 +142,130 @@ void check_routing(const sls::Symbolic& S0) {
       }
 }
 
+// build_fir_operator against an exact restatement from the CSC masks.  The value array is the slices' stored entries back to
+// back, Sx[0..T−1] then Su[0..T−1]; the operator holds the stored-true entries of Sx[1..T−1] (lag τ = t) and Su[0..T−1] (lag
+// τ = t + 1), β rows first, inside a row ascending in (τ, c), each as hoff = τ·Nx − c and perm = its index in the value array.
+void csr_equals_csc(const sls::HostCsr& R, const Csc& m, int base) {
+  EXPECT(R.nrows == m.nr && R.ncols == m.nc && (int64_t)R.ptr.size() == m.nr + 1, "CSR copy: shape");
+  EXPECT(R.idx.size() == m.ri.size() && R.val.size() == m.ri.size(), "CSR copy: number of entries");
+  if ((int64_t)R.ptr.size() != m.nr + 1 || R.idx.size() != m.ri.size() || R.val.size() != m.ri.size()) return;
+  EXPECT(R.ptr[0] == 0 && R.ptr[m.nr] == (int32_t)m.ri.size(), "CSR copy: row pointer ends");
+  std::vector<std::vector<std::pair<int32_t, double>>> rows((size_t)m.nr);       // columns ascend: entries arrive in (r, c) order
+  for (int64_t c = 0; c < m.nc; ++c)
+    for (int64_t k = m.cp[c] - base; k < m.cp[c + 1] - base; ++k) rows[(size_t)(m.ri[k] - base)].push_back({(int32_t)c, m.v[k]});
+  for (int64_t r = 0; r < m.nr; ++r) {
+    const bool len_ok = R.ptr[r] >= 0 && R.ptr[r + 1] - R.ptr[r] == (int32_t)rows[r].size() && R.ptr[r + 1] <= (int32_t)R.idx.size();
+    EXPECT(len_ok, "CSR copy: row length");
+    if (!len_ok) return;
+    for (size_t q = 0; q < rows[r].size(); ++q)
+      EXPECT(R.idx[R.ptr[r] + q] == rows[r][q].first && R.val[R.ptr[r] + q] == rows[r][q].second, "CSR copy: entry");
+  }
+}
+
+void check_fir(const Plant& P, const Masks& M, int64_t T, int base) {
+  sls_dims dims{P.Nx, P.Nu, P.Nx + P.Nu, P.Nx, T, base, 0};
+  sls_csc_f64 A = P.A.f64(), B1 = P.B1.f64(), B2 = P.B2.f64();
+  std::string msg;
+  sls::FirOperator F;
+  const int rc = sls::build_fir_operator(&dims, &A, &B1, &B2, M.bx.data(), M.bu.data(), F, msg);
+  EXPECT(rc == 0, "build_fir_operator");
+  if (rc) { std::fprintf(stderr, "  %s\n", msg.c_str()); return; }
+  struct Entry { int64_t row, lag, col, perm; };
+  std::vector<Entry> eb, eu;                           // expected β and u entries
+  std::vector<int64_t> forbidden;                      // value-array indices the operator must not read: Sx[0], stored false
+  int64_t off = 0, n_true = 0;
+  for (int part = 0; part < 2; ++part)
+    for (int64_t t = 0; t < T; ++t) {
+      const Csc& m = part ? M.u[t] : M.x[t];
+      for (int64_t c = 0; c < P.Nx; ++c)
+        for (int64_t k = m.cp[c] - base; k < m.cp[c + 1] - base; ++k) {
+          const bool stored_true = m.b.empty() || m.b[k];
+          if ((part == 0 && t == 0) || !stored_true) { forbidden.push_back(off + k); continue; }
+          (part ? eu : eb).push_back(Entry{m.ri[k] - base, part ? t + 1 : t, c, off + k});
+          ++n_true;
+        }
+      off += (int64_t)m.ri.size();
+    }
+  auto by_row = [](const Entry& a, const Entry& b) { return a.row != b.row ? a.row < b.row : a.lag != b.lag ? a.lag < b.lag : a.col < b.col; };
+  std::sort(eb.begin(), eb.end(), by_row); std::sort(eu.begin(), eu.end(), by_row);
+  EXPECT(F.Nx == P.Nx && F.Nu == P.Nu && F.Nw == P.Nx && F.T == T && F.n_values == off, "FIR dimensions");
+  // pointer arrays
+  EXPECT((int64_t)F.beta_ptr.size() == P.Nx + 1 && (int64_t)F.u_ptr.size() == P.Nu + 1, "FIR pointer array lengths");
+  if ((int64_t)F.beta_ptr.size() != P.Nx + 1 || (int64_t)F.u_ptr.size() != P.Nu + 1) return;
+  EXPECT(F.beta_ptr[0] == 0, "beta_ptr[0]");
+  for (int64_t r = 0; r < P.Nx; ++r) EXPECT(F.beta_ptr[r] <= F.beta_ptr[r + 1], "beta_ptr monotone");
+  for (int64_t r = 0; r < P.Nu; ++r) EXPECT(F.u_ptr[r] <= F.u_ptr[r + 1], "u_ptr monotone");
+  EXPECT(F.u_ptr[0] == F.beta_ptr[P.Nx] && F.u_ptr[0] == (int64_t)eb.size(), "u_ptr[0] == beta_ptr[Nx]");
+  EXPECT(F.u_ptr[P.Nu] == n_true, "u_ptr[Nu] == stored-true entries of Sx[1..T-1] and Su");
+  EXPECT((int64_t)F.hoff.size() == n_true && (int64_t)F.perm.size() == n_true, "FIR entry count");
+  if ((int64_t)F.hoff.size() != n_true || (int64_t)F.perm.size() != n_true || F.u_ptr[P.Nu] != n_true) return;
+  // entries, row by row
+  for (int part = 0; part < 2; ++part) {
+    const std::vector<Entry>& ex = part ? eu : eb;
+    const std::vector<int32_t>& ptr = part ? F.u_ptr : F.beta_ptr;
+    const int64_t first = part ? (int64_t)eb.size() : 0;
+    for (size_t q = 0; q < ex.size(); ++q) {
+      const int64_t e = first + (int64_t)q;
+      EXPECT(ptr[ex[q].row] <= e && e < ptr[ex[q].row + 1], "FIR entry in its row");
+      EXPECT(F.hoff[e] == ex[q].lag * P.Nx - ex[q].col, "FIR hoff == lag*Nx - col");
+      EXPECT(F.perm[e] == ex[q].perm, "FIR perm == slice offset + position in the slice");
+    }
+  }
+  // perm as a whole: injective, never into Sx[0], never at a stored-false entry
+  std::vector<int32_t> sorted(F.perm);
+  std::sort(sorted.begin(), sorted.end());
+  EXPECT(std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end(), "FIR perm injective");
+  EXPECT(sorted.empty() || (sorted.front() >= (int64_t)M.x[0].ri.size() && sorted.back() < off), "FIR perm outside Sx[0], inside the array");
+  for (int64_t f : forbidden) EXPECT(!std::binary_search(sorted.begin(), sorted.end(), (int32_t)f), "FIR perm points at Sx[0] or a stored-false entry");
+  // history addresses: 1 ≤ hoff ≤ T·Nx, so that (k+T)·Nx − hoff stays inside the T zero slots in front at k = 1
+  for (int32_t h : F.hoff) EXPECT(h >= 1 && h <= T * P.Nx, "FIR hoff range");
+  // orphans and the row-oriented plant
+  std::vector<int32_t> orphans;
+  for (int64_t j = 0; j < P.Nu; ++j) if (P.B2.cp[j + 1] == P.B2.cp[j]) orphans.push_back((int32_t)j);
+  EXPECT(F.orphan == orphans, "orphan list == empty B2 columns");
+  csr_equals_csc(F.A, P.A, base); csr_equals_csc(F.B1, P.B1, base); csr_equals_csc(F.B2, P.B2, base);
+}
+
+// random masks that no recipe produced: slice `empty_x` of Sx and `empty_u` of Su hold nothing, one entry of Sx[1] (when there
+// is one) and one of Su[0] are stored false
+Masks random_masks(int64_t Nx, int64_t Nu, int64_t T, int base, unsigned seed, int64_t empty_x, int64_t empty_u) {
+  std::mt19937 g(seed);
+  std::uniform_real_distribution<double> u(0.0, 1.0);
+  Masks M; M.x.resize(T); M.u.resize(T);
+  auto fill = [&](Csc& m, int64_t nr, double density) {
+    m.nr = nr; m.nc = Nx; m.cp.assign(Nx + 1, base);
+    for (int64_t c = 0; c < Nx; ++c) {
+      for (int64_t r = 0; r < nr; ++r) if (u(g) < density) m.ri.push_back(r + base);
+      m.cp[c + 1] = (int64_t)m.ri.size() + base;
+    }
+  };
+  for (int64_t t = 0; t < T; ++t) {
+    fill(M.x[t], Nx, t == empty_x ? 0.0 : t == 0 ? 0.1 : 0.35);
+    fill(M.u[t], Nu, t == empty_u ? 0.0 : 0.4);
+  }
+  if (T > 1 && M.x[1].ri.size() > 2) { M.x[1].b.assign(M.x[1].ri.size(), 1); M.x[1].b[2] = 0; }
+  if (M.u[0].ri.size() > 1) { M.u[0].b.assign(M.u[0].ri.size(), 1); M.u[0].b.back() = 0; }
+  for (int64_t t = 0; t < T; ++t) { M.bx.push_back(M.x[t].boolean()); M.bu.push_back(M.u[t].boolean()); }
+  return M;
+}
+
+// the closed-loop operator at its small edges: T = 1 (no β entries), Nu = 0, an empty slice next to stored-false entries,
+// an actuator without a state
+void exercise_fir_edges(int base) {
+  Plant P = random_plant(11, base, 5u);                                  // Nu = 5
+  check_fir(P, random_masks(P.Nx, P.Nu, 1, base, 21u, -1, -1), 1, base);
+  check_fir(P, random_masks(P.Nx, P.Nu, 5, base, 22u, 2, 3), 5, base);
+  {                                                                      // actuator 1 drives nothing: an empty B2 column
+    std::vector<std::vector<double>> B2(P.Nx, std::vector<double>(P.Nu, 0.0));
+    for (int64_t j = 0; j < P.Nu; ++j) if (j != 1) { B2[2 * j][j] = 1.0; if (j == 3) B2[9][j] = -0.5; }
+    Plant Q = P; Q.B2 = from_dense(B2, P.Nx, P.Nu, base);
+    check_fir(Q, random_masks(Q.Nx, Q.Nu, 4, base, 23u, -1, 0), 4, base);
+  }
+  Plant Z = P; Z.Nu = 0; Z.B2 = from_dense(std::vector<std::vector<double>>(P.Nx), P.Nx, 0, base);
+  check_fir(Z, random_masks(Z.Nx, 0, 3, base, 24u, -1, -1), 3, base);
+  std::printf("fir_edges base=%d: done\n", base);
+}
+
 void exercise(const Plant& P, int64_t d, int64_t T, int base, bool irregular, const char* name) {
   Masks M = make_masks(P, d, T, 1.5, base);
   if (irregular) {                                    // a stored-false entry: forces the explicit tables (no compact layout)
@@ -199,9 +324,7 @@ void exercise(const Plant& P, int64_t d, int64_t T, int base, bool irregular, co
   EXPECT(sls::mask_recipe_inputs(&dims, &A, &B2, d, 1.5, kx, ku, kmax, a_cp, a_ri, b_rp, b_ci, msg) == 0, "mask_recipe_inputs");
   EXPECT(sls::index_set_inputs(&dims, &A, &M.bx[T - 1], &M.bu[T - 1], a_cp, a_ri, sx_cp, sx_ri, su_cp, su_ri, msg) == 0, "index_set_inputs");
   // closed-loop operator
-  sls::FirOperator F;
-  EXPECT(sls::build_fir_operator(&dims, &A, &B1, &B2, M.bx.data(), M.bu.data(), F, msg) == 0, "build_fir_operator");
-  for (int32_t p : F.perm) EXPECT(p >= 0 && p < F.n_values, "FIR perm range");
+  check_fir(P, M, T, base);
   // malformed inputs must be refused, not read out of bounds
   {
     Csc bad = P.A; if (!bad.ri.empty()) bad.ri[0] = P.Nx + 5 + base;             // row out of range
@@ -232,6 +355,7 @@ int main() {
     exercise(chain(30, base, false), 3, 8, base, true, "chain30_irregular");
     exercise(grid(9, base), 2, 6, base, false, "grid9");
     exercise(random_plant(70, base, 11u + base), 2, 7, base, false, "random70");
+    exercise_fir_edges(base);
   }
   // worker pool: a pass large enough for several threads (Nx/256 ≥ 2)
   exercise(chain(600, 0, false), 6, 12, 0, false, "chain600");
