@@ -264,6 +264,46 @@ int  sls_plan_refine(sls_plan* plan, const sls_dims* dims, const sls_plant* P,
                      const sls_csc_bool* Sx, const sls_csc_bool* Su,
                      int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols,
                      void* hip_stream, double* d_values, int packed, int64_t* n_refined);
+/* ---- new values of A and B2 for a live plan (same non-zero pattern: no rebuild) ---------------------------------------------
+ * Masks, index sets, destinations, launch list and workspace depend on the pattern of (A≠0), (B2≠0) alone; only the plan's copy
+ * of the operator (and the four-wave kernel's prepared records, gathered from it) holds numbers.  sls_plan_update_plant rewrites
+ * those on `hip_stream`; the next sls_plan_execute solves the new plant.
+ *   A_nzval [nnz(A)], B2_nzval [nnz(B2)]: the CSC nzval arrays, in the order of the matrices the plan was built from.  Either may
+ *     be NULL (unchanged); both NULL is a no-op that returns 0.
+ *   on_device = 0: HOST arrays, not kept after return.  on_device = 1: DEVICE pointers on the plan's device, read on `hip_stream`
+ *     (they must stay valid and unchanged until the update has run there).
+ * Ordering: the call enqueues on `hip_stream` and returns, like sls_plan_execute (host arrays up to 8 MiB go through the
+ * context's pinned buffer; larger ones are copied synchronously).  sls_plan_execute joins its auxiliary streams back into the
+ * caller's stream before it ends, so an update enqueued on the same stream after an execute runs behind all of that execute's
+ * launches, and an execute enqueued after the update sees the new values.  Executes of this plan on OTHER streams are the
+ * caller's to order against the update (sls_plan_synchronize, or an event).
+ * The zero rule: kernel selection sized the kernels' LDS lists from the NON-ZERO counts at plan time, and the gathers skip zeros
+ * at run time.  A non-zero entry may therefore take any finite value, 0.0 included; an entry that was exactly 0.0 when the plan
+ * was built must stay 0.0 (a gather could overrun its list otherwise); non-finite values are refused too.
+ *   host path:   checked before anything is enqueued — SLS_EINVAL, the message names the matrix and the nzval position, the
+ *                plan is untouched.
+ *   device path: the kernel checks each entry; an offending entry is not written and is counted.  sls_plan_update_result waits
+ *                for the last update and returns the count (0 = applied in full; always 0 after a host-path update).  A non-zero
+ *                count means the operator is a mix of old and new values — safe (the capacities hold), but the caller repeats
+ *                the update with valid values.
+ * Equivalence: when the new values have the non-zero pattern of the plan-time values, the plan is equivalent to one built from
+ * the new plant.  When an entry goes to 0.0 the plan keeps its plan-time index sets — a superset of what the reference would now
+ * compute (src/reduction.jl:14 reads (A≠0) by value), whose extra rows are still constrained — so the results may differ from a
+ * fresh plan's.
+ * Only A and B2 change: B1, C1, D11, D12 and the ridge term stay plan constants, and sls_plan_objective (which reads neither A
+ * nor B2) stays correct.  Which columns are near-singular depends on the values: an update detaches and frees a refinement
+ * attached by sls_plan_refine (waiting for the plan's last execute first); run sls_plan_refine again with the new plant.  Works
+ * for every plan kind (sls_h2_sf_plan, sls_h2_sf_plan_localized, both objectives, either layout).  A closed-loop simulator
+ * (sls_closed_loop_plan) keeps its own copy of the plant and is not updated.                                                   */
+int  sls_plan_update_plant(sls_plan* plan, void* hip_stream, const double* A_nzval, const double* B2_nzval, int on_device);
+int  sls_plan_update_result(sls_plan* plan, int64_t* n_rejected);
+/* The operator values the plan holds now, as CSC nzval arrays in the plan's order (HOST outputs of nnz(A) / nnz(B2) doubles,
+ * either may be NULL): what the updates so far left on the device, refused entries of the device path at their old values.
+ * Like sls_plan_update_result it waits for the plan's last update and for nothing else on the device (the copy runs on the
+ * plan's own stream behind that update).  A caller that updates from device memory and later needs the plant on the host — to
+ * pass it to sls_plan_refine — reads it here instead of keeping its own copies.  Like every call on a context, the update
+ * entry points are for one thread at a time per context (they share the context's pinned staging buffer).                    */
+int  sls_plan_fetch_plant(sls_plan* plan, double* A_nzval, double* B2_nzval);
 /* ---- objective value of every column, evaluated on the device from the written Φ ------------------------------------------
  * The number the reference's JuMP model calls objective_value(problem) (src/synthesis.jl:52): per subproblem the cost it
  * minimised, at the point that was written — Σₜ‖[C̃1 D̃12]Φ̃[t]B̃1 + D̃11‖²_F for the 𝓗₂ objective (the ridge term of

@@ -66,6 +66,15 @@ int sls_debug_objective_host(const sls_dims* dims, const sls_plant* P, const sls
                              const double* ridge_u, const double* const* phix_vals, const double* const* phiu_vals,
                              double* col_objective, double* total, int64_t* col_terms, double* col_abs);
 
+/* Host twin of sls_plan_update_plant (csrc/sls_symbolic.cpp: apply_operator_update): the four operator value arrays a plan of
+ * (A, B2) holds — A_val / B_val in row order, At_val / Bt_val in the CSC order — after an update with A_nzval / B2_nzval
+ * (either NULL = unchanged), plus the value map row_pos[nnz(A) + nnz(B2)] and the plan-time-zero marks.  Needs no device.
+ * Every output is nullable and is filled even when the update is refused (SLS_EINVAL: the arrays then hold the plan-time
+ * values, untouched). */
+int sls_debug_operator_update_host(const sls_dims* dims, const sls_csc_f64* A, const sls_csc_f64* B2, const double* A_nzval,
+                                   const double* B2_nzval, double* A_val, double* At_val, double* B_val, double* Bt_val,
+                                   int32_t* row_pos, uint8_t* zero);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@
 module SLSMI355X
 
 using SparseArrays
-export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective
+export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!
 
 const LIB = get(ENV, "SLS_MI355X_LIB", "libsls_mi355x.so")
 
@@ -84,6 +84,36 @@ function objective_values(plan::Ptr{Cvoid}, d_values::Ptr{Cvoid}, nsub::Integer;
                plan, d_values, packed ? 1 : 0, J, total)
     rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
     return J, total[]
+end
+
+"""
+    n_rejected = update_plant!(plan, A, B2; stream=C_NULL, wait=true, nnzA=-1, nnzB2=-1)
+
+`sls_plan_update_plant` on a resident plan (a `Ptr{Cvoid}` from `sls_h2_sf_plan`): new values of `A` and / or `B2` (a
+`SparseMatrixCSC{Float64}`, a `Vector{Float64}` of `nzval`, or `nothing` = unchanged), host path; the next `sls_plan_execute`
+solves the new plant without a rebuild.  UNCHECKED: a raw plan pointer carries no pattern, so the caller guarantees that a matrix
+has the stored pattern the plan was built from and that a vector has exactly its `nnz` entries in that CSC order — a shorter array
+makes the library read past its end.  Pass `nnzA` / `nnzB2` (the `nnz` of the plan's matrices) to have the lengths checked.  An entry that was exactly 0.0 when the
+plan was built must stay 0.0 and every value must be finite, else the call errors (`SLS_EINVAL`) and the plan is untouched.  An
+attached refinement is dropped.  With `wait = true` returns `sls_plan_update_result` (0 after a host-path update).
+"""
+function update_plant!(plan::Ptr{Cvoid}, A, B2; stream::Ptr{Cvoid}=C_NULL, wait::Bool=true, nnzA::Integer=-1, nnzB2::Integer=-1)
+    nz(M::SparseMatrixCSC) = convert(Vector{Float64}, nonzeros(M))
+    nz(v::AbstractVector) = convert(Vector{Float64}, v)
+    nz(::Nothing) = nothing
+    a, b = nz(A), nz(B2)
+    (a !== nothing && nnzA >= 0 && length(a) != nnzA) && error("update_plant!: A has $(length(a)) values, the plan stores $nnzA")
+    (b !== nothing && nnzB2 >= 0 && length(b) != nnzB2) && error("update_plant!: B2 has $(length(b)) values, the plan stores $nnzB2")
+    GC.@preserve a b begin
+        rc = ccall((:sls_plan_update_plant, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint), plan, stream,
+                   a === nothing ? Ptr{Float64}(C_NULL) : pointer(a), b === nothing ? Ptr{Float64}(C_NULL) : pointer(b), 0)
+    end
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    wait || return 0
+    n = Ref{Int64}(0)
+    rc = ccall((:sls_plan_update_result, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), plan, n)
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    return n[]
 end
 
 """

@@ -87,6 +87,7 @@ EXPORTS = [
     "sls_closed_loop_plan", "sls_closed_loop_run", "sls_closed_loop_run_host", "sls_closed_loop_last_ms",
     "sls_closed_loop_entries", "sls_closed_loop_destroy",
     "sls_plan_objective", "sls_plan_fetch_objective", "sls_ctx_want_objective", "sls_ctx_last_objective",
+    "sls_plan_update_plant", "sls_plan_update_result", "sls_plan_fetch_plant",
 ]
 
 _lib = None
@@ -179,9 +180,15 @@ def load_library(path: str | None = None):
     lib.sls_plan_fetch_objective.restype = C.c_int; lib.sls_plan_fetch_objective.argtypes = [vp, vp, C.c_int, dp, dp]
     lib.sls_ctx_want_objective.restype = C.c_int; lib.sls_ctx_want_objective.argtypes = [vp, C.c_int]
     lib.sls_ctx_last_objective.restype = C.c_int; lib.sls_ctx_last_objective.argtypes = [vp, dp, C.c_int64, dp]
+    lib.sls_plan_update_plant.restype = C.c_int; lib.sls_plan_update_plant.argtypes = [vp, vp, vp, vp, C.c_int]
+    lib.sls_plan_update_result.restype = C.c_int; lib.sls_plan_update_result.argtypes = [vp, i64p]
+    lib.sls_plan_fetch_plant.restype = C.c_int; lib.sls_plan_fetch_plant.argtypes = [vp, dp, dp]
     # diagnostics outside the public header
     lib.sls_debug_objective_host.restype = C.c_int
     lib.sls_debug_objective_host.argtypes = common + [dp, dp, dpp, dpp, dp, dp, i64p, dp]
+    lib.sls_debug_operator_update_host.restype = C.c_int
+    lib.sls_debug_operator_update_host.argtypes = [C.POINTER(sls_dims), C.POINTER(sls_csc_f64), C.POINTER(sls_csc_f64), dp, dp, dp, dp, dp, dp,
+                                                   i32p, C.POINTER(C.c_uint8)]
     lib.sls_debug_tile_invert.restype = C.c_int; lib.sls_debug_tile_invert.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_int]
     lib.sls_plan_debug_read_workspace.restype = C.c_int; lib.sls_plan_debug_read_workspace.argtypes = [vp, C.c_int64, C.c_int64, dp]
     lib.sls_plan_debug_twisted4_tables.restype = C.c_int
@@ -225,6 +232,9 @@ class Marshalled:
         exercise the path the `ccall` binding takes); groups are always given 0-based on the Python side."""
         self.keep = []
         self.base = int(index_base)
+        # A and B2 as handed to the library (references only: struct, colptr, rowval, nzval, nrows), and — once
+        # Plan.update_plant has called own_plant_values — the nzval arrays this object owns and the structs point at
+        self.csc, self.nzval = {}, None
         T = len(Sx)
         if len(Su) != T:
             raise ValueError("𝓢x and 𝓢u must have the same length T")
@@ -232,7 +242,7 @@ class Marshalled:
         self.plant = sls_plant()
         for name, attr in (("A", "A"), ("B1", "B1"), ("B2", "B2"), ("C1", "C1"), ("D11", "D11"), ("D12", "D12")):
             M = getattr(P, attr)
-            setattr(self.plant, name, C.pointer(self._f64(M)) if M is not None else None)
+            setattr(self.plant, name, C.pointer(self._f64(M, name if name in ("A", "B2") else None)) if M is not None else None)
         self.Sx = (sls_csc_bool * T)(*[self._bool(m) for m in Sx])
         self.Su = (sls_csc_bool * T)(*[self._bool(m) for m in Su])
         if groups is None:
@@ -260,14 +270,37 @@ class Marshalled:
         rowval = np.ascontiguousarray(M.indices, dtype=np.int64) + self.base
         return M, colptr, rowval
 
-    def _f64(self, M):
+    def _f64(self, M, track=None):
         M, colptr, rowval = self._csc_arrays(M)
         nz = np.ascontiguousarray(M.data, dtype=np.float64)
         self.keep += [colptr, rowval, nz]
         s = sls_csc_f64(M.shape[0], M.shape[1], colptr.ctypes.data_as(C.POINTER(C.c_int64)),
                         rowval.ctypes.data_as(C.POINTER(C.c_int64)), nz.ctypes.data_as(C.POINTER(C.c_double)))
         self.keep.append(s)
+        if track:
+            self.csc[track] = (s, colptr, rowval, nz, M.shape[0])
         return s
+
+    def pattern(self, name):
+        """0-based (indptr, indices, nrows) of the stored pattern of A or B2 as the library received it"""
+        _, colptr, rowval, _, nrows = self.csc[name]
+        return colptr - self.base, rowval - self.base, nrows
+
+    def nnz(self, name):
+        return int(self.csc[name][3].size)
+
+    def own_plant_values(self):
+        """First Plan.update_plant: from here on the nzval arrays of A and B2 behind the ctypes structs are arrays of this
+        object (never the caller's own, which np.ascontiguousarray may have handed through), so that new values can be
+        written into them.  Nothing is copied for objects that are never updated."""
+        if self.nzval is None:
+            self.nzval = {}
+            for name, (s, _, _, nz, _) in self.csc.items():
+                own = nz.copy()
+                s.nzval = own.ctypes.data_as(C.POINTER(C.c_double))
+                self.keep.append(own)
+                self.nzval[name] = own
+        return self.nzval
 
     def _bool(self, M):
         M, colptr, rowval = self._csc_arrays(M)

@@ -46,6 +46,7 @@ hipError_t launch_level_prefix(const int32_t* cntx, const int32_t* cntu, int Nx,
                                int64_t* totu, hipStream_t stream);
 hipError_t launch_objective(const ObjectiveParams& p, int lds_doubles, double* d_total, hipStream_t stream);
 hipError_t launch_tile_invert(const double* d_A, int n, double* d_ws, double* d_out, bool mlds, hipStream_t stream);
+hipError_t launch_operator_update(const OperatorUpdateParams& p, hipStream_t stream);
 }  // namespace sls
 
 namespace {
@@ -89,7 +90,7 @@ struct sls_plan {
   bool streams_borrowed = false, scratch_borrowed = false, arena_borrowed = false, stream_external = false, ltab_borrowed = false;
   hipEvent_t ev_batch = nullptr, ev_batch_done = nullptr;     // sls_plan_execute_batch fork / join edges
   void* own_scratch = nullptr;
-  Symbolic sym;            // host copy (pools are cleared after upload except what download needs)
+  Symbolic sym;            // host copy (pools are cleared after upload except what download needs; its operator values are the plan-time ones)
   sls_plan_info info{};
   hipStream_t stream = nullptr;
   // device buffers
@@ -102,9 +103,9 @@ struct sls_plan {
   int32_t* d_counters = nullptr;      // one work-queue counter per launch (tile kernel)
   unsigned char* d_big = nullptr;     // big tile launches: their carve buffers (inside the scratch workspace)
   bool has_tile = false;
-  // Prepared records of the four-wave columns (twisted4_prepare_kernel, layout: sls_device.h), written once in plan_finish.
-  // They hold index lists AND the gathered values of A / B2: plan constants like w_pool, because the plan uploads its own copy
-  // of the operator and no entry point changes it.  An entry point that updates operator values has to rerun the kernel.
+  // Prepared records of the four-wave columns (twisted4_prepare_kernel, layout: sls_device.h), written in plan_finish.
+  // They hold index lists AND the gathered values of A / B2, taken from the plan's own copy of the operator:
+  // sls_plan_update_plant reruns the kernel behind every change of that copy.
   unsigned char* d_t4 = nullptr;
   int64_t t4_stride = 0, t4_records = 0;
   struct Launch : LaunchSpec {         // what kernel selection decided + what the launch runs on
@@ -137,6 +138,16 @@ struct sls_plan {
   double* d_colobj = nullptr;
   std::vector<int32_t> obj_gen;
   int obj_lds_doubles = 0;
+  // operator update (sls_plan_update_plant): the value map and plan-time-zero marks (host copy: the host path's check), their
+  // device copies, a staging array for host values (nnzA + nnzB doubles), the refusal counter of the device path and the end
+  // of the last update on the stream it was enqueued on
+  OperatorValueMap opmap;
+  const int32_t* d_upd_pos = nullptr;
+  const uint8_t* d_upd_zero = nullptr;
+  double* d_upd_stage = nullptr;
+  unsigned long long* d_upd_rejected = nullptr;
+  hipEvent_t ev_upd = nullptr;
+  bool upd_recorded = false;
 };
 
 namespace {
@@ -179,6 +190,7 @@ unsigned char* slot_pinned(sls_ctx* ctx, int slot, size_t bytes) {
   { std::lock_guard<std::mutex> l(g_err_mu); ctx_alive = g_live_ctx.count(ctx) > 0; }
   if (!ctx_alive || slot < 0 || slot >= (int)ctx->slots.size() || sls_knob("SLS_PAGEABLE_D2H")) return nullptr;
   sls_ctx::Slot& sl = ctx->slots[slot];
+  if (sl.pinned_pending) { (void)hipEventSynchronize(sl.pinned_busy); sl.pinned_pending = false; }   // an update's H2D copy still reads it
   constexpr size_t kBytes = 8u << 20;
   if (!sl.pinned) {
     if (hipHostMalloc(&sl.pinned, kBytes, hipHostMallocDefault) != hipSuccess) { sl.pinned = nullptr; return nullptr; }
@@ -340,6 +352,18 @@ int wait_plan_done(sls_plan* pl) {
   return 0;
 }
 
+// the prepared records of every four-wave launch of the plan, from the operator values the plan holds now
+hipError_t launch_twisted4_prepares(sls_plan* pl, hipStream_t stream) {
+  for (const auto& L : pl->launches) {
+    if (!(L.kind == LaunchKind::Twisted && L.four)) continue;
+    KernelParams q = pl->kp;
+    q.order_off = L.order_off; q.nsub = L.nsub; q.t4_stride = pl->t4_stride;
+    hipError_t e = launch_twisted4_prepare(q, pl->d_t4 + L.t4_off * pl->t4_stride, stream);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 }  // namespace
 
 extern "C" {
@@ -407,6 +431,7 @@ void sls_destroy(sls_ctx* ctx) {
     if (ctx->slots[i].arena) (void)hipFree(ctx->slots[i].arena);
     if (ctx->slots[i].ltab) (void)hipFree(ctx->slots[i].ltab);
     for (hipStream_t st : ctx->slots[i].dl_streams) if (st) (void)hipStreamDestroy(st);
+    if (ctx->slots[i].pinned_busy) { (void)hipEventSynchronize(ctx->slots[i].pinned_busy); (void)hipEventDestroy(ctx->slots[i].pinned_busy); }
     if (ctx->slots[i].pinned) (void)hipHostFree(ctx->slots[i].pinned);
   }
   delete ctx;
@@ -956,6 +981,13 @@ static int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_pla
     kp.dbg_level = std::max(1, std::atoi(lv));
   }
   if (const char* ko = sls_knob("SLS_KNOCK_OUT")) kp.knock_out = std::atoi(ko);
+  {
+    // operator update: every plan can take new values of A / B2 (the device-resident route's operator comes through here too)
+    build_operator_value_map(S, pl->opmap);
+    const size_t nop = pl->opmap.row_pos.size();
+    if ((rc = upload(pl, pl->opmap.row_pos, &pl->d_upd_pos)) || (rc = upload(pl, pl->opmap.zero, &pl->d_upd_zero))) return bail(rc);
+    if ((rc = dalloc(pl, std::max<size_t>(nop, 1), &pl->d_upd_stage)) || (rc = dalloc(pl, 1, &pl->d_upd_rejected))) return bail(rc);
+  }
   for (auto& L : pl->launches)
     if (L.kind == LaunchKind::Twisted && L.four) { L.t4_off = pl->t4_records; pl->t4_records += L.nsub; }
   if (pl->t4_records) {
@@ -970,14 +1002,9 @@ static int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_pla
                              const_cast<int32_t*>(pl->d_dest), pl->stream);
     if (e != hipSuccess) return bail(hipfail(ctx, e, "launch expand_tables_kernel"));
   }
-  // four-wave launches: the per-column records, once, behind the tables they read (same stream)
-  for (const auto& L : pl->launches) {
-    if (!(L.kind == LaunchKind::Twisted && L.four)) continue;
-    KernelParams q = kp;
-    q.order_off = L.order_off; q.nsub = L.nsub; q.t4_stride = pl->t4_stride;
-    e = launch_twisted4_prepare(q, pl->d_t4 + L.t4_off * pl->t4_stride, pl->stream);
-    if (e != hipSuccess) return bail(hipfail(ctx, e, "launch twisted4_prepare_kernel"));
-  }
+  // four-wave launches: the per-column records, behind the tables they read (same stream)
+  e = launch_twisted4_prepares(pl, pl->stream);
+  if (e != hipSuccess) return bail(hipfail(ctx, e, "launch twisted4_prepare_kernel"));
   // the plan's own set-up work (status clear, table expansion) ran on the plan's stream: wait for that stream only — a
   // device-wide wait here would also wait for whatever the caller has in flight on other streams (an RCCL collective, another plan)
   e = hipStreamSynchronize(pl->stream);
@@ -1382,6 +1409,104 @@ int sls_plan_execute(sls_plan* plan, void* hip_stream, double* d_values, int pac
   return 0;
 }
 
+int sls_plan_update_plant(sls_plan* plan, void* hip_stream, const double* A_nzval, const double* B2_nzval, int on_device) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  if (!A_nzval && !B2_nzval) return 0;
+  sls_ctx* ctx = plan->ctx;
+  const OperatorValueMap& M = plan->opmap;
+  if (!on_device) {                        // everything is checked before anything is enqueued: a refused update leaves the plan as it was
+    std::string msg;
+    if (int rc = check_operator_update(M, A_nzval, B2_nzval, msg)) return fail(ctx, rc, msg);
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCHK(ctx, hipSetDevice(plan->dev));
+  if (!plan->ev_upd) HIPCHK(ctx, hipEventCreateWithFlags(&plan->ev_upd, hipEventDisableTiming));
+  const KernelParams& kp = plan->kp;
+  OperatorUpdateParams up{};
+  up.nnzA = M.nnzA; up.nnzB = M.nnzB;
+  up.row_pos = plan->d_upd_pos; up.zero = plan->d_upd_zero;
+  up.A_val = const_cast<double*>(kp.A_val); up.At_val = const_cast<double*>(kp.At_val);
+  up.B_val = const_cast<double*>(kp.B_val); up.Bt_val = const_cast<double*>(kp.Bt_val);
+  up.rejected = plan->d_upd_rejected;
+  if (on_device) {
+    up.newA = A_nzval; up.newB = B2_nzval;
+  } else {
+    // host arrays are not kept after return: into the slot's pinned buffer (laid out like the staging array: A's values, then
+    // B2's) and from there by asynchronous copies on the caller's stream, behind whatever still reads the staging array
+    const size_t nA = (size_t)M.nnzA, nB = (size_t)M.nnzB;
+    double* pin = reinterpret_cast<double*>(slot_pinned(ctx, plan->slot, (nA + nB) * sizeof(double)));
+    const double* srcA = A_nzval; const double* srcB = B2_nzval;
+    if (pin) {
+      if (A_nzval && nA) { std::memcpy(pin, A_nzval, nA * sizeof(double)); srcA = pin; }
+      if (B2_nzval && nB) { std::memcpy(pin + nA, B2_nzval, nB * sizeof(double)); srcB = pin + nA; }
+    }
+    if (A_nzval && nA) HIPCHK(ctx, hipMemcpyAsync(plan->d_upd_stage, srcA, nA * sizeof(double), hipMemcpyHostToDevice, st));
+    if (B2_nzval && nB) HIPCHK(ctx, hipMemcpyAsync(plan->d_upd_stage + nA, srcB, nB * sizeof(double), hipMemcpyHostToDevice, st));
+    if (pin) {
+      sls_ctx::Slot& sl = ctx->slots[plan->slot];
+      if (!sl.pinned_busy) HIPCHK(ctx, hipEventCreateWithFlags(&sl.pinned_busy, hipEventDisableTiming));
+      HIPCHK(ctx, hipEventRecord(sl.pinned_busy, st));
+      sl.pinned_pending = true;
+    } else {
+      HIPCHK(ctx, hipStreamSynchronize(st));           // no pinned buffer (or too small): the copy has read the caller's arrays
+    }
+    up.newA = A_nzval ? plan->d_upd_stage : nullptr;
+    up.newB = B2_nzval ? plan->d_upd_stage + nA : nullptr;
+  }
+  HIPCHK(ctx, hipMemsetAsync(plan->d_upd_rejected, 0, sizeof(unsigned long long), st));
+  hipError_t e = launch_operator_update(up, st);
+  if (e != hipSuccess) return hipfail(ctx, e, "launch operator_update_kernel");
+  // the four-wave records are the only other place that holds operator values
+  e = launch_twisted4_prepares(plan, st);
+  if (e != hipSuccess) return hipfail(ctx, e, "launch twisted4_prepare_kernel");
+  HIPCHK(ctx, hipEventRecord(plan->ev_upd, st));
+  plan->upd_recorded = true;
+  if (plan->refine) {
+    // which columns are near-singular depends on the values: the attached pass goes — only now that the update is enqueued in
+    // full (a failure above leaves it attached), and after the last execute, which runs it, has ended; the caller runs
+    // sls_plan_refine again with the new plant
+    if (int rc = wait_plan_done(plan)) return rc;
+    sls_plan_destroy(plan->refine);
+    plan->refine = nullptr; plan->refine_dst.clear();
+  }
+  return 0;
+}
+
+// What the update entry points read back: behind the last update (an event edge into the plan's own stream), copied there and
+// waited for there — nothing else on the device is waited for.  `bytes` ≤ the slot's pinned buffer goes through it.
+static int read_behind_update(sls_plan* plan, void* dst, const void* d_src, size_t bytes) {
+  if (bytes == 0) return 0;
+  hipStream_t ps = plan->stream;
+  if (plan->upd_recorded) HIPCHK(plan->ctx, hipStreamWaitEvent(ps, plan->ev_upd, 0));
+  unsigned char* pin = slot_pinned(plan->ctx, plan->slot, bytes);
+  HIPCHK(plan->ctx, hipMemcpyAsync(pin ? static_cast<void*>(pin) : dst, d_src, bytes, hipMemcpyDeviceToHost, ps));
+  HIPCHK(plan->ctx, hipStreamSynchronize(ps));
+  if (pin) std::memcpy(dst, pin, bytes);
+  return 0;
+}
+
+int sls_plan_update_result(sls_plan* plan, int64_t* n_rejected) {
+  if (!plan || !n_rejected) return fail(nullptr, SLS_EINVAL, "null argument");
+  *n_rejected = 0;
+  if (!plan->upd_recorded) return 0;
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  unsigned long long n = 0;
+  if (int rc = read_behind_update(plan, &n, plan->d_upd_rejected, sizeof(n))) return rc;
+  *n_rejected = (int64_t)n;
+  return 0;
+}
+
+int sls_plan_fetch_plant(sls_plan* plan, double* A_nzval, double* B2_nzval) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  // At_val / Bt_val are the CSC nzval order itself
+  if (A_nzval)
+    if (int rc = read_behind_update(plan, A_nzval, plan->kp.At_val, (size_t)plan->opmap.nnzA * sizeof(double))) return rc;
+  if (B2_nzval)
+    if (int rc = read_behind_update(plan, B2_nzval, plan->kp.Bt_val, (size_t)plan->opmap.nnzB * sizeof(double))) return rc;
+  return 0;
+}
+
 int sls_plan_execute_batch(sls_plan* const* plans, int nplans, void* hip_stream, double* const* d_values, int packed) {
   if (nplans < 0 || (nplans > 0 && (!plans || !d_values))) return fail(nullptr, SLS_EINVAL, "null argument");
   if (nplans == 0) return 0;
@@ -1566,6 +1691,28 @@ int sls_debug_objective_host(const sls_dims* dims, const sls_plant* P, const sls
     if (nu > 0) std::copy(phiu_vals[t], phiu_vals[t] + nu, vals.begin() + S.off_u[t]);
   }
   rc = objective_host(S, (dims->flags & SLS_SOLVE_SUM_OF_NORMS) ? 1 : 0, vals.data(), col_objective, total, col_terms, col_abs, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): the host twin of sls_plan_update_plant — the operator arrays of a plan of (A, B2),
+   the value map and zero marks, then apply_operator_update with the new nzval arrays.  Needs no device. */
+int sls_debug_operator_update_host(const sls_dims* dims, const sls_csc_f64* A, const sls_csc_f64* B2, const double* A_nzval,
+                                   const double* B2_nzval, double* A_val, double* At_val, double* B_val, double* Bt_val,
+                                   int32_t* row_pos, uint8_t* zero) {
+  Symbolic S;
+  std::string msg;
+  int rc = operator_csr_checked(dims, A, B2, S, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  OperatorValueMap M;
+  build_operator_value_map(S, M);
+  rc = apply_operator_update(S, M, A_nzval, B2_nzval, msg);
+  if (A_val) std::copy(S.A_csr.val.begin(), S.A_csr.val.end(), A_val);
+  if (At_val) std::copy(S.At_csr.val.begin(), S.At_csr.val.end(), At_val);
+  if (B_val) std::copy(S.B_csr.val.begin(), S.B_csr.val.end(), B_val);
+  if (Bt_val) std::copy(S.Bt_csr.val.begin(), S.Bt_csr.val.end(), Bt_val);
+  if (row_pos) std::copy(M.row_pos.begin(), M.row_pos.end(), row_pos);
+  if (zero) std::copy(M.zero.begin(), M.zero.end(), zero);
   if (rc) return fail(nullptr, rc, msg);
   return 0;
 }
@@ -1795,6 +1942,7 @@ void sls_plan_destroy(sls_plan* plan) {
   if (plan->ev_done) (void)hipEventDestroy(plan->ev_done);
   if (plan->ev_batch) (void)hipEventDestroy(plan->ev_batch);
   if (plan->ev_batch_done) (void)hipEventDestroy(plan->ev_batch_done);
+  if (plan->ev_upd) (void)hipEventDestroy(plan->ev_upd);
   if (plan->stream && !plan->streams_borrowed && !plan->stream_external) (void)hipStreamDestroy(plan->stream);
   if (ctx_alive && plan->slot < (int)plan->ctx->slots.size()) {
     if (plan->streams_borrowed) plan->ctx->slots[plan->slot].streams_in_use = 0;

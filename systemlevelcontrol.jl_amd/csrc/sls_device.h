@@ -301,4 +301,18 @@ struct ColumnTableParams {
   int32_t* idx_pool;  uint64_t* cmask;  int32_t* cbase;
 };
 
+// ---- operator update (sls_update.hip: operator_update_kernel) ----
+// Entry k < nnzA is position k of A's CSC nzval, entry nnzA + j position j of B2's.  At_val / Bt_val hold the CSC order itself;
+// row_pos[k] is the entry's place in A_val / B_val (OperatorValueMap, sls_symbolic.h), zero[k] the plan-time-zero mark.
+struct OperatorUpdateParams {
+  int64_t nnzA, nnzB;
+  const double* newA;       // nnzA new values, or NULL: A unchanged
+  const double* newB;       // nnzB new values, or NULL: B2 unchanged
+  const int32_t* row_pos;   // [nnzA + nnzB]
+  const uint8_t* zero;      // [nnzA + nnzB]
+  double* A_val;  double* At_val;
+  double* B_val;  double* Bt_val;
+  unsigned long long* rejected;   // entries refused (not finite, or non-zero on a plan-time zero): counted, not written
+};
+
 }  // namespace sls

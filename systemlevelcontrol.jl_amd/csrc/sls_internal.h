@@ -31,6 +31,9 @@ struct sls_ctx {
     void* ltab = nullptr; size_t ltab_bytes = 0; bool ltab_in_use = false;         // device-built tables of the localized route (same idea)
     // pinned staging ring of the download (sls_plan_download): kDlLanes lanes, each its own stream and pinned chunk
     void* pinned = nullptr; size_t pinned_bytes = 0;
+    // sls_plan_update_plant leaves an asynchronous H2D copy reading the pinned buffer: the next user waits for this event first.
+    // Plain state like the "in use" flags above: it relies on the same rule, one thread at a time per context.
+    hipEvent_t pinned_busy = nullptr; bool pinned_pending = false;
     std::vector<hipStream_t> dl_streams;
   };
   std::vector<Slot> slots;

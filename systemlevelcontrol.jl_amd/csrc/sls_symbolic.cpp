@@ -76,6 +76,17 @@ void csc_as_csr_of_transpose(const sls_csc_f64* m, int base, HostCsr& out) {
   }
 }
 
+// Where csc_to_csr put every CSC position: the same walk (columns ascending, a write cursor per row) over the CSC storage the
+// plan kept as At_csr / Bt_csr, starting from the row pointers of A_csr / B_csr.
+void value_map_of(const HostCsr& rows, const HostCsr& csc, int32_t* row_pos, uint8_t* zero) {
+  std::vector<int32_t> w(rows.ptr.begin(), rows.ptr.end() - 1);
+  const int64_t nnz = (int64_t)csc.idx.size();
+  for (int64_t k = 0; k < nnz; ++k) {
+    row_pos[k] = w[csc.idx[k]]++;
+    zero[k] = csc.val[k] == 0.0 ? 1 : 0;
+  }
+}
+
 bool weights_are_default(const Inputs& in) {
   const sls_plant* P = in.P;
   const int base = in.dims->index_base;
@@ -111,6 +122,76 @@ bool weights_are_default(const Inputs& in) {
 }
 
 }  // namespace
+
+void fill_operator_csr(const sls_csc_f64* A, const sls_csc_f64* B2, int base, Symbolic& S) {
+  csc_to_csr(A, base, S.A_csr);
+  csc_as_csr_of_transpose(A, base, S.At_csr);
+  csc_to_csr(B2, base, S.B_csr);
+  csc_as_csr_of_transpose(B2, base, S.Bt_csr);
+  auto longest = [](const HostCsr& M) {
+    int32_t mx = 1;
+    for (int64_t r = 0; r < M.nrows; ++r) mx = std::max(mx, M.ptr[r + 1] - M.ptr[r]);
+    return mx;
+  };
+  S.max_row_A = longest(S.A_csr); S.max_row_At = longest(S.At_csr);
+  S.max_row_B = longest(S.B_csr); S.max_row_Bt = longest(S.Bt_csr);
+}
+
+int operator_csr_checked(const sls_dims* dims, const sls_csc_f64* A, const sls_csc_f64* B2, Symbolic& S, std::string& msg) {
+  if (!dims) { msg = "null dims"; return SLS_EINVAL; }
+  if (dims->index_base != 0 && dims->index_base != 1) { msg = "index_base must be 0 or 1"; return SLS_EINVAL; }
+  if (dims->Nx <= 0 || dims->Nu < 0 || dims->Nx > 0x7fffffffLL || dims->Nu > 0x7fffffffLL) { msg = "bad Nx / Nu"; return SLS_EINVAL; }
+  int rc;
+  if ((rc = check_csc(A, dims->Nx, dims->Nx, dims->index_base, "A", msg))) return rc;
+  if ((rc = check_csc(B2, dims->Nx, dims->Nu, dims->index_base, "B2", msg))) return rc;
+  S.Nx = dims->Nx; S.Nu = dims->Nu;
+  fill_operator_csr(A, B2, dims->index_base, S);
+  return 0;
+}
+
+void build_operator_value_map(const Symbolic& S, OperatorValueMap& M) {
+  M.nnzA = (int64_t)S.At_csr.val.size(); M.nnzB = (int64_t)S.Bt_csr.val.size();
+  M.row_pos.assign((size_t)(M.nnzA + M.nnzB), 0);
+  M.zero.assign((size_t)(M.nnzA + M.nnzB), 0);
+  if (M.nnzA) value_map_of(S.A_csr, S.At_csr, M.row_pos.data(), M.zero.data());
+  if (M.nnzB) value_map_of(S.B_csr, S.Bt_csr, M.row_pos.data() + M.nnzA, M.zero.data() + M.nnzA);
+}
+
+int check_operator_update(const OperatorValueMap& M, const double* A_nzval, const double* B2_nzval, std::string& msg) {
+  const double* src[2] = {A_nzval, B2_nzval};
+  const int64_t n[2] = {M.nnzA, M.nnzB}, first[2] = {0, M.nnzA};
+  const char* name[2] = {"A", "B2"};
+  for (int q = 0; q < 2; ++q) {
+    if (!src[q]) continue;
+    for (int64_t k = 0; k < n[q]; ++k) {
+      const double v = src[q][k];
+      if (!std::isfinite(v)) {
+        msg = std::string("operator update: ") + name[q] + " nzval position " + std::to_string(k) + " is not finite";
+        return SLS_EINVAL;
+      }
+      if (M.zero[(size_t)(first[q] + k)] && v != 0.0) {
+        msg = std::string("operator update: ") + name[q] + " nzval position " + std::to_string(k) +
+              " was 0.0 when the plan was built and must stay 0.0 (the plan's list capacities count non-zeros)";
+        return SLS_EINVAL;
+      }
+    }
+  }
+  return 0;
+}
+
+int apply_operator_update(Symbolic& S, const OperatorValueMap& M, const double* A_nzval, const double* B2_nzval, std::string& msg) {
+  if ((int64_t)S.At_csr.val.size() != M.nnzA || (int64_t)S.A_csr.val.size() != M.nnzA || (int64_t)S.Bt_csr.val.size() != M.nnzB ||
+      (int64_t)S.B_csr.val.size() != M.nnzB || (int64_t)M.row_pos.size() != M.nnzA + M.nnzB || M.zero.size() != M.row_pos.size()) {
+    msg = "operator update: the value map does not belong to this symbolic pass";
+    return SLS_EINVAL;
+  }
+  if (int rc = check_operator_update(M, A_nzval, B2_nzval, msg)) return rc;
+  if (A_nzval)
+    for (int64_t k = 0; k < M.nnzA; ++k) { S.At_csr.val[(size_t)k] = A_nzval[k]; S.A_csr.val[(size_t)M.row_pos[(size_t)k]] = A_nzval[k]; }
+  if (B2_nzval)
+    for (int64_t k = 0; k < M.nnzB; ++k) { S.Bt_csr.val[(size_t)k] = B2_nzval[k]; S.B_csr.val[(size_t)M.row_pos[(size_t)(M.nnzA + k)]] = B2_nzval[k]; }
+  return 0;
+}
 
 int validate_inputs(const Inputs& in, std::string& msg) {
   if (!in.dims || !in.P) { msg = "null dims/plant"; return SLS_EINVAL; }
@@ -374,17 +455,7 @@ int localized_prepare(const sls_dims* dims, const sls_plant* P, int64_t d, doubl
   if ((rc = mask_recipe_inputs(dims, P->A, P->B2, d, alpha, L.kx, L.ku, L.kmax, L.a_cp, L.a_ri, L.b_rp, L.b_ci, msg))) return rc;
   if (L.kmax + 2 > 62) { msg = "localization radius d + 2 > 62 levels: use the mask-based entry point"; return SLS_EUNSUPPORTED; }
   S.Nx = dm.Nx; S.Nu = dm.Nu; S.T = dm.T;
-  csc_to_csr(P->A, b, S.A_csr);
-  csc_as_csr_of_transpose(P->A, b, S.At_csr);
-  csc_to_csr(P->B2, b, S.B_csr);
-  csc_as_csr_of_transpose(P->B2, b, S.Bt_csr);
-  auto longest = [](const HostCsr& M) {
-    int32_t mx = 1;
-    for (int64_t r = 0; r < M.nrows; ++r) mx = std::max(mx, M.ptr[r + 1] - M.ptr[r]);
-    return mx;
-  };
-  S.max_row_A = longest(S.A_csr); S.max_row_At = longest(S.At_csr);
-  S.max_row_B = longest(S.B_csr); S.max_row_Bt = longest(S.Bt_csr);
+  fill_operator_csr(P->A, P->B2, b, S);
   return 0;
 }
 
@@ -867,17 +938,7 @@ int build_symbolic(const Inputs& in, int64_t gbeg, int64_t gend, Symbolic& S, st
   S.n_values = S.off_u[T];
   if (S.n_values > 0x7fffffffLL) { msg = "more than 2^31 values in Φ: not supported by this build"; return SLS_EUNSUPPORTED; }
 
-  csc_to_csr(in.P->A, base, S.A_csr);
-  csc_as_csr_of_transpose(in.P->A, base, S.At_csr);
-  csc_to_csr(in.P->B2, base, S.B_csr);
-  csc_as_csr_of_transpose(in.P->B2, base, S.Bt_csr);
-  auto longest = [](const HostCsr& M) {
-    int32_t mx = 1;
-    for (int64_t r = 0; r < M.nrows; ++r) mx = std::max(mx, M.ptr[r + 1] - M.ptr[r]);
-    return mx;
-  };
-  S.max_row_A = longest(S.A_csr); S.max_row_At = longest(S.At_csr);
-  S.max_row_B = longest(S.B_csr); S.max_row_Bt = longest(S.Bt_csr);
+  fill_operator_csr(in.P->A, in.P->B2, base, S);
 
   const bool dbg_t = sls_knob("SLS_DEBUG_TIMING") != nullptr;
   auto clk = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };

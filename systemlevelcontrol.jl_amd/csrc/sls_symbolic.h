@@ -160,6 +160,32 @@ struct LocalizedHost {
 };
 int localized_prepare(const sls_dims* dims, const sls_plant* P, int64_t d, double alpha, Symbolic& S, LocalizedHost& L, std::string& msg);
 
+// The shared operator of a plan: A and B2 in row order (A_csr, B_csr) and their CSC storage read as CSR of the transposes
+// (At_csr, Bt_csr), with the longest rows.  build_symbolic and localized_prepare both come through here; matrices already checked.
+void fill_operator_csr(const sls_csc_f64* A, const sls_csc_f64* B2, int base, Symbolic& S);
+// the same after checking A (Nx×Nx) and B2 (Nx×Nu) alone — for callers without masks (the update's host twin in the tests)
+int operator_csr_checked(const sls_dims* dims, const sls_csc_f64* A, const sls_csc_f64* B2, Symbolic& S, std::string& msg);
+
+// ---- operator update (sls_plan_update_plant): new values of A / B2 for a plan whose pattern stays ----
+// A plan holds the operator four times: A_csr / B_csr (row order) and At_csr / Bt_csr, which ARE the caller's CSC storage
+// (csc_as_csr_of_transpose copies nzval verbatim: position k of the caller's nzval is position k of At_val / Bt_val, no map
+// needed).  row_pos[k] is where csc_to_csr put CSC position k in A_csr.val (k < nnzA) or, for k = nnzA + j, where it put position
+// j of B2 in B_csr.val.  zero[k] marks the entries that were exactly 0.0 when the plan was built: kernel selection sized its
+// LDS lists from the non-zero counts, so those entries must stay 0.0 (the zero rule).
+struct OperatorValueMap {
+  int64_t nnzA = 0, nnzB = 0;
+  std::vector<int32_t> row_pos;   // nnzA + nnzB
+  std::vector<uint8_t> zero;      // nnzA + nnzB
+};
+// from S.A_csr / S.At_csr / S.B_csr / S.Bt_csr as build_symbolic or localized_prepare left them
+void build_operator_value_map(const Symbolic& S, OperatorValueMap& M);
+// the finite rule and the zero rule over the given arrays (either may be NULL = unchanged): 0, or SLS_EINVAL with a message
+// that names the matrix and the 0-based nzval position of the first offender
+int check_operator_update(const OperatorValueMap& M, const double* A_nzval, const double* B2_nzval, std::string& msg);
+// host twin of operator_update_kernel (sls_update.hip): checks first — on a refusal nothing is written — then writes the new
+// values into the four val arrays of S
+int apply_operator_update(Symbolic& S, const OperatorValueMap& M, const double* A_nzval, const double* B2_nzval, std::string& msg);
+
 // predicted cost per group (Σ over its columns of (T+1)·ñx³)
 int group_costs(const Inputs& in, std::vector<double>& cost, std::string& msg);
 

@@ -155,8 +155,62 @@ class Plan:
     def refine(self, d_values, packed=False, stream=None):
         """sls_plan_refine: after an execute, re-solve the near-singular columns of the one-wave / twisted kernels on the tile
         kernel and attach that pass to the plan (later executes run it too).  Returns the number of subproblems refined."""
+        if getattr(self, "_plant_updated", False):       # after updates: pass the plant the device holds
+            own = self.m.own_plant_values()
+            own["A"][:], own["B2"][:] = self.plant_values()
+            self._plant_updated = False
         n = C.c_int64()
         _capi.check(self._lib.sls_plan_refine(self.handle, *self.m.common_args(), stream, d_values, int(packed), C.byref(n)), self.ctx.handle)
+        return n.value
+
+    def update_plant(self, A=None, B2=None, stream=None):
+        """sls_plan_update_plant: new values of A and / or B2 for this plan, enqueued on `stream`; the next `execute` solves
+        the new plant without a rebuild.  Each argument is None (unchanged), a scipy sparse matrix whose stored pattern equals
+        the plan's (ValueError otherwise), a 1-D float64 NumPy array of nzval in the plan's CSC order, or a CUDA torch tensor
+        of nzval, which selects the device path (both arguments must then be tensors, or one of them None; a tensor must stay
+        valid and unchanged until the update has run on `stream`, and is not kept beyond the call).  An entry that was exactly
+        0.0 when the plan was built must stay 0.0 and every value must be finite: the host path raises SLSError (SLS_EINVAL)
+        and leaves the plan untouched, the device path skips such entries and counts them (`update_result`).
+        An attached refinement is dropped — call `refine` again.  The marshalled plant of this object follows: the host path
+        writes the new values into it at once, and `refine` first reads the plan's own values back from the device
+        (`plant_values`), so it always passes the plant the device holds."""
+        given = [(name, v) for name, v in (("A", A), ("B2", B2)) if v is not None]
+        if not given:
+            return
+        on_device = [_is_device_tensor(v) for _, v in given]
+        if any(on_device) != all(on_device):
+            raise ValueError("update_plant: A and B2 must both be host arrays or both be device tensors")
+        ptrs, host = {"A": None, "B2": None}, {}
+        for name, v in given:
+            nnz = self.m.nnz(name)
+            if on_device[0]:
+                if v.dtype != _torch().float64 or v.dim() != 1 or not v.is_contiguous() or v.device.index != self.info["device"]:
+                    raise ValueError(f"update_plant: {name} must be a contiguous 1-D float64 tensor on the plan's device")
+                if v.numel() != nnz:
+                    raise ValueError(f"update_plant: {name} has {v.numel()} values, the plan's {name} stores {nnz}")
+                ptrs[name] = v.data_ptr()
+            else:
+                host[name] = _nzval_of(name, v, nnz, self.m)
+                ptrs[name] = host[name].ctypes.data
+        _capi.check(self._lib.sls_plan_update_plant(self.handle, stream, ptrs["A"], ptrs["B2"], int(on_device[0])), self.ctx.handle)
+        own = self.m.own_plant_values()
+        for name, nz in host.items():
+            own[name][:] = nz
+        self._plant_updated = True
+
+    def plant_values(self):
+        """sls_plan_fetch_plant: (A nzval, B2 nzval) as the plan holds them on the device now — waits for the last
+        `update_plant`; entries its device path refused are at their old values."""
+        a, b = np.zeros(max(self.m.nnz("A"), 1)), np.zeros(max(self.m.nnz("B2"), 1))
+        dp = C.POINTER(C.c_double)
+        _capi.check(self._lib.sls_plan_fetch_plant(self.handle, a.ctypes.data_as(dp), b.ctypes.data_as(dp)), self.ctx.handle)
+        return a[: self.m.nnz("A")], b[: self.m.nnz("B2")]
+
+    def update_result(self):
+        """sls_plan_update_result: waits for the last `update_plant` and returns how many entries its device path refused
+        (0: applied in full; always 0 after a host-path update)."""
+        n = C.c_int64()
+        _capi.check(self._lib.sls_plan_update_result(self.handle, C.byref(n)), self.ctx.handle)
         return n.value
 
     def packed_dest(self):
@@ -260,6 +314,33 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _is_device_tensor(v):
+    t = sys.modules.get("torch")
+    return t is not None and isinstance(v, t.Tensor) and v.is_cuda
+
+
+def _nzval_of(name, v, nnz, m):
+    """The nzval array of a host argument of `Plan.update_plant`: a scipy matrix is checked against the plan's stored pattern."""
+    if sp.issparse(v):
+        M = sp.csc_matrix(v)
+        if not M.has_sorted_indices:
+            M = M.copy(); M.sort_indices()
+        indptr, indices, nrows = m.pattern(name)
+        if M.shape != (nrows, indptr.size - 1) or M.nnz != nnz or not np.array_equal(M.indptr, indptr) or \
+                not np.array_equal(M.indices, indices):
+            raise ValueError(f"update_plant: the stored pattern of {name} differs from the one the plan was built from")
+        v = M.data
+    nz = np.ascontiguousarray(v, dtype=np.float64)
+    if nz.ndim != 1 or nz.size != nnz:
+        raise ValueError(f"update_plant: {name} needs {nnz} nzval entries (1-D), got shape {nz.shape}")
+    return nz
 
 
 class _WantObjective:
