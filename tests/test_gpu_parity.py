@@ -471,10 +471,15 @@ def test_short_horizons(slc, oracle, T, routing, monkeypatch):
         assert np.abs(got[ok] - want[ok]).max() < TOL
 
 
-def test_columns_without_reachable_actuators(slc, gpu_ctx, oracle):
+@pytest.mark.parametrize("routing", ["default", "tile"])
+def test_columns_without_reachable_actuators(slc, oracle, routing, monkeypatch):
     """README chain dynamics with only two actuators, at one end: most columns see ñu = 0 (no input within d+1 hops) and
     are infeasible — the response cannot be killed; the columns next to the actuators are feasible.  Statuses and the
-    feasible values against the oracle; ñu = 0 exercises the empty-input paths of the kernels."""
+    feasible values against the oracle; ñu = 0 exercises the empty-input paths of the kernels — with every column forced
+    onto the tile kernel, those of its plain build too."""
+    if routing == "tile":
+        monkeypatch.setenv("SLS_FORCE_GENERAL", "1")
+    gpu_ctx = slc.Context([0])
     Nx, T, d = 14, 10, 3
     Pc = slc.workloads.chain_plant(Nx)
     B2 = sp.identity(Nx, format="csc")[:, [Nx - 2, Nx - 1]]
@@ -484,7 +489,13 @@ def test_columns_without_reachable_actuators(slc, gpu_ctx, oracle):
     ox, ou, dg = oracle.SLS_H2(Po, S, return_diag=True)
     assert min(d_["m"] for d_ in dg) == 0
     want = np.concatenate([flat_phi(ox, S[0]), flat_phi(ou, S[1])])
+    if routing == "tile":
+        plan = slc.Plan(gpu_ctx, P, S)
+        desc = plan.describe()
+        plan.close()
+        assert desc.count(";") == 1 and desc.startswith("h2_column_tile_kernel<"), desc
     got, _, _, info = _flat(slc, P, S, ctx=gpu_ctx)
+    gpu_ctx.close()
     feasible = np.array([d_["resid"] < 1e-9 for d_ in dg])
     assert np.array_equal(info["col_status"] == 0, feasible)
     cols = np.concatenate([np.repeat(np.arange(P.Nx), np.diff(M.indptr)) for M in S[0] + S[1]])
