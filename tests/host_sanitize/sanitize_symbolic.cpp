@@ -2,7 +2,7 @@
 // built and run by tests/test_host.py::test_symbolic_pass_under_sanitizers with g++ -fsanitize=address,undefined.  Drives every
 // host-only entry the C ABI forwards to — mask recipe, validation, index sets, the full symbolic pass in its four table layouts
 // (explicit / compact × packed / mask order), shard ranges, caller groups (decoupled and coupled), cost model, the inputs of
-// the two device passes, the closed-loop FIR operator (restated exactly from the masks: check_fir), kernel selection (csrc/sls_routing.cpp: the launch list of every shard for
+// the two device passes (also on the hub, long-range, dense and stored-zero plants of tests/symbolic_cases.py), the closed-loop FIR operator (restated exactly from the masks: check_fir), kernel selection (csrc/sls_routing.cpp: the launch list of every shard for
 // 1, 8 and 256 CUs, both objectives, with and without force_tile) — on a chain, a 2-D grid and a random plant, in both index bases, plus
 // malformed inputs that must be refused without touching memory out of bounds.  Exit code 0 = clean.
 #include <algorithm>
@@ -346,6 +346,114 @@ void exercise(const Plant& P, int64_t d, int64_t T, int base, bool irregular, co
   std::printf("%s base=%d irregular=%d: done\n", name, base, (int)irregular);
 }
 
+
+// ---- the plants of the device-pass edge cases (tests/symbolic_cases.py), restated: hub, long-range chain, dense, holes ----
+// built by column (no dense image: the long-range chain has 4200 states); stored zeros are kept as stored entries
+Csc from_columns(const std::vector<std::vector<std::pair<int64_t, double>>>& cols, int64_t nr, int base) {
+  Csc m; m.nr = nr; m.nc = (int64_t)cols.size(); m.cp.assign(cols.size() + 1, base);
+  for (size_t c = 0; c < cols.size(); ++c) {
+    std::vector<std::pair<int64_t, double>> col = cols[c];
+    std::sort(col.begin(), col.end());
+    for (auto& e : col) { m.ri.push_back(e.first + base); m.v.push_back(e.second); }
+    m.cp[c + 1] = (int64_t)m.ri.size() + base;
+  }
+  return m;
+}
+Csc identity(int64_t n, int base) {
+  std::vector<std::vector<std::pair<int64_t, double>>> cols((size_t)n);
+  for (int64_t i = 0; i < n; ++i) cols[(size_t)i].push_back({i, 1.0});
+  return from_columns(cols, n, base);
+}
+std::vector<std::vector<std::pair<int64_t, double>>> chain_columns(int64_t Nx) {
+  std::vector<std::vector<std::pair<int64_t, double>>> cols((size_t)Nx);
+  for (int64_t i = 0; i < Nx; ++i) {
+    cols[(size_t)i].push_back({i, 1.0});
+    if (i + 1 < Nx) { cols[(size_t)i].push_back({i + 1, -0.2}); cols[(size_t)i + 1].push_back({i, 0.2}); }
+  }
+  return cols;
+}
+// unit diagonal, state 0 feeds states 1…m: a level of m + 1 states
+Plant hub_plant(int64_t Nx, int64_t m, int base) {
+  std::vector<std::vector<std::pair<int64_t, double>>> cols((size_t)Nx);
+  for (int64_t i = 0; i < Nx; ++i) cols[(size_t)i].push_back({i, 1.0});
+  for (int64_t j = 1; j <= m; ++j) cols[0].push_back({j, 0.3});
+  return Plant{Nx, Nx, from_columns(cols, Nx, base), identity(Nx, base), identity(Nx, base)};
+}
+// chain with edges 5→2100, 5→4190, 2060→3, 4199→0; an actuator on every third state
+Plant far_plant(int base) {
+  const int64_t Nx = 4200, Nu = Nx / 3;
+  auto cols = chain_columns(Nx);
+  cols[5].push_back({2100, 0.15}); cols[5].push_back({4190, 0.15}); cols[2060].push_back({3, 0.15}); cols[4199].push_back({0, 0.15});
+  std::vector<std::vector<std::pair<int64_t, double>>> b((size_t)Nu);
+  for (int64_t j = 0; j < Nu; ++j) b[(size_t)j].push_back({3 * j, 1.0});
+  return Plant{Nx, Nu, from_columns(cols, Nx, base), identity(Nx, base), from_columns(b, Nx, base)};
+}
+Plant dense_plant(int64_t Nx, int base) {
+  std::vector<std::vector<std::pair<int64_t, double>>> cols((size_t)Nx), b;
+  for (int64_t c = 0; c < Nx; ++c) for (int64_t r = 0; r < Nx; ++r) cols[(size_t)c].push_back({r, 1.0});
+  for (int64_t j = 0; j < Nx; j += 2) b.push_back({{j, 1.0}});
+  return Plant{Nx, (int64_t)b.size(), from_columns(cols, Nx, base), identity(Nx, base), from_columns(b, Nx, base)};
+}
+// stored zeros in A and B2; column 7 of A holds stored zeros only (empty level 1); states 3, 4, 10 drive no actuator; Nu = 0 variant
+Plant holes_plant(int base, bool no_inputs) {
+  const int64_t Nx = 14;
+  auto cols = chain_columns(Nx);
+  cols[2].push_back({0, 0.5}); cols[12].push_back({9, 0.5});
+  for (auto& e : cols[7]) e.second = 0.0;
+  for (auto& e : cols[2]) if (e.first == 1) e.second = 0.0;
+  for (auto& e : cols[11]) if (e.first == 12) e.second = 0.0;
+  std::vector<std::vector<std::pair<int64_t, double>>> b = {{{0, 1.0}, {1, 1.0}}, {{2, 1.0}, {4, 0.0}}, {{5, 1.0}, {6, 1.0}, {7, 1.0}}, {{8, 1.0}, {9, 1.0}}, {{11, 1.0}, {12, 1.0}, {13, 1.0}}};
+  if (no_inputs) b.clear();
+  return Plant{Nx, (int64_t)b.size(), from_columns(cols, Nx, base), identity(Nx, base), from_columns(b, Nx, base)};
+}
+
+// mask recipe and the inputs of the two device passes on such a plant: every mask a valid CSC pattern (pointers monotone,
+// rows ascending and in range), 𝓢x[0] = I, the patterns handed to the device by value (A) and structurally (masks)
+void exercise_device_inputs(const Plant& P, int64_t d, int64_t T, double alpha, int base, int64_t want_level, const char* name) {
+  Masks M = make_masks(P, d, T, alpha, base);
+  int64_t biggest = 0;
+  for (int part = 0; part < 2; ++part)
+    for (int64_t t = 0; t < T; ++t) {
+      const Csc& m = part ? M.u[t] : M.x[t];
+      const int64_t nr = part ? P.Nu : P.Nx;
+      EXPECT(m.cp[0] == base && m.cp[P.Nx] == (int64_t)m.ri.size() + base, "mask pointer ends");
+      for (int64_t c = 0; c < P.Nx; ++c) {
+        EXPECT(m.cp[c] <= m.cp[c + 1], "mask pointers monotone");
+        biggest = std::max(biggest, m.cp[c + 1] - m.cp[c]);
+        for (int64_t k = m.cp[c] - base; k < m.cp[c + 1] - base; ++k) {
+          EXPECT(m.ri[k] - base >= 0 && m.ri[k] - base < nr, "mask row in range");
+          EXPECT(k == m.cp[c] - base || m.ri[k - 1] < m.ri[k], "mask rows ascending");
+        }
+      }
+    }
+  EXPECT((int64_t)M.x[0].ri.size() == P.Nx, "Sx[0] is the identity");
+  EXPECT(want_level < 0 || biggest == want_level, "largest mask column");
+  sls_dims dims{P.Nx, P.Nu, P.Nx + P.Nu, P.Nx, T, base, 0};
+  sls_csc_f64 A = P.A.f64(), B2 = P.B2.f64();
+  std::string msg;
+  std::vector<int32_t> kx, ku, a_cp, a_ri, b_rp, b_ci, sx_cp, sx_ri, su_cp, su_ri;
+  int kmax = 0;
+  EXPECT(sls::mask_recipe_inputs(&dims, &A, &B2, d, alpha, kx, ku, kmax, a_cp, a_ri, b_rp, b_ci, msg) == 0, "mask_recipe_inputs");
+  int64_t nzA = 0, nzB = 0;
+  for (double v : P.A.v) nzA += v != 0.0;
+  for (double v : P.B2.v) nzB += v != 0.0;
+  EXPECT((int64_t)a_cp.size() == P.Nx + 1 && a_cp.back() == nzA && (int64_t)a_ri.size() == nzA, "A pattern by value");
+  EXPECT((int64_t)b_rp.size() == P.Nx + 1 && b_rp.back() == nzB && (int64_t)b_ci.size() == nzB, "B2 row pattern by value");
+  for (int32_t r : a_ri) EXPECT(r >= 0 && r < P.Nx, "A row in range");
+  for (int32_t j : b_ci) EXPECT(j >= 0 && j < P.Nu, "B2 column in range");
+  EXPECT((int64_t)kx.size() == T && (int64_t)ku.size() == T && kmax <= d + 1, "level schedule");
+  // last masks with stored-false entries: they still count
+  Csc& lx = M.x[T - 1]; Csc& lu = M.u[T - 1];
+  lx.b.assign(lx.ri.size(), 1); lu.b.assign(lu.ri.size(), 1);
+  for (size_t k = 0; k < lx.b.size(); k += 3) lx.b[k] = 0;
+  for (size_t k = 0; k < lu.b.size(); k += 4) lu.b[k] = 0;
+  sls_csc_bool bx = lx.boolean(), bu = lu.boolean();
+  EXPECT(sls::index_set_inputs(&dims, &A, &bx, &bu, a_cp, a_ri, sx_cp, sx_ri, su_cp, su_ri, msg) == 0, "index_set_inputs");
+  EXPECT(sx_ri.size() == lx.ri.size() && su_ri.size() == lu.ri.size() && (int64_t)a_ri.size() == nzA, "index-set inputs: masks structural, A by value");
+  EXPECT((int64_t)sx_cp.size() == P.Nx + 1 && (int64_t)su_cp.size() == P.Nx + 1, "index-set input pointers");
+  std::printf("%s base=%d: largest mask column %lld: done\n", name, base, (long long)biggest);
+}
+
 }  // namespace
 
 int main() {
@@ -356,6 +464,14 @@ int main() {
     exercise(grid(9, base), 2, 6, base, false, "grid9");
     exercise(random_plant(70, base, 11u + base), 2, 7, base, false, "random70");
     exercise_fir_edges(base);
+    // the device passes' edge plants (tests/symbolic_cases.py): a level of 1025 states, states 4000 apart in one level, every
+    // level full, stored zeros with an empty level, no inputs at all, 62 levels
+    exercise_device_inputs(hub_plant(1100, 1024, base), 1, 3, 1.5, base, 1025, "hub1025");
+    exercise_device_inputs(far_plant(base), 2, 4, 1.5, base, -1, "far4200");
+    exercise_device_inputs(dense_plant(40, base), 2, 3, 1.5, base, 40, "dense40");
+    exercise_device_inputs(holes_plant(base, false), 2, 4, 1.5, base, -1, "holes");
+    exercise_device_inputs(holes_plant(base, true), 2, 4, 0.5, base, -1, "holes_no_inputs");
+    exercise_device_inputs(hub_plant(70, 20, base), 60, 24, 3.0, base, 21, "hub_deep60");
   }
   // worker pool: a pass large enough for several threads (Nx/256 ≥ 2)
   exercise(chain(600, 0, false), 6, 12, 0, false, "chain600");
