@@ -304,6 +304,35 @@ int  sls_plan_update_result(sls_plan* plan, int64_t* n_rejected);
  * pass it to sls_plan_refine — reads it here instead of keeping its own copies.  Like every call on a context, the update
  * entry points are for one thread at a time per context (they share the context's pinned staging buffer).                    */
 int  sls_plan_fetch_plant(sls_plan* plan, double* A_nzval, double* B2_nzval);
+/* ---- re-solve only some columns of a resident plan ---------------------------------------------------------------------------
+ * Subproblem q reads the plant only through A[s_x(q), s_x(q)] and B2[s_x(q), s_u(q)], so a change of A[i,j] can move it only if
+ * i and j lie in s_x(q), and a change of B2[i,k] only if i lies in s_x(q) and k in s_u(q); every other column would be solved
+ * again to the same bits.  The index sets are plan-time (the zero rule above keeps them), so the rule is exact for the plan as
+ * it runs.
+ * sls_plan_execute_columns runs the listed subproblems only: `subs` [nsubs] are positions in col_status order, 0-based, strictly
+ *   ascending, in HOST memory (SLS_EINVAL otherwise).  Same kernels, LDS plans, workspaces and launch parameters as
+ *   sls_plan_execute, each launch over the listed columns it owns (none: skipped).  Entries of d_values, and status / residual /
+ *   iteration words, of other subproblems are not written.  A coupled group (non-diagonal B1[c_j,c_j]) is solved as a whole when
+ *   any of its columns is listed.  *n_solved (nullable): subproblems solved.  nsubs = 0 returns 0 and enqueues nothing.
+ * sls_plan_track_changes(plan, 1): every later sls_plan_update_plant (either path) also marks, in one "dirty" byte per
+ *   subproblem on the device, the subproblems touched by the entries it actually changes: accepted, and the bits of the new
+ *   value differ from the plan's current value (0.0 → −0.0 counts; a refused entry does not).  Marks accumulate over updates;
+ *   turning tracking on clears them (and makes the feature's device buffers, which are not part of workspace_bytes).
+ *   sls_plan_track_changes(plan, 0): later updates mark nothing; existing marks stay.
+ * sls_plan_execute_dirty runs sls_plan_execute_columns on the marked set, then clears the marks on the same stream.  0 solved and
+ *   nothing enqueued when tracking was never on.
+ * THE HOST WAIT: grids and skipped launches are decided on the host, so sls_plan_execute_columns and sls_plan_execute_dirty build
+ *   the launch lists on `hip_stream`, then wait for that stream — for everything enqueued on it before the call — and copy two
+ *   int32 per launch to the host before they enqueue the solve.  The solve itself is asynchronous like sls_plan_execute.
+ * A full sls_plan_execute neither reads nor clears the marks.  SLS_EUNSUPPORTED while a refinement is attached (sls_plan_refine).
+ * sls_plan_fetch_dirty copies the marks to dirty[n_subproblems] (HOST); it waits for the plan's last execute and last update,
+ *   like sls_plan_update_result.  sls_plan_clear_dirty clears them on `hip_stream`.                                            */
+int  sls_plan_execute_columns(sls_plan* plan, void* hip_stream, double* d_values, int packed, const int64_t* subs, int64_t nsubs,
+                              int64_t* n_solved);
+int  sls_plan_track_changes(sls_plan* plan, int on);
+int  sls_plan_execute_dirty(sls_plan* plan, void* hip_stream, double* d_values, int packed, int64_t* n_solved);
+int  sls_plan_fetch_dirty(sls_plan* plan, uint8_t* dirty);
+int  sls_plan_clear_dirty(sls_plan* plan, void* hip_stream);
 /* ---- objective value of every column, evaluated on the device from the written Φ ------------------------------------------
  * The number the reference's JuMP model calls objective_value(problem) (src/synthesis.jl:52): per subproblem the cost it
  * minimised, at the point that was written — Σₜ‖[C̃1 D̃12]Φ̃[t]B̃1 + D̃11‖²_F for the 𝓗₂ objective (the ridge term of

@@ -75,6 +75,14 @@ int sls_debug_operator_update_host(const sls_dims* dims, const sls_csc_f64* A, c
                                    const double* B2_nzval, double* A_val, double* At_val, double* B_val, double* Bt_val,
                                    int32_t* row_pos, uint8_t* zero);
 
+/* Host twin of the marks sls_plan_track_changes keeps (csrc/sls_symbolic.cpp: mark_affected_host): the host symbolic pass over
+ * all groups, then dirty[n_subproblems] in col_status order — 1 where a flagged entry can move the subproblem (A[i,j] with i and j
+ * in its s_x; B2[i,k] with i in s_x and k in s_u), 0 elsewhere.  changed_A[nnz(A)] / changed_B2[nnz(B2)]: one flag per CSC
+ * position, either NULL = none.  Needs no device. */
+int sls_debug_affected_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su, int64_t ngroups,
+                            const int64_t* group_ptr, const int64_t* group_cols, const uint8_t* changed_A, const uint8_t* changed_B2,
+                            uint8_t* dirty);
+
 #ifdef __cplusplus
 }
 #endif

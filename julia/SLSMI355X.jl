@@ -11,7 +11,7 @@
 module SLSMI355X
 
 using SparseArrays
-export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!
+export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, track_changes!, execute_dirty!
 
 const LIB = get(ENV, "SLS_MI355X_LIB", "libsls_mi355x.so")
 
@@ -112,6 +112,32 @@ function update_plant!(plan::Ptr{Cvoid}, A, B2; stream::Ptr{Cvoid}=C_NULL, wait:
     wait || return 0
     n = Ref{Int64}(0)
     rc = ccall((:sls_plan_update_result, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), plan, n)
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    return n[]
+end
+
+"""
+    track_changes!(plan, on=true)
+
+`sls_plan_track_changes`: with tracking on, every later `update_plant!` also marks the subproblems touched by the entries it
+actually changed; turning it on clears the marks.
+"""
+function track_changes!(plan::Ptr{Cvoid}, on::Bool=true)
+    rc = ccall((:sls_plan_track_changes, LIB), Cint, (Ptr{Cvoid}, Cint), plan, on ? 1 : 0)
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    return nothing
+end
+
+"""
+    n_solved = execute_dirty!(plan, d_values; packed=false, stream=C_NULL)
+
+`sls_plan_execute_dirty`: re-solve only the marked subproblems into the device array `d_values`, then clear the marks on
+`stream`.  Waits for `stream` once before the solve is enqueued; the solve itself is asynchronous like `sls_plan_execute`.
+"""
+function execute_dirty!(plan::Ptr{Cvoid}, d_values::Ptr{Cvoid}; packed::Bool=false, stream::Ptr{Cvoid}=C_NULL)
+    n = Ref{Int64}(0)
+    rc = ccall((:sls_plan_execute_dirty, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{Int64}), plan, stream, d_values,
+               packed ? 1 : 0, n)
     rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
     return n[]
 end

@@ -88,6 +88,7 @@ EXPORTS = [
     "sls_closed_loop_entries", "sls_closed_loop_destroy",
     "sls_plan_objective", "sls_plan_fetch_objective", "sls_ctx_want_objective", "sls_ctx_last_objective",
     "sls_plan_update_plant", "sls_plan_update_result", "sls_plan_fetch_plant",
+    "sls_plan_execute_columns", "sls_plan_track_changes", "sls_plan_execute_dirty", "sls_plan_fetch_dirty", "sls_plan_clear_dirty",
 ]
 
 _lib = None
@@ -183,12 +184,20 @@ def load_library(path: str | None = None):
     lib.sls_plan_update_plant.restype = C.c_int; lib.sls_plan_update_plant.argtypes = [vp, vp, vp, vp, C.c_int]
     lib.sls_plan_update_result.restype = C.c_int; lib.sls_plan_update_result.argtypes = [vp, i64p]
     lib.sls_plan_fetch_plant.restype = C.c_int; lib.sls_plan_fetch_plant.argtypes = [vp, dp, dp]
+    u8p = C.POINTER(C.c_uint8)
+    lib.sls_plan_execute_columns.restype = C.c_int; lib.sls_plan_execute_columns.argtypes = [vp, vp, vp, C.c_int, i64p, C.c_int64, i64p]
+    lib.sls_plan_track_changes.restype = C.c_int; lib.sls_plan_track_changes.argtypes = [vp, C.c_int]
+    lib.sls_plan_execute_dirty.restype = C.c_int; lib.sls_plan_execute_dirty.argtypes = [vp, vp, vp, C.c_int, i64p]
+    lib.sls_plan_fetch_dirty.restype = C.c_int; lib.sls_plan_fetch_dirty.argtypes = [vp, u8p]
+    lib.sls_plan_clear_dirty.restype = C.c_int; lib.sls_plan_clear_dirty.argtypes = [vp, vp]
     # diagnostics outside the public header
     lib.sls_debug_objective_host.restype = C.c_int
     lib.sls_debug_objective_host.argtypes = common + [dp, dp, dpp, dpp, dp, dp, i64p, dp]
     lib.sls_debug_operator_update_host.restype = C.c_int
     lib.sls_debug_operator_update_host.argtypes = [C.POINTER(sls_dims), C.POINTER(sls_csc_f64), C.POINTER(sls_csc_f64), dp, dp, dp, dp, dp, dp,
                                                    i32p, C.POINTER(C.c_uint8)]
+    lib.sls_debug_affected_host.restype = C.c_int
+    lib.sls_debug_affected_host.argtypes = common + [u8p, u8p, u8p]
     lib.sls_debug_tile_invert.restype = C.c_int; lib.sls_debug_tile_invert.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_int]
     lib.sls_plan_debug_read_workspace.restype = C.c_int; lib.sls_plan_debug_read_workspace.argtypes = [vp, C.c_int64, C.c_int64, dp]
     lib.sls_plan_debug_twisted4_tables.restype = C.c_int

@@ -148,6 +148,22 @@ struct sls_plan {
   unsigned long long* d_upd_rejected = nullptr;
   hipEvent_t ev_upd = nullptr;
   bool upd_recorded = false;
+  // partial re-solve (sls_plan_execute_columns / _dirty, sls_plan_track_changes): one device allocation made by
+  // the first of those calls (partial_ensure) — a plan that never uses them holds none of it and reports the same
+  // workspace_bytes.  Layouts: sls_device.h (ChangedEntriesParams, MarkAffectedParams, CompactOrderParams).
+  struct Partial {
+    bool ready = false, track = false;
+    uint8_t* dirty = nullptr;         // [nsub] marks of the tracked updates
+    uint8_t* marks = nullptr;         // [nsub] the list of an sls_plan_execute_columns call
+    uint8_t* chg = nullptr;           // [nnzA + nnzB]
+    uint8_t* row_chg = nullptr;       // [Nx]
+    int32_t* sel_order = nullptr;     // [order entries]
+    int32_t* sel_pos = nullptr;
+    int32_t* count = nullptr;         // [2 · launches]
+    const int32_t* launch_tab = nullptr;   // [launches][3]
+    std::vector<int32_t> h_count;
+    std::vector<uint8_t> h_marks;
+  } part;
 };
 
 namespace {
@@ -1336,6 +1352,61 @@ int sls_plan_value_offsets(const sls_plan* plan, int64_t* off_x, int64_t* off_u)
   return 0;
 }
 
+// A run over a subset of the columns (sls_plan_execute_columns): the compacted order of compact_order_kernel, laid out like the
+// plan's own order, with the host's copy of the per-launch counts.
+struct SelectedRun {
+  const int32_t* order;     // device
+  const int32_t* pos;       // device: position of each kept item in its launch (the four-wave records are indexed by it)
+  const int32_t* count;     // host: work items kept per launch
+};
+
+// The launches of one execute on the caller's stream `st`: launch 0 there, the others on plan-owned streams that fork from /
+// join back into it (event edges only; nothing blocks the host).  sel = NULL: every launch in full.  Otherwise the same kernels,
+// LDS plans, workspaces and launch parameters over the kept items of each launch; a launch that keeps none is skipped.
+static int enqueue_launches(sls_plan* plan, const KernelParams& kp, hipStream_t st, const SelectedRun* sel) {
+  const bool multi = plan->launches.size() > 1;
+  if (plan->has_tile) HIPCHK(plan->ctx, hipMemsetAsync(plan->d_counters, 0, plan->launches.size() * sizeof(int32_t), st));
+  if (multi) HIPCHK(plan->ctx, hipEventRecord(plan->ev_fork, st));
+  for (size_t li = 0; li < plan->launches.size(); ++li) {
+    const auto& L = plan->launches[li];
+    const int nsub = sel ? sel->count[li] : L.nsub;
+    if (sel && nsub <= 0) continue;
+    const int grid = sel ? std::min(L.grid, nsub) : L.grid;
+    hipStream_t ls = (li == 0) ? st : L.stream;
+    if (li > 0) HIPCHK(plan->ctx, hipStreamWaitEvent(ls, plan->ev_fork, 0));
+    KernelParams q = kp;
+    q.order_off = L.order_off; q.nsub = nsub; q.fac_stride = L.fac_stride;
+    if (sel) q.order = sel->order;
+    q.fac_ws = kp.fac_ws + L.fac_off;
+    hipError_t e;
+    const bool tile = L.kind == LaunchKind::Tile;
+    if (tile || L.kind == LaunchKind::Workgroup) {
+      q.nmax = L.nmax; q.mmax = L.mmax; q.nnzA_cap = L.nnzA_cap; q.nnzB_cap = L.nnzB_cap;
+      q.vec_in_lds = L.vec_in_lds; q.vec_stride = L.vec_stride; q.vec_ws = kp.vec_ws ? kp.vec_ws + L.vec_off : nullptr;
+      q.tile_oth_rows = L.oth_rows;
+      q.work_counter = tile ? plan->d_counters + li : nullptr;
+      q.big_ws = L.big ? plan->d_big + L.big_off : nullptr; q.big_stride = L.big_stride;
+      e = tile ? launch_tile(q, grid, L.lds, ls, L.mlds, L.two_per_cu, L.gw, L.big) : launch_general(q, grid, L.lds, ls, L.wide);
+    } else {
+      q.w_mcap = L.mcap; q.w_nm_max = L.nm_max; q.w_pl_off = L.pl_off;
+      q.work_counter = (kp.objective == 1 && L.kind == LaunchKind::OneWave) ? plan->d_counters + li : nullptr;
+      q.vec_in_lds = L.vec_in_lds; q.vec_stride = L.vec_stride; q.vec_ws = kp.vec_ws ? kp.vec_ws + L.vec_off : nullptr;
+      if (L.four) {
+        q.t4_rec = plan->d_t4 + L.t4_off * plan->t4_stride; q.t4_stride = plan->t4_stride;
+        q.t4_pos = sel ? sel->pos + L.order_off : nullptr;
+      }
+      e = (L.kind == LaunchKind::Twisted) ? (L.four ? launch_twisted4(L.cls, q, grid, L.lds, ls) : launch_twisted(L.cls, q, grid, L.lds, ls))
+                        : launch_wave(L.cls, q, grid, L.lds, ls);
+    }
+    if (e != hipSuccess) return hipfail(plan->ctx, e, "kernel launch");
+    if (li > 0) {
+      HIPCHK(plan->ctx, hipEventRecord(L.done, ls));
+      HIPCHK(plan->ctx, hipStreamWaitEvent(st, L.done, 0));
+    }
+  }
+  return 0;
+}
+
 int sls_plan_execute(sls_plan* plan, void* hip_stream, double* d_values, int packed) {
   if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
   if (!d_values && plan->info.n_packed > 0) return fail(plan->ctx, SLS_EINVAL, "null device value pointer");
@@ -1354,41 +1425,8 @@ int sls_plan_execute(sls_plan* plan, void* hip_stream, double* d_values, int pac
     HIPCHK(plan->ctx, hipEventCreate(&plan->ev_stop[ev]));
   }
   if (timed) HIPCHK(plan->ctx, hipEventRecord(plan->ev_start[ev], st));
-  // size classes run concurrently: launch 0 on the caller's stream, the others on plan-owned streams that fork
-  // from / join back into it (event edges only; nothing blocks the host)
-  const bool multi = plan->launches.size() > 1;
-  if (plan->has_tile) HIPCHK(plan->ctx, hipMemsetAsync(plan->d_counters, 0, plan->launches.size() * sizeof(int32_t), st));
-  if (multi) HIPCHK(plan->ctx, hipEventRecord(plan->ev_fork, st));
-  for (size_t li = 0; li < plan->launches.size(); ++li) {
-    const auto& L = plan->launches[li];
-    hipStream_t ls = (li == 0) ? st : L.stream;
-    if (li > 0) HIPCHK(plan->ctx, hipStreamWaitEvent(ls, plan->ev_fork, 0));
-    KernelParams q = kp;
-    q.order_off = L.order_off; q.nsub = L.nsub; q.fac_stride = L.fac_stride;
-    q.fac_ws = kp.fac_ws + L.fac_off;
-    hipError_t e;
-    const bool tile = L.kind == LaunchKind::Tile;
-    if (tile || L.kind == LaunchKind::Workgroup) {
-      q.nmax = L.nmax; q.mmax = L.mmax; q.nnzA_cap = L.nnzA_cap; q.nnzB_cap = L.nnzB_cap;
-      q.vec_in_lds = L.vec_in_lds; q.vec_stride = L.vec_stride; q.vec_ws = kp.vec_ws ? kp.vec_ws + L.vec_off : nullptr;
-      q.tile_oth_rows = L.oth_rows;
-      q.work_counter = tile ? plan->d_counters + li : nullptr;
-      q.big_ws = L.big ? plan->d_big + L.big_off : nullptr; q.big_stride = L.big_stride;
-      e = tile ? launch_tile(q, L.grid, L.lds, ls, L.mlds, L.two_per_cu, L.gw, L.big) : launch_general(q, L.grid, L.lds, ls, L.wide);
-    } else {
-      q.w_mcap = L.mcap; q.w_nm_max = L.nm_max; q.w_pl_off = L.pl_off;
-      q.work_counter = (kp.objective == 1 && L.kind == LaunchKind::OneWave) ? plan->d_counters + li : nullptr;
-      q.vec_in_lds = L.vec_in_lds; q.vec_stride = L.vec_stride; q.vec_ws = kp.vec_ws ? kp.vec_ws + L.vec_off : nullptr;
-      if (L.four) { q.t4_rec = plan->d_t4 + L.t4_off * plan->t4_stride; q.t4_stride = plan->t4_stride; }
-      e = (L.kind == LaunchKind::Twisted) ? (L.four ? launch_twisted4(L.cls, q, L.grid, L.lds, ls) : launch_twisted(L.cls, q, L.grid, L.lds, ls))
-                        : launch_wave(L.cls, q, L.grid, L.lds, ls);
-    }
-    if (e != hipSuccess) return hipfail(plan->ctx, e, "kernel launch");
-    if (li > 0) {
-      HIPCHK(plan->ctx, hipEventRecord(L.done, ls));
-      HIPCHK(plan->ctx, hipStreamWaitEvent(st, L.done, 0));
-    }
-  }
+  // size classes run concurrently (enqueue_launches)
+  if (int rc = enqueue_launches(plan, kp, st, nullptr)) return rc;
   if (plan->refine) {                      // attached by sls_plan_refine: after the joins above, same stream, same array, same layout
     int rc = sls_plan_execute(plan->refine, hip_stream, d_values, packed);
     if (rc) return rc;
@@ -1406,6 +1444,141 @@ int sls_plan_execute(sls_plan* plan, void* hip_stream, double* d_values, int pac
     HIPCHK(plan->ctx, hipEventRecord(plan->ev_done, st));
     plan->last_done = plan->ev_done;
   }
+  return 0;
+}
+
+// ---- partial re-solve: sls_plan_execute_columns, sls_plan_track_changes, sls_plan_execute_dirty ----
+
+// The device buffers of the partial re-solve, made by the first call that needs them: one allocation, cleared, plus the table
+// of the launches' slices of `order`.  Not counted in workspace_bytes, which describes the plan as sls_h2_sf_plan left it.
+static int partial_ensure(sls_plan* plan) {
+  sls_plan::Partial& pt = plan->part;
+  if (pt.ready) return 0;
+  const size_t ns = (size_t)std::max<int64_t>(plan->kp.nsub, 1), nl = std::max<size_t>(plan->launches.size(), 1);
+  const size_t nop = (size_t)std::max<int64_t>(plan->opmap.nnzA + plan->opmap.nnzB, 1), nx = (size_t)std::max<int64_t>(plan->sym.Nx, 1);
+  size_t no = 1;
+  std::vector<int32_t> tab(3 * nl, 0);
+  for (size_t li = 0; li < plan->launches.size(); ++li) {
+    const auto& L = plan->launches[li];
+    no = std::max(no, (size_t)L.order_off + (size_t)L.nsub);
+    tab[3 * li] = L.order_off; tab[3 * li + 1] = L.nsub; tab[3 * li + 2] = (L.kind == LaunchKind::Tile && L.gw) ? 1 : 0;
+  }
+  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t o_dirty = 0, o_marks = o_dirty + al(ns), o_chg = o_marks + al(ns), o_row = o_chg + al(nop), o_sel = o_row + al(nx),
+               o_pos = o_sel + al(4 * no), o_cnt = o_pos + al(4 * no), o_tab = o_cnt + al(8 * nl), total = o_tab + al(12 * nl);
+  unsigned char* base = nullptr;
+  HIPCHK(plan->ctx, hipMalloc(reinterpret_cast<void**>(&base), total));
+  plan->dev_allocs.push_back(base);
+  HIPCHK(plan->ctx, hipMemset(base, 0, total));
+  HIPCHK(plan->ctx, hipMemcpy(base + o_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  pt.dirty = base + o_dirty; pt.marks = base + o_marks; pt.chg = base + o_chg; pt.row_chg = base + o_row;
+  pt.sel_order = reinterpret_cast<int32_t*>(base + o_sel); pt.sel_pos = reinterpret_cast<int32_t*>(base + o_pos);
+  pt.count = reinterpret_cast<int32_t*>(base + o_cnt); pt.launch_tab = reinterpret_cast<const int32_t*>(base + o_tab);
+  pt.h_count.assign(2 * nl, 0);
+  pt.ready = true;
+  return 0;
+}
+
+// The selected run over the subproblems marked in `d_marks` (by out_index).  compact_order_kernel builds the launch lists on
+// `st`; the host then WAITS for `st` — the one host wait of the partial re-solve — to read the per-launch counts (two int32 per
+// launch), because grids and skipped launches are decided on the host.  No timing events: sls_plan_kernel_time_ms keeps
+// averaging full executes.
+static int execute_marked(sls_plan* plan, hipStream_t st, double* d_values, int packed, const uint8_t* d_marks, int64_t* n_solved) {
+  sls_plan::Partial& pt = plan->part;
+  const size_t nl = plan->launches.size();
+  KernelParams kp = plan->kp;
+  kp.out = d_values;
+  kp.dest_pool = packed ? plan->d_pdest : plan->d_dest;
+  CompactOrderParams cp{};
+  cp.subs = kp.subs; cp.order = kp.order; cp.launch_tab = pt.launch_tab; cp.marks = d_marks;
+  cp.sel_order = pt.sel_order; cp.sel_pos = pt.sel_pos; cp.count = pt.count; cp.nlaunch = (int32_t)nl;
+  hipError_t e = launch_compact_order(cp, st);
+  if (e != hipSuccess) return hipfail(plan->ctx, e, "launch compact_order_kernel");
+  if (nl) HIPCHK(plan->ctx, hipMemcpyAsync(pt.h_count.data(), pt.count, 2 * nl * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(plan->ctx, hipStreamSynchronize(st));
+  int64_t items = 0, cols = 0;
+  for (size_t li = 0; li < nl; ++li) { items += pt.h_count[li]; cols += pt.h_count[nl + li]; }
+  if (n_solved) *n_solved = cols;
+  if (items == 0) return 0;
+  SelectedRun sel{pt.sel_order, pt.sel_pos, pt.h_count.data()};
+  if (int rc = enqueue_launches(plan, kp, st, &sel)) return rc;
+  return 0;
+}
+
+// the end of a partial run on the caller's stream: what status reads and downloads wait for
+static int record_partial_done(sls_plan* plan, hipStream_t st) {
+  if (!plan->ev_done) HIPCHK(plan->ctx, hipEventCreateWithFlags(&plan->ev_done, hipEventDisableTiming));
+  HIPCHK(plan->ctx, hipEventRecord(plan->ev_done, st));
+  plan->last_done = plan->ev_done;
+  return 0;
+}
+
+static int partial_args(sls_plan* plan, double* d_values, int packed, const char* who) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  if (plan->refine) return fail(plan->ctx, SLS_EUNSUPPORTED, std::string(who) + ": a refinement is attached to this plan (it re-solves columns of its own after every full execute)");
+  if (!d_values && plan->info.n_packed > 0) return fail(plan->ctx, SLS_EINVAL, "null device value pointer");
+  if (packed && !plan->d_pdest) return fail(plan->ctx, SLS_EINVAL, "this plan was built without the packed layout");
+  return 0;
+}
+
+int sls_plan_execute_columns(sls_plan* plan, void* hip_stream, double* d_values, int packed, const int64_t* subs, int64_t nsubs,
+                             int64_t* n_solved) {
+  if (n_solved) *n_solved = 0;
+  if (int rc = partial_args(plan, d_values, packed, "sls_plan_execute_columns")) return rc;
+  if (nsubs < 0 || (nsubs > 0 && !subs)) return fail(plan->ctx, SLS_EINVAL, "sls_plan_execute_columns: bad subproblem list");
+  const int64_t ns = plan->kp.nsub;
+  for (int64_t i = 0; i < nsubs; ++i) {
+    if (subs[i] < 0 || subs[i] >= ns)
+      return fail(plan->ctx, SLS_EINVAL, "sls_plan_execute_columns: subproblem " + std::to_string(subs[i]) + " is outside 0 .. " + std::to_string(ns - 1));
+    if (i > 0 && subs[i] <= subs[i - 1])
+      return fail(plan->ctx, SLS_EINVAL, "sls_plan_execute_columns: the subproblem list must be strictly ascending (position " + std::to_string(i) + ")");
+  }
+  if (nsubs == 0) return 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  if (int rc = partial_ensure(plan)) return rc;
+  sls_plan::Partial& pt = plan->part;
+  pt.h_marks.assign((size_t)ns, 0);
+  for (int64_t i = 0; i < nsubs; ++i) pt.h_marks[(size_t)subs[i]] = 1;
+  // h_marks belongs to the plan and execute_marked waits for `st` before it returns: the copy has read it by then
+  HIPCHK(plan->ctx, hipMemcpyAsync(pt.marks, pt.h_marks.data(), (size_t)ns, hipMemcpyHostToDevice, st));
+  if (int rc = execute_marked(plan, st, d_values, packed, pt.marks, n_solved)) return rc;
+  return record_partial_done(plan, st);
+}
+
+int sls_plan_track_changes(sls_plan* plan, int on) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  sls_plan::Partial& pt = plan->part;
+  if (!on) { pt.track = false; return 0; }
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  if (int rc = partial_ensure(plan)) return rc;
+  // the marks are cleared behind the last update and the last execute, on the plan's own stream, and waited for
+  hipStream_t ps = plan->stream;
+  if (plan->upd_recorded) HIPCHK(plan->ctx, hipStreamWaitEvent(ps, plan->ev_upd, 0));
+  if (plan->last_done) HIPCHK(plan->ctx, hipStreamWaitEvent(ps, plan->last_done, 0));
+  HIPCHK(plan->ctx, hipMemsetAsync(pt.dirty, 0, (size_t)std::max<int64_t>(plan->kp.nsub, 1), ps));
+  HIPCHK(plan->ctx, hipStreamSynchronize(ps));
+  pt.track = true;
+  return 0;
+}
+
+int sls_plan_execute_dirty(sls_plan* plan, void* hip_stream, double* d_values, int packed, int64_t* n_solved) {
+  if (n_solved) *n_solved = 0;
+  if (int rc = partial_args(plan, d_values, packed, "sls_plan_execute_dirty")) return rc;
+  sls_plan::Partial& pt = plan->part;
+  if (!pt.ready || plan->kp.nsub == 0) return 0;          // tracking was never on: no mark exists
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  if (int rc = execute_marked(plan, st, d_values, packed, pt.dirty, n_solved)) return rc;
+  HIPCHK(plan->ctx, hipMemsetAsync(pt.dirty, 0, (size_t)plan->kp.nsub, st));
+  return record_partial_done(plan, st);
+}
+
+int sls_plan_clear_dirty(sls_plan* plan, void* hip_stream) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  if (!plan->part.ready || plan->kp.nsub == 0) return 0;
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  HIPCHK(plan->ctx, hipMemsetAsync(plan->part.dirty, 0, (size_t)plan->kp.nsub, reinterpret_cast<hipStream_t>(hip_stream)));
   return 0;
 }
 
@@ -1452,6 +1625,21 @@ int sls_plan_update_plant(sls_plan* plan, void* hip_stream, const double* A_nzva
     }
     up.newA = A_nzval ? plan->d_upd_stage : nullptr;
     up.newB = B2_nzval ? plan->d_upd_stage + nA : nullptr;
+  }
+  if (plan->part.track) {
+    // before operator_update_kernel overwrites the old values: the entries this update changes, then the subproblems they touch
+    sls_plan::Partial& pt = plan->part;
+    ChangedEntriesParams cp{};
+    cp.up = up; cp.rowA = kp.At_colidx; cp.rowB = kp.Bt_colidx; cp.chg = pt.chg; cp.row_chg = pt.row_chg;
+    HIPCHK(ctx, hipMemsetAsync(pt.row_chg, 0, (size_t)std::max<int64_t>(plan->sym.Nx, 1), st));
+    hipError_t et = launch_changed_entries(cp, st);
+    if (et != hipSuccess) return hipfail(ctx, et, "launch changed_entries_kernel");
+    MarkAffectedParams mp{};
+    mp.subs = kp.subs; mp.nsub = kp.nsub; mp.idx_pool = kp.idx_pool;
+    mp.A_rowptr = kp.A_rowptr; mp.A_colidx = kp.A_colidx; mp.B_rowptr = kp.B_rowptr; mp.B_colidx = kp.B_colidx;
+    mp.nnzA = M.nnzA; mp.chg = pt.chg; mp.row_chg = pt.row_chg; mp.dirty = pt.dirty;
+    et = launch_mark_affected(mp, st);
+    if (et != hipSuccess) return hipfail(ctx, et, "launch mark_affected_kernel");
   }
   HIPCHK(ctx, hipMemsetAsync(plan->d_upd_rejected, 0, sizeof(unsigned long long), st));
   hipError_t e = launch_operator_update(up, st);
@@ -1505,6 +1693,16 @@ int sls_plan_fetch_plant(sls_plan* plan, double* A_nzval, double* B2_nzval) {
   if (B2_nzval)
     if (int rc = read_behind_update(plan, B2_nzval, plan->kp.Bt_val, (size_t)plan->opmap.nnzB * sizeof(double))) return rc;
   return 0;
+}
+
+int sls_plan_fetch_dirty(sls_plan* plan, uint8_t* dirty) {
+  if (!plan || (!dirty && plan->kp.nsub > 0)) return fail(nullptr, SLS_EINVAL, "null argument");
+  const size_t n = (size_t)plan->kp.nsub;
+  if (n == 0) return 0;
+  if (!plan->part.ready) { std::fill(dirty, dirty + n, (uint8_t)0); return 0; }   // tracking was never on
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  if (int rc = wait_plan_done(plan)) return rc;            // an sls_plan_execute_dirty clears the marks before its end
+  return read_behind_update(plan, dirty, plan->part.dirty, n);
 }
 
 int sls_plan_execute_batch(sls_plan* const* plans, int nplans, void* hip_stream, double* const* d_values, int packed) {
@@ -1713,6 +1911,30 @@ int sls_debug_operator_update_host(const sls_dims* dims, const sls_csc_f64* A, c
   if (Bt_val) std::copy(S.Bt_csr.val.begin(), S.Bt_csr.val.end(), Bt_val);
   if (row_pos) std::copy(M.row_pos.begin(), M.row_pos.end(), row_pos);
   if (zero) std::copy(M.zero.begin(), M.zero.end(), zero);
+  if (rc) return fail(nullptr, rc, msg);
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): the host twin of the marks sls_plan_track_changes keeps — the host symbolic pass
+   over all groups, then mark_affected_host with the caller's changed flags.  Needs no device. */
+int sls_debug_affected_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su, int64_t ngroups,
+                            const int64_t* group_ptr, const int64_t* group_cols, const uint8_t* changed_A, const uint8_t* changed_B2,
+                            uint8_t* dirty) {
+  if (!dirty) return fail(nullptr, SLS_EINVAL, "null argument");
+  Inputs in{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
+  std::string msg;
+  int rc = validate_inputs(in, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  std::vector<int64_t> gptr, gcols;
+  normalise_groups(in, gptr, gcols);
+  Symbolic S;
+  S.want_packed = false; S.compact = false;
+  rc = build_symbolic(in, 0, (int64_t)gptr.size() - 1, S, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  OperatorValueMap M;
+  build_operator_value_map(S, M);
+  std::fill(dirty, dirty + S.subs.size(), (uint8_t)0);
+  rc = mark_affected_host(S, M, changed_A, changed_B2, dirty, msg);
   if (rc) return fail(nullptr, rc, msg);
   return 0;
 }

@@ -81,6 +81,9 @@ struct KernelParams {
   // record s belongs to order[order_off + s]
   const unsigned char* t4_rec;
   int64_t t4_stride;     // bytes per record (twisted4_record_bytes)
+  // a selected run (sls_plan_execute_columns) draws from a compacted order: t4_pos[s] is the launch position whose record column
+  // s of the compacted list uses.  NULL = the full execute, record s itself
+  const int32_t* t4_pos;
 };
 
 // LDS bytes the general kernel needs for given caps (must match the carve in the kernel).
@@ -313,6 +316,42 @@ struct OperatorUpdateParams {
   double* A_val;  double* At_val;
   double* B_val;  double* Bt_val;
   unsigned long long* rejected;   // entries refused (not finite, or non-zero on a plan-time zero): counted, not written
+};
+
+// ---- partial re-solve (sls_partial.hip) ----
+// changed_entries_kernel: which entries an update is about to change.  Entry numbering, row_pos and zero as in
+// OperatorUpdateParams (`up`); row_of[k] is the plant row of CSC position k (At_colidx, then Bt_colidx).  chg is indexed like
+// A_val / B_val (row order; B2's entries behind A's nnzA), row_chg by plant row.  Every entry's flag is rewritten by every call;
+// row_chg is cleared by the host first.
+struct ChangedEntriesParams {
+  OperatorUpdateParams up;
+  const int32_t* rowA;      // At_colidx
+  const int32_t* rowB;      // Bt_colidx
+  uint8_t* chg;             // [nnzA + nnzB]
+  uint8_t* row_chg;         // [Nx]
+};
+
+// mark_affected_kernel: dirty[out_index] = 1 for every subproblem some changed entry can move
+struct MarkAffectedParams {
+  const SubDesc* subs;  int32_t nsub;
+  const int32_t* idx_pool;
+  const int32_t* A_rowptr;  const int32_t* A_colidx;
+  const int32_t* B_rowptr;  const int32_t* B_colidx;
+  int64_t nnzA;
+  const uint8_t* chg;  const uint8_t* row_chg;
+  uint8_t* dirty;           // [nsub], by out_index; only ever set
+};
+
+// compact_order_kernel: per launch, the work items of order[order_off .. order_off + nsub) whose mark is set, in their order
+struct CompactOrderParams {
+  const SubDesc* subs;
+  const int32_t* order;
+  const int32_t* launch_tab;   // [nlaunch][3]: order_off, nsub, 1 when a work item may be a coupled group (tile kernel, CG build)
+  const uint8_t* marks;        // by out_index
+  int32_t* sel_order;          // kept items of launch l at sel_order[order_off ..), same offsets as `order`
+  int32_t* sel_pos;            // … and the position s each had in the launch
+  int32_t* count;              // [2·nlaunch]: kept work items per launch, then the subproblems they stand for
+  int32_t nlaunch;
 };
 
 }  // namespace sls

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/sls_mi355x.h"
+#include "sls_device.h"
 
 struct sls_ctx {
   std::vector<int> devs;
@@ -45,6 +46,10 @@ int fail(sls_ctx* ctx, int code, const std::string& msg);
 int hipfail(sls_ctx* ctx, hipError_t e, const char* what);
 // a plan / loop object may outlive its context (host-language GC order): checked before touching it
 bool ctx_is_live(const sls_ctx* ctx);
+// sls_partial.hip: the entries an update changes, the subproblems they touch, the compacted launch lists of a selected run
+hipError_t launch_changed_entries(const ChangedEntriesParams& p, hipStream_t stream);
+hipError_t launch_mark_affected(const MarkAffectedParams& p, hipStream_t stream);
+hipError_t launch_compact_order(const CompactOrderParams& p, hipStream_t stream);
 }  // namespace sls
 
 #define HIPCHK(ctx, call)                                        \

@@ -193,6 +193,41 @@ int apply_operator_update(Symbolic& S, const OperatorValueMap& M, const double* 
   return 0;
 }
 
+int mark_affected_host(const Symbolic& S, const OperatorValueMap& M, const uint8_t* changed_A, const uint8_t* changed_B2, uint8_t* dirty,
+                       std::string& msg) {
+  if ((int64_t)S.At_csr.idx.size() != M.nnzA || (int64_t)S.A_csr.idx.size() != M.nnzA || (int64_t)S.Bt_csr.idx.size() != M.nnzB ||
+      (int64_t)S.B_csr.idx.size() != M.nnzB || (int64_t)M.row_pos.size() != M.nnzA + M.nnzB || (int64_t)S.A_csr.ptr.size() != S.Nx + 1 ||
+      (int64_t)S.B_csr.ptr.size() != S.Nx + 1) {
+    msg = "affected columns: the value map does not belong to this symbolic pass";
+    return SLS_EINVAL;
+  }
+  // the flags where changed_entries_kernel puts them: at the entry's row-order position, and a byte per plant row
+  std::vector<uint8_t> chg((size_t)(M.nnzA + M.nnzB), 0), row_chg((size_t)S.Nx, 0);
+  for (int64_t k = 0; k < M.nnzA + M.nnzB; ++k) {
+    const bool isA = k < M.nnzA;
+    const uint8_t* src = isA ? changed_A : changed_B2;
+    const int64_t j = isA ? k : k - M.nnzA;
+    if (!src || !src[j]) continue;
+    chg[(size_t)((isA ? 0 : M.nnzA) + M.row_pos[(size_t)k])] = 1;
+    row_chg[(size_t)(isA ? S.At_csr.idx : S.Bt_csr.idx)[(size_t)j]] = 1;
+  }
+  for (const SubDesc& sd : S.subs) {
+    const int32_t* sx = S.idx_pool.data() + sd.off_sx;
+    const int32_t* su = S.idx_pool.data() + sd.off_su;
+    bool hit = false;
+    for (int32_t ii = 0; ii < sd.n && !hit; ++ii) {
+      const int32_t r = sx[ii];
+      if (!row_chg[(size_t)r]) continue;
+      for (int32_t e = S.A_csr.ptr[(size_t)r]; e < S.A_csr.ptr[(size_t)r + 1] && !hit; ++e)
+        hit = chg[(size_t)e] && std::binary_search(sx, sx + sd.n, S.A_csr.idx[(size_t)e]);
+      for (int32_t e = S.B_csr.ptr[(size_t)r]; e < S.B_csr.ptr[(size_t)r + 1] && !hit; ++e)
+        hit = chg[(size_t)(M.nnzA + e)] && std::binary_search(su, su + sd.m, S.B_csr.idx[(size_t)e]);
+    }
+    if (hit) dirty[sd.out_index] = 1;
+  }
+  return 0;
+}
+
 int validate_inputs(const Inputs& in, std::string& msg) {
   if (!in.dims || !in.P) { msg = "null dims/plant"; return SLS_EINVAL; }
   const sls_dims& d = *in.dims;

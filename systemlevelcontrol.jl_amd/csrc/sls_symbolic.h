@@ -185,6 +185,12 @@ int check_operator_update(const OperatorValueMap& M, const double* A_nzval, cons
 // host twin of operator_update_kernel (sls_update.hip): checks first — on a refusal nothing is written — then writes the new
 // values into the four val arrays of S
 int apply_operator_update(Symbolic& S, const OperatorValueMap& M, const double* A_nzval, const double* B2_nzval, std::string& msg);
+// host twin of changed_entries_kernel's flag layout and mark_affected_kernel (sls_partial.hip): dirty[out_index] = 1 for every
+// subproblem of S that a flagged entry can move — A[i,j] with i, j ∈ s_x, B2[i,k] with i ∈ s_x and k ∈ s_u; other bytes of
+// `dirty` are left alone (marks accumulate).  changed_A / changed_B2: one flag per CSC position, either may be NULL.  S needs its
+// subs, idx_pool and operator arrays (build_symbolic).
+int mark_affected_host(const Symbolic& S, const OperatorValueMap& M, const uint8_t* changed_A, const uint8_t* changed_B2, uint8_t* dirty,
+                       std::string& msg);
 
 // predicted cost per group (Σ over its columns of (T+1)·ñx³)
 int group_costs(const Inputs& in, std::vector<double>& cost, std::string& msg);

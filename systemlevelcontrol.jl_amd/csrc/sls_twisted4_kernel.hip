@@ -998,7 +998,8 @@ __global__ __launch_bounds__(256, 1) void h2_column_twisted4_kernel(const Kernel
   double* fac = p.fac_ws + (int64_t)blockIdx.x * p.fac_stride;
   for (int s = blockIdx.x; s < p.nsub; s += gridDim.x) {
     const SubDesc sd = p.subs[p.order[p.order_off + s]];
-    twisted4_solve_column<NPL, RPL>(p, sd, p.t4_rec + (int64_t)s * p.t4_stride, fac, lds_raw);
+    const int rs = p.t4_pos ? p.t4_pos[s] : s;      // a selected run: the record of the column's place in the full launch
+    twisted4_solve_column<NPL, RPL>(p, sd, p.t4_rec + (int64_t)rs * p.t4_stride, fac, lds_raw);
   }
 }
 

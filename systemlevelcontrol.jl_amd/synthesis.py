@@ -213,6 +213,48 @@ class Plan:
         _capi.check(self._lib.sls_plan_update_result(self.handle, C.byref(n)), self.ctx.handle)
         return n.value
 
+    # -- partial re-solve: only the columns a local plant change touched (sls_mi355x.h) --
+    def execute_columns(self, d_values, subs, packed=False, stream=None):
+        """sls_plan_execute_columns: solve only the subproblems `subs` (positions in col_status order, 0-based, strictly
+        ascending; ValueError otherwise) into `d_values`; entries and status words of the others are not written.  A coupled
+        group is solved as a whole when any of its columns is listed.  Waits for `stream` once, before the solve is enqueued
+        (the launch lists are sized on the host).  Returns the number of subproblems solved."""
+        s = np.asarray(subs)
+        if s.ndim != 1 or (s.size and not np.issubdtype(s.dtype, np.integer)):
+            raise ValueError("execute_columns: subs must be a 1-D sequence of integers")
+        s = np.ascontiguousarray(s, dtype=np.int64)
+        n = self.info["n_subproblems"]
+        if s.size and (s[0] < 0 or s[-1] >= n or np.any(np.diff(s) <= 0)):
+            raise ValueError(f"execute_columns: subs must be strictly ascending inside 0 .. {n - 1}")
+        if s.size == 0:
+            return 0
+        k = C.c_int64()
+        _capi.check(self._lib.sls_plan_execute_columns(self.handle, stream, d_values, int(packed), s.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                       s.size, C.byref(k)), self.ctx.handle)
+        return k.value
+
+    def track_changes(self, on=True):
+        """sls_plan_track_changes: with tracking on, every later `update_plant` also marks the subproblems touched by the
+        entries it actually changed (accepted, and different in their bits); turning it on clears the marks."""
+        _capi.check(self._lib.sls_plan_track_changes(self.handle, int(bool(on))), self.ctx.handle)
+
+    def execute_dirty(self, d_values, packed=False, stream=None):
+        """sls_plan_execute_dirty: `execute_columns` on the marked subproblems, then the marks are cleared on the same stream.
+        Returns the number of subproblems solved (0, and nothing is enqueued, when tracking was never on)."""
+        k = C.c_int64()
+        _capi.check(self._lib.sls_plan_execute_dirty(self.handle, stream, d_values, int(packed), C.byref(k)), self.ctx.handle)
+        return k.value
+
+    def dirty(self):
+        """sls_plan_fetch_dirty: the marks as a uint8 array in col_status order (waits for the last update and execute)."""
+        n = self.info["n_subproblems"]
+        d = np.zeros(max(n, 1), dtype=np.uint8)
+        _capi.check(self._lib.sls_plan_fetch_dirty(self.handle, d.ctypes.data_as(C.POINTER(C.c_uint8))), self.ctx.handle)
+        return d[:n]
+
+    def clear_dirty(self, stream=None):
+        _capi.check(self._lib.sls_plan_clear_dirty(self.handle, stream), self.ctx.handle)
+
     def packed_dest(self):
         d = np.zeros(max(self.info["n_packed"], 1), dtype=np.int64)
         _capi.check(self._lib.sls_plan_packed_dest(self.handle, d.ctypes.data_as(C.POINTER(C.c_int64))))
