@@ -33,6 +33,22 @@ int sls_plan_debug_read_workspace(sls_plan* plan, int64_t offset, int64_t count,
 int sls_plan_debug_twisted4_tables(sls_plan* plan, int64_t* n_columns, int32_t* caps, int64_t* columns, int32_t* counts,
                                    int32_t* indices, double* values, uint64_t* bits);
 
+/* The plan-time static blocks of the same columns (the second thing twisted4_prepare_kernel builds), in col_status order.
+ * Block k of a column's block-tridiagonal Schur system has the static part
+ *     S_k = δ·I + Wx_k + B̃·Wu_{k−1}·B̃ᵀ + Ã·Wx_{k−1}·Ãᵀ                          (no factor P in it: fixed by the plan),
+ * slot k = 1 … T of the column's pool holds S_k, slot 0 the upward helper's first block: S_1 with δ·w/(δ + w) in the place of
+ * Wx_0.  *n_columns: the columns; *n_slots = T + 1; delta[n]: the column's shift δ; valid[n][T + 1]: 1 where the kernel
+ * filled the slot — exactly the slots a helper wave reads (the others are reused from a neighbour while the masks repeat, or
+ * lie on the other side of the meeting block) — unfilled slots hold zeros; offsets[n + 1]: column i's doubles are
+ * blocks[offsets[i] … offsets[i + 1]).  A column's pool is [T + 1][TQ][64] doubles, TQ = (offsets[i + 1] − offsets[i]) / (64·(T + 1))
+ * = TR·(TR + 1)/2 with TR = 3 tile rows in the classes <32,10>, <32,12> and 4 in <32,14>, <32,16>: lane 8·a + b of the
+ * helper's 8×8 lane grid owns the entries (a + 8·ri, b + 8·cj) of the block, 0 ≤ ri, cj < TR, and stores those with ri ≤ cj in
+ * the order q = (0,0), (0,1), … (0,TR−1), (1,1), … — the upper block triangle of the symmetric S_k, rows and columns beyond ñx
+ * included (δ on their diagonal).  Every output but n_columns may be NULL.  SLS_EINVAL when the plan has no four-wave launch
+ * or keeps no pool (SLS_T4_PRESTATIC=0 in lab mode, or a pool beyond the plan's byte budget). */
+int sls_plan_debug_twisted4_static(sls_plan* plan, int64_t* n_columns, int32_t* n_slots, int64_t* offsets, double* delta,
+                                   uint8_t* valid, double* blocks);
+
 /* Invert one dense SPD matrix (host, n×n row-major) with the tile kernel's blocked symmetric FP64-MFMA sweep — the unit
  * test of the MFMA operand / result lane maps (tests/test_gpu_tile.py).  mlds != 0: block resident in LDS. */
 int sls_debug_tile_invert(sls_ctx* ctx, int dev_slot, int n, const double* h_A, double* h_out, int mlds);

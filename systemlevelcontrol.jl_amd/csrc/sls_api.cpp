@@ -34,7 +34,7 @@ hipError_t launch_scatter(const double* src, const int64_t* idx, int64_t n, doub
 hipError_t launch_wave(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t launch_twisted(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream);
 hipError_t launch_twisted4(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream);
-hipError_t launch_twisted4_prepare(const KernelParams& p, unsigned char* pool, hipStream_t stream);
+hipError_t launch_twisted4_prepare(int cls, const KernelParams& p, unsigned char* pool, hipStream_t stream);
 hipError_t launch_tile(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool mlds, bool two_per_cu,
                        bool general_weights, bool big);
 hipError_t launch_expand_tables(const SubDesc* subs, int nsub, int T, const uint64_t* cmask, const int32_t* cbase, const int64_t* coff,
@@ -81,6 +81,7 @@ double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 constexpr int kEventPool = 64;
+constexpr int64_t kT4StaticBudget = 64ll << 20;   // bytes of plan-time static blocks a plan may hold (four-wave kernel)
 }  // namespace
 
 struct sls_plan {
@@ -108,11 +109,17 @@ struct sls_plan {
   // sls_plan_update_plant reruns the kernel behind every change of that copy.
   unsigned char* d_t4 = nullptr;
   int64_t t4_stride = 0, t4_records = 0;
+  // The static blocks S_k of the same columns (layout: sls_device.h, twisted4_static_doubles), written by the same kernel from
+  // the same copy.  NULL — the launches rebuild the blocks themselves — when the pool would exceed kT4StaticBudget or with
+  // SLS_T4_PRESTATIC=0 (lab mode).
+  double* d_t4s = nullptr;
+  int64_t t4s_doubles = 0;
   struct Launch : LaunchSpec {         // what kernel selection decided + what the launch runs on
     explicit Launch(const LaunchSpec& spec) : LaunchSpec(spec) {}
     hipStream_t stream = nullptr;      // aux stream (launch 0 runs on the caller's stream)
     hipEvent_t done = nullptr;
     int64_t t4_off = 0;                // four-wave launch: its first record in d_t4
+    int64_t t4s_off = 0, t4s_stride = 0;   // … its first double in d_t4s, doubles per column
   };
   std::vector<Launch> launches;
   hipEvent_t ev_fork = nullptr;
@@ -374,7 +381,9 @@ hipError_t launch_twisted4_prepares(sls_plan* pl, hipStream_t stream) {
     if (!(L.kind == LaunchKind::Twisted && L.four)) continue;
     KernelParams q = pl->kp;
     q.order_off = L.order_off; q.nsub = L.nsub; q.t4_stride = pl->t4_stride;
-    hipError_t e = launch_twisted4_prepare(q, pl->d_t4 + L.t4_off * pl->t4_stride, stream);
+    q.w_mcap = L.mcap;
+    q.t4_static = pl->d_t4s ? pl->d_t4s + L.t4s_off : nullptr; q.t4_static_stride = L.t4s_stride;
+    hipError_t e = launch_twisted4_prepare(L.cls, q, pl->d_t4 + L.t4_off * pl->t4_stride, stream);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -1005,10 +1014,20 @@ static int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_pla
     if ((rc = dalloc(pl, std::max<size_t>(nop, 1), &pl->d_upd_stage)) || (rc = dalloc(pl, 1, &pl->d_upd_rejected))) return bail(rc);
   }
   for (auto& L : pl->launches)
-    if (L.kind == LaunchKind::Twisted && L.four) { L.t4_off = pl->t4_records; pl->t4_records += L.nsub; }
+    if (L.kind == LaunchKind::Twisted && L.four) {
+      L.t4_off = pl->t4_records; pl->t4_records += L.nsub;
+      L.t4s_stride = twisted4_static_doubles(L.cls, kp.T);
+      L.t4s_off = pl->t4s_doubles; pl->t4s_doubles += L.t4s_stride * L.nsub;
+    }
   if (pl->t4_records) {
-    pl->t4_stride = twisted4_record_bytes(kp.w_nzA, kp.w_nzAc, kp.w_nzB, kp.w_nzBc);
+    pl->t4_stride = twisted4_record_bytes(kp.w_nzA, kp.w_nzAc, kp.w_nzB, kp.w_nzBc, kp.T);
     if ((rc = dalloc(pl, (size_t)(pl->t4_records * pl->t4_stride), &pl->d_t4))) return bail(rc);
+    // A four-wave launch has at most one column per compute unit, a column (T + 1) slots of 3 or 5 KiB: the README chain takes
+    // 5.3 MiB, 256 columns at T = 29 take 23 MiB.  Beyond the budget (256 columns: horizons past 84 in the three-tile classes,
+    // past 50 in the four-tile ones) the plan keeps no pool and its launches use the rebuild instantiation.
+    const char* pre = sls_knob("SLS_T4_PRESTATIC");
+    if (!(pre && pre[0] == '0') && pl->t4s_doubles * (int64_t)sizeof(double) <= kT4StaticBudget)
+      if ((rc = dalloc(pl, (size_t)pl->t4s_doubles, &pl->d_t4s))) return bail(rc);
   }
   tick("launch list + requests");
   if ((rc = arena_commit(pl))) return bail(rc);
@@ -1394,6 +1413,7 @@ static int enqueue_launches(sls_plan* plan, const KernelParams& kp, hipStream_t 
       if (L.four) {
         q.t4_rec = plan->d_t4 + L.t4_off * plan->t4_stride; q.t4_stride = plan->t4_stride;
         q.t4_pos = sel ? sel->pos + L.order_off : nullptr;
+        q.t4_static = plan->d_t4s ? plan->d_t4s + L.t4s_off : nullptr; q.t4_static_stride = L.t4s_stride;
       }
       e = (L.kind == LaunchKind::Twisted) ? (L.four ? launch_twisted4(L.cls, q, grid, L.lds, ls) : launch_twisted(L.cls, q, grid, L.lds, ls))
                         : launch_wave(L.cls, q, grid, L.lds, ls);
@@ -2063,6 +2083,55 @@ int sls_plan_debug_twisted4_tables(sls_plan* plan, int64_t* n_columns, int32_t* 
     if (counts) std::memcpy(counts + 4 * i, rec + 16, 16);
     if (values) std::memcpy(values + ne * i, rec + kT4RecHeader, ne * 8);
     if (indices) std::memcpy(indices + ne * i, rec + kT4RecHeader + ne * 8, ne * 4);
+  }
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): δ, slot flags and static blocks of the four-wave columns, in col_status order */
+int sls_plan_debug_twisted4_static(sls_plan* plan, int64_t* n_columns, int32_t* n_slots, int64_t* offsets, double* delta,
+                                   uint8_t* valid, double* blocks) {
+  if (!plan || !n_columns) return fail(nullptr, SLS_EINVAL, "null argument");
+  if (!plan->t4_records) return fail(plan->ctx, SLS_EINVAL, "this plan has no four-wave launch");
+  if (!plan->d_t4s) return fail(plan->ctx, SLS_EINVAL, "this plan keeps no static blocks (its launches rebuild them)");
+  const KernelParams& kp = plan->kp;
+  const int64_t slots = kp.T + 1;
+  *n_columns = plan->t4_records;
+  if (n_slots) *n_slots = (int32_t)slots;
+  struct Col { int64_t out_index, record, first, doubles; };
+  std::vector<Col> by_col;
+  for (const auto& L : plan->launches) {
+    if (!(L.kind == LaunchKind::Twisted && L.four)) continue;
+    for (int s = 0; s < L.nsub; ++s)
+      by_col.push_back({plan->sym.subs[(size_t)plan->sym.order[(size_t)L.order_off + s]].out_index, L.t4_off + s,
+                        L.t4s_off + s * L.t4s_stride, L.t4s_stride});
+  }
+  std::sort(by_col.begin(), by_col.end(), [](const Col& a, const Col& b) { return a.out_index < b.out_index; });
+  if (offsets) {
+    int64_t o = 0;
+    for (size_t i = 0; i < by_col.size(); ++i) { offsets[i] = o; o += by_col[i].doubles; }
+    offsets[by_col.size()] = o;
+  }
+  if (!delta && !valid && !blocks) return 0;
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  HIPCHK(plan->ctx, hipDeviceSynchronize());      // a plant update may still be rewriting the pool on the caller's stream
+  if (delta || valid) {
+    std::vector<unsigned char> host((size_t)(plan->t4_records * plan->t4_stride));
+    HIPCHK(plan->ctx, hipMemcpy(host.data(), plan->d_t4, host.size(), hipMemcpyDeviceToHost));
+    const size_t tail = (size_t)twisted4_record_tail(kp.w_nzA, kp.w_nzAc, kp.w_nzB, kp.w_nzBc);
+    for (size_t i = 0; i < by_col.size(); ++i) {
+      const unsigned char* rec = host.data() + (size_t)by_col[i].record * plan->t4_stride + tail;
+      if (delta) std::memcpy(delta + i, rec, 8);
+      if (valid) std::memcpy(valid + (size_t)slots * i, rec + 8, (size_t)slots);
+    }
+  }
+  if (blocks) {
+    std::vector<double> host((size_t)plan->t4s_doubles);
+    HIPCHK(plan->ctx, hipMemcpy(host.data(), plan->d_t4s, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+    int64_t o = 0;
+    for (size_t i = 0; i < by_col.size(); ++i) {
+      std::memcpy(blocks + o, host.data() + by_col[i].first, (size_t)by_col[i].doubles * sizeof(double));
+      o += by_col[i].doubles;
+    }
   }
   return 0;
 }

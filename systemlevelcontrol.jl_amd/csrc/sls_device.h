@@ -84,6 +84,10 @@ struct KernelParams {
   // a selected run (sls_plan_execute_columns) draws from a compacted order: t4_pos[s] is the launch position whose record column
   // s of the compacted list uses.  NULL = the full execute, record s itself
   const int32_t* t4_pos;
+  // the static blocks S_k of THIS launch's columns (twisted4_prepare_kernel, layout: twisted4_static_doubles below), indexed
+  // like the records; NULL = the launch rebuilds them (twisted4_prepare_kernel then writes none either)
+  double* t4_static;
+  int64_t t4_static_stride;   // doubles per column
 };
 
 // LDS bytes the general kernel needs for given caps (must match the carve in the kernel).
@@ -214,8 +218,23 @@ constexpr int kT4RecHeader = 32;                         // bytes in front of th
 static inline __host__ __device__ int64_t twisted4_record_entries(int nzA, int nzAc, int nzB, int nzBc) {
   return (int64_t)(nzA + nzAc + nzB) * 32 + (int64_t)nzBc * 64;
 }
-static inline __host__ __device__ int64_t twisted4_record_bytes(int nzA, int nzAc, int nzB, int nzBc) {
+// Behind the lists (twisted4_record_tail): the column's Tikhonov shift δ (one double), then one byte per slot 0 … T of the
+// column's static-block pool, 1 = twisted4_prepare_kernel filled the slot.
+static inline __host__ __device__ int64_t twisted4_record_tail(int nzA, int nzAc, int nzB, int nzBc) {
   return kT4RecHeader + 12 * twisted4_record_entries(nzA, nzAc, nzB, nzBc);      // a multiple of 32
+}
+static inline __host__ __device__ int64_t twisted4_record_bytes(int nzA, int nzAc, int nzB, int nzBc, int T) {
+  return twisted4_record_tail(nzA, nzAc, nzB, nzBc) + (8 + (T + 1) + 31) / 32 * 32;
+}
+// Static blocks of one four-wave column: slots k = 1 … T hold S_k = δI + W_k + B̃ Wu_{k−1} B̃ᵀ + Ã W_{k−1} Ãᵀ, slot 0 the
+// upward helper's first block (S_1 with δ·w/(δ + w) in the place of Wx_0).  A slot is what the helper wave holds in registers:
+// lane 8·a + b of the 8×8 lane grid owns the entries (a + 8·ri, b + 8·cj) of the block; of those the tiles ri ≤ cj are stored,
+// in the order (0,0), (0,1), … (0,TR−1), (1,1), … — TQ = TR(TR+1)/2 doubles per lane (6 in the three-tile classes, 10 in the
+// four-tile ones) — as [slot][q][lane]: TQ coalesced rows of 64 doubles per slot.
+static inline __host__ __device__ int twisted4_tile_rows(int cls) { return cls <= 3 ? 3 : 4; }     // TR of the NPL = 32 classes 2 … 5
+static inline __host__ __device__ int64_t twisted4_static_doubles(int cls, int T) {
+  const int64_t TR = twisted4_tile_rows(cls);
+  return (int64_t)(T + 1) * (TR * (TR + 1) / 2) * 64;
 }
 
 // ---- device mask recipe (sls_masks.hip) ----

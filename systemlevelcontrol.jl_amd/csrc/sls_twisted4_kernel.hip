@@ -28,6 +28,9 @@
 // and values (a binary search in the index set per entry), the list lengths, and which blocks repeat their predecessor's
 // masks — depends only on what a plan fixes.  twisted4_prepare_kernel (below) does it once per plan, one record per column in a
 // plan-owned pool; a launch copies the record into LDS with coalesced loads and builds its dense images from there.
+// The static parts S_k themselves (and δ) are plan constants too: the same kernel builds them into a second pool, in the helper's
+// register layout, and the helpers load them (h2_column_twisted4_kernel<…, PRE = true>); the instantiation with PRE = false
+// still rebuilds them per launch, for plans whose pool would be too large and for SLS_T4_PRESTATIC=0.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <utility>
@@ -40,9 +43,10 @@ namespace sls {
 #define SLS_T4_EXP 0          // timing experiments (WRONG results on purpose): 1 = helper does not eliminate, 2 = helper without cross-lane traffic, 3 = without ds_bpermute
 #endif
 
-// meeting block.  The upward side carries the mask ramp (its helper rebuilds the static part for every block while the
-// masks still grow — in the three-tile classes from Ã / B̃ values gathered once per column into registers, so a rebuild reads
-// weights only — the downward side's masks repeat) and the middle block's own inversion: it gets the shorter half.
+// meeting block.  The upward side carries the mask ramp (its helper needs a fresh static part for every block while the
+// masks still grow — loaded from the plan's pool, or rebuilt: in the three-tile classes from Ã / B̃ values gathered once per
+// column into registers, so a rebuild reads weights only — the downward side's masks repeat) and the middle block's own
+// inversion: it gets the shorter half.
 #ifndef SLS_T4_MIDDLE_SHIFT
 #define SLS_T4_MIDDLE_SHIFT 0
 #endif
@@ -367,9 +371,96 @@ __device__ __forceinline__ void helper_eliminate(double (&Xw)[TR * TR], double (
   });
 }
 
-template <int NPL, int RPL>
+// Static part of block k on the lane grid, S_k = δI + W_k + Ã W_{k−1} Ãᵀ + B̃ Wu_{k−1} B̃ᵀ (stored half, tiles ri ≤ cj): the ONE text
+// of this arithmetic.  twisted4_prepare_kernel runs it once per plan into the column's pool; the rebuild instantiation of the
+// solve kernel runs it per launch.  Both must give the same bits, so the order is fixed: the diagonal δ + wc[i], then the Ã
+// entries in list order (the first KH from registers, padding included, then the tail up to the longest list), then B̃'s.
+// wc / wp: Wx_k / Wx_{k−1} rows of the weight table, wu: Wu_{k−1}; fold0: δ·w/(δ + w) in the place of Wx_0 (upward block 1).
+// HOIST: the second factors come from GA / GB (the values the LDS gathers below would read, held in registers).
+template <int TR, bool HOIST, int KH, int KB, int NPL, int LDT>
+__device__ __forceinline__ void twisted4_static_block(double (&Sw)[TR * TR], const double delta, const double* wc_, const double* wp_,
+                                                      const double* wu_, const bool fold0, const int ta, const int tb,
+                                                      const int nzA, const int nzB, const int MC,
+                                                      const int (&hac)[TR][KH], const double (&hav)[TR][KH],
+                                                      const int (&hbc)[TR][KB], const double (&hbv)[TR][KB],
+                                                      const double (&GA)[KH][TR][TR], const double (&GB)[KB][TR][TR],
+                                                      const int32_t* arow_c, const double* arow_v, const int32_t* brow_c,
+                                                      const double* brow_v, const double* Ad, const double* Bd) {
+#pragma unroll
+  for (int ri = 0; ri < TR; ++ri) {
+    const int i = ta + 8 * ri;
+    const double di = delta + wc_[i];
+#pragma unroll
+    for (int cj = 0; cj < TR; ++cj) Sw[ri * TR + cj] = (i == tb + 8 * cj) ? di : 0.0;
+  }
+#pragma unroll
+  for (int e = 0; e < KH; ++e) {
+#pragma unroll
+    for (int ri = 0; ri < TR; ++ri) {
+      const int cc = hac[ri][e];
+      const double w0 = wp_[cc];
+      const double v = hav[ri][e] * (fold0 ? delta * w0 / (delta + w0) : w0);
+#pragma unroll
+      for (int cj = ri; cj < TR; ++cj) {
+        double g;
+        if constexpr (HOIST) g = GA[e][ri][cj]; else g = Ad[(tb + 8 * cj) * LDT + cc];
+        Sw[ri * TR + cj] = __builtin_fma(v, g, Sw[ri * TR + cj]);
+      }
+    }
+  }
+  for (int e = KH; e < nzA; ++e) {
+#pragma unroll
+    for (int ri = 0; ri < TR; ++ri) {
+      const int i = ta + 8 * ri;
+      const int cc = arow_c[e * NPL + i];
+      const double w0 = wp_[cc];
+      const double v = arow_v[e * NPL + i] * (fold0 ? delta * w0 / (delta + w0) : w0);
+#pragma unroll
+      for (int cj = ri; cj < TR; ++cj) Sw[ri * TR + cj] = __builtin_fma(v, Ad[(tb + 8 * cj) * LDT + cc], Sw[ri * TR + cj]);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < KB; ++e) {
+#pragma unroll
+    for (int ri = 0; ri < TR; ++ri) {
+      const int cc = hbc[ri][e];
+      const double v = hbv[ri][e] * wu_[cc];
+#pragma unroll
+      for (int cj = ri; cj < TR; ++cj) {
+        double g;
+        if constexpr (HOIST) g = GB[e][ri][cj]; else g = Bd[(tb + 8 * cj) * MC + cc];
+        Sw[ri * TR + cj] = __builtin_fma(v, g, Sw[ri * TR + cj]);
+      }
+    }
+  }
+  for (int e = KB; e < nzB; ++e) {
+#pragma unroll
+    for (int ri = 0; ri < TR; ++ri) {
+      const int i = ta + 8 * ri;
+      const int cc = brow_c[e * NPL + i];
+      const double v = brow_v[e * NPL + i] * wu_[cc];
+#pragma unroll
+      for (int cj = ri; cj < TR; ++cj) Sw[ri * TR + cj] = __builtin_fma(v, Bd[(tb + 8 * cj) * MC + cc], Sw[ri * TR + cj]);
+    }
+  }
+}
+
+// Which slots of a column's pool the helpers read (c = twisted4_middle(T); bits: the mask-repeat words of the record, taken as
+// 0 when the reuse is compiled out).  The upward helper produces blocks 1 … c: block 1 from slot 0, block 2 always from slot 2,
+// a later block k from slot k unless k < 64 and bit k of bits[0] lets it reuse its predecessor's.  The downward helper
+// produces blocks T … c + 1 (its contribution to the middle block c is zeros): block T always from slot T, a later block k
+// from slot k unless k < 64 and bit k of bits[1] is set.  The solve kernel's helper loop follows the same rule.
+static inline __host__ __device__ bool twisted4_slot_read(int slot, int T, int c, unsigned long long up, unsigned long long down) {
+  if (slot == 0) return c >= 1;
+  const bool rep_up = slot < 64 && ((up >> slot) & 1ull), rep_down = slot < 64 && ((down >> slot) & 1ull);
+  const bool by_up = slot >= 2 && slot <= c && (slot == 2 || !rep_up);
+  const bool by_down = slot >= c + 1 && slot <= T && (slot == T || !rep_down);
+  return by_up || by_down;
+}
+
+template <int NPL, int RPL, bool PRE>
 __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, const SubDesc& sd, const unsigned char* __restrict__ rec,
-                                                      double* __restrict__ fac, unsigned char* lds_raw) {
+                                                      const double* __restrict__ spool, double* __restrict__ fac, unsigned char* lds_raw) {
   static_assert(NPL == 32, "written for the NPL = 32 classes (8×8 lane grid)");
   constexpr int HS = 64 / NPL, NP = HS * RPL;
   constexpr int TR = (NP + 7) / 8, NR = 8 * TR, TT = TR * TR;
@@ -452,9 +543,11 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
     for (int i = lane; i < T * nm; i += 64) mask[i] = p.mask_pool[sd.off_mask + i];
   } else if (wv == 2) {
     for (int i = lane; i < NR * LDT; i += 64) Ad[i] = 0.0;
-    for (int i = lane; i < NPL * MC; i += 64) Bd[i] = 0.0;
+    if constexpr (!PRE) { for (int i = lane; i < NPL * MC; i += 64) Bd[i] = 0.0; }
   } else {
     if (lane < 4) nzs[lane] = reinterpret_cast<const int32_t*>(rec + 16)[lane];
+    // δ depends on the weights and the row lists only: with the plan-time blocks it comes from the record, like them
+    if constexpr (PRE) { if (lane == 4) red[4] = *reinterpret_cast<const double*>(rec + twisted4_record_tail(capA, capAc, capB, capBc)); }
     if (lane < 2) samew[lane] = reinterpret_cast<const unsigned long long*>(rec)[lane];
     for (int i = lane; i < (T + 1) * NPL; i += 64) { lam[i] = 0.0; rq[i] = 0.0; xs[i] = 0.0; }
   }
@@ -465,7 +558,9 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
   }
   __syncthreads();
   // LDS only from here: no global chain, no search
-  if (wv == 0) {
+  if (PRE && wv < 2) {
+    // plan-time static blocks: no δ reduction and no dense B̃ in the launch (the regions stay in the carve, unused)
+  } else if (wv == 0) {
     const int a0 = nzs[0], a2 = nzs[2];
     double sc = 0.0;
     if (lane < n) {
@@ -499,9 +594,11 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
       const int k = i / NPL, jj = i % NPL;
       wxt[i] = (k < T && jj < n && mask[k * nm + jj]) ? hx[jj] : 0.0;
     }
-    for (int i = lane; i < T * MC; i += 64) {
-      const int k = i / MC, q = i % MC;
-      wut[i] = (q < m && mask[k * nm + n + q]) ? hu[q] : 0.0;
+    if constexpr (!PRE) {
+      for (int i = lane; i < T * MC; i += 64) {
+        const int k = i / MC, q = i % MC;
+        wut[i] = (q < m && mask[k * nm + n + q]) ? hu[q] : 0.0;
+      }
     }
   }
   __syncthreads();
@@ -767,11 +864,12 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
     } else {
       // =================== helper wave: static part S_k, border X, elimination behind the chain wave's pivots ===================
       // row lists of Ã and B̃ for this lane's tile rows a + 8·ri: first KH / KB entries in registers for the whole column
-      constexpr int KH = 4, KB = 2;
+      // (rebuild instantiation only: with plan-time blocks the helper reads no list at all)
+      constexpr int KH = 4, KB = 2, TQ = TR * (TR + 1) / 2;
       int hac[TR][KH], hbc[TR][KB];
       double hav[TR][KH], hbv[TR][KB];
 #pragma unroll
-      for (int ri = 0; ri < TR; ++ri) {
+      for (int ri = 0; ri < TR && !PRE; ++ri) {
         const int i = ta + 8 * ri;
 #pragma unroll
         for (int e = 0; e < KH; ++e) { const bool ok = e < capA; hac[ri][e] = ok ? arow_c[e * NPL + i] : 0; hav[ri][e] = ok ? arow_v[e * NPL + i] : 0.0; }
@@ -789,10 +887,12 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
         for (int ri = 0; ri < TR; ++ri) {
 #pragma unroll
           for (int cj = ri; cj < TR; ++cj) {
+            if constexpr (!PRE) {
 #pragma unroll
-            for (int e = 0; e < KH; ++e) GA[e][ri][cj] = Ad[(tb + 8 * cj) * LDT + hac[ri][e]];
+              for (int e = 0; e < KH; ++e) GA[e][ri][cj] = Ad[(tb + 8 * cj) * LDT + hac[ri][e]];
 #pragma unroll
-            for (int e = 0; e < KB; ++e) GB[e][ri][cj] = Bd[(tb + 8 * cj) * MC + hbc[ri][e]];
+              for (int e = 0; e < KB; ++e) GB[e][ri][cj] = Bd[(tb + 8 * cj) * MC + hbc[ri][e]];
+            }
           }
 #pragma unroll
           for (int cj = 0; cj < TR; ++cj) {
@@ -833,79 +933,59 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
       double Xn[TT];
       if (s_end >= 2) load_border((dir == 0) ? 2 : T - 1, Xn);
       if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { __builtin_amdgcn_sched_barrier(0); ph[3] = __builtin_amdgcn_s_memtime() - tlast; }   // pre-loop: lap(0) → first block
+      // What step s starts from: 0 = zeros (the downward helper's share of the middle block), 1 = the cached static part of the
+      // step before (masks repeat), 2 = a fresh static part — rebuilt here, or read from the column's plan-time pool
+      // (twisted4_slot_read states the same rule per slot).  `have`: a cached part exists (any fresh block but the upward first).
+      auto step_kind = [&](int s, bool have) -> int {
+        const int k = (dir == 0) ? s : T - s + 1;
+        if (dir == 1 && k == c) return 0;
+        return (have && k < 64 && ((samebits >> k) & 1ull) && !(dir == 0 && s == 2)) ? 1 : 2;
+      };
+      // Plan-time blocks: the step that needs a fresh block loads this lane's TQ doubles of it and waits for them — one memory
+      // latency (≈ 1.7 k cycles) where the rebuild took 2.8 k.  Loading a step ahead, behind the previous block's elimination,
+      // hides that latency too and was measured SLOWER: a helper that is never late runs in lock step
+      // with its chain wave, whose Gauss–Jordan then loses more than the hand-off waits gain.
+      auto load_slot = [&](int s, double (&Sl)[TQ]) {
+        const int slot = (dir == 0 && s == 1) ? 0 : ((dir == 0) ? s : T - s + 1);
+        const double* src = spool + (int64_t)slot * (TQ * 64) + lane;
+#pragma unroll
+        for (int q = 0; q < TQ; ++q) Sl[q] = src[q * 64];
+      };
+      auto hand_over = [&](const double (&Sw)[TT], int s) {
+#pragma unroll
+        for (int ri = 0; ri < TR; ++ri) {
+#pragma unroll
+          for (int cj = ri; cj < TR; ++cj) hand[(ta + 8 * ri) * LDT + tb + 8 * cj] = Sw[ri * TR + cj];
+        }
+        if (lane == 0) flag_store(flagB, s);
+        WSYNC();
+      };
       for (int s = 1; s <= s_end; ++s) {
         unsigned long long q0 = (SLS_T4_PHASES != 0) ? __builtin_amdgcn_s_memtime() : 0;
         const int k = (dir == 0) ? s : T - s + 1;           // block being produced (downward helper's last step: k = c, the middle)
-        const bool mid_down = (dir == 1) && (k == c);
-        const bool same = have_S && !mid_down && k < 64 && ((samebits >> k) & 1ull) && !(dir == 0 && s == 2);
+        const int kind = step_kind(s, have_S);
+        const bool fold0 = (dir == 0) && (s == 1);           // upward, block 1: P_0 = (δ + Wx_0)⁻¹ is diagonal, W − W P_0 W = δ·w/(δ + w) takes the place of Wx_0
         double Sw[TT];
-        if (mid_down) {
+        if (kind == 0) {
 #pragma unroll
           for (int q = 0; q < TT; ++q) Sw[q] = 0.0;
-        } else if (same) {
+        } else if (kind == 1) {
 #pragma unroll
           for (int q = 0; q < TT; ++q) Sw[q] = Sc[q];
         } else {
-          const double* wc_ = wxt + k * NPL;
-          const double* wp_ = wxt + (k - 1) * NPL;
-          const double* wu_ = wut + (k - 1) * MC;
-          const bool fold0 = (dir == 0) && (s == 1);         // upward, block 1: P_0 = (δ + Wx_0)⁻¹ is diagonal, W − W P_0 W = δ·w/(δ + w) takes the place of Wx_0
-#pragma unroll
-          for (int ri = 0; ri < TR; ++ri) {
-            const int i = ta + 8 * ri;
-            const double di = delta + wc_[i];
-#pragma unroll
-            for (int cj = 0; cj < TR; ++cj) Sw[ri * TR + cj] = (i == tb + 8 * cj) ? di : 0.0;
-          }
-#pragma unroll
-          for (int e = 0; e < KH; ++e) {
+          if constexpr (PRE) {
+            double Sl[TQ];
+            load_slot(s, Sl);
+            int q = 0;
 #pragma unroll
             for (int ri = 0; ri < TR; ++ri) {
-              const int cc = hac[ri][e];
-              const double w0 = wp_[cc];
-              const double v = hav[ri][e] * (fold0 ? delta * w0 / (delta + w0) : w0);
 #pragma unroll
-              for (int cj = ri; cj < TR; ++cj) {
-                double g;
-                if constexpr (HOIST) g = GA[e][ri][cj]; else g = Ad[(tb + 8 * cj) * LDT + cc];
-                Sw[ri * TR + cj] = __builtin_fma(v, g, Sw[ri * TR + cj]);
-              }
+              for (int cj = 0; cj < TR; ++cj) Sw[ri * TR + cj] = (ri <= cj) ? Sl[q++] : 0.0;      // the half below is never read
             }
-          }
-          for (int e = KH; e < nzA; ++e) {
-#pragma unroll
-            for (int ri = 0; ri < TR; ++ri) {
-              const int i = ta + 8 * ri;
-              const int cc = arow_c[e * NPL + i];
-              const double w0 = wp_[cc];
-              const double v = arow_v[e * NPL + i] * (fold0 ? delta * w0 / (delta + w0) : w0);
-#pragma unroll
-              for (int cj = ri; cj < TR; ++cj) Sw[ri * TR + cj] = __builtin_fma(v, Ad[(tb + 8 * cj) * LDT + cc], Sw[ri * TR + cj]);
-            }
-          }
-#pragma unroll
-          for (int e = 0; e < KB; ++e) {
-#pragma unroll
-            for (int ri = 0; ri < TR; ++ri) {
-              const int cc = hbc[ri][e];
-              const double v = hbv[ri][e] * wu_[cc];
-#pragma unroll
-              for (int cj = ri; cj < TR; ++cj) {
-                double g;
-                if constexpr (HOIST) g = GB[e][ri][cj]; else g = Bd[(tb + 8 * cj) * MC + cc];
-                Sw[ri * TR + cj] = __builtin_fma(v, g, Sw[ri * TR + cj]);
-              }
-            }
-          }
-          for (int e = KB; e < nzB; ++e) {
-#pragma unroll
-            for (int ri = 0; ri < TR; ++ri) {
-              const int i = ta + 8 * ri;
-              const int cc = brow_c[e * NPL + i];
-              const double v = brow_v[e * NPL + i] * wu_[cc];
-#pragma unroll
-              for (int cj = ri; cj < TR; ++cj) Sw[ri * TR + cj] = __builtin_fma(v, Bd[(tb + 8 * cj) * MC + cc], Sw[ri * TR + cj]);
-            }
+          } else {
+            twisted4_static_block<TR, HOIST, KH, KB, NPL, LDT>(Sw, delta, wxt + k * NPL, wxt + (k - 1) * NPL, wut + (k - 1) * MC, fold0,
+                                                               ta, tb, nzA, nzB, MC, hac, hav, hbc, hbv, GA, GB,
+                                                               arow_c, arow_v, brow_c, brow_v, Ad, Bd);
           }
           if (!fold0) {
 #pragma unroll
@@ -922,13 +1002,7 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
           if (SLS_T4_EXP != 1 && SLS_T4_EXP != 4) helper_eliminate<NP, TR, RS>(Xw, Sw, lane, n, rowbuf, flagA, (s - 1) * 64, xbuf, ph[2]);
           if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { __builtin_amdgcn_sched_barrier(0); asm volatile("" :: "v"(Sw[0])); const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[1] += q1 - q0; q0 = q1; }
         }
-#pragma unroll
-        for (int ri = 0; ri < TR; ++ri) {
-#pragma unroll
-          for (int cj = ri; cj < TR; ++cj) hand[(ta + 8 * ri) * LDT + tb + 8 * cj] = Sw[ri * TR + cj];
-        }
-        if (lane == 0) flag_store(flagB, s);
-        WSYNC();
+        hand_over(Sw, s);
       }
     }
     lap(1);                        // own half of the factorisation
@@ -992,14 +1066,17 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
   }
 }
 
-template <int NPL, int RPL>
+// PRE: the helpers read the static blocks from the plan's pool (p.t4_static); otherwise they rebuild them in the launch.  A
+// template flag, not a branch: the rebuild's gather registers must not stay live in the instantiation that never rebuilds.
+template <int NPL, int RPL, bool PRE>
 __global__ __launch_bounds__(256, 1) void h2_column_twisted4_kernel(const KernelParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   double* fac = p.fac_ws + (int64_t)blockIdx.x * p.fac_stride;
   for (int s = blockIdx.x; s < p.nsub; s += gridDim.x) {
     const SubDesc sd = p.subs[p.order[p.order_off + s]];
-    const int rs = p.t4_pos ? p.t4_pos[s] : s;      // a selected run: the record of the column's place in the full launch
-    twisted4_solve_column<NPL, RPL>(p, sd, p.t4_rec + (int64_t)rs * p.t4_stride, fac, lds_raw);
+    const int rs = p.t4_pos ? p.t4_pos[s] : s;      // a selected run: the record (and the pool) of the column's place in the full launch
+    const double* spool = PRE ? p.t4_static + (int64_t)rs * p.t4_static_stride : nullptr;
+    twisted4_solve_column<NPL, RPL, PRE>(p, sd, p.t4_rec + (int64_t)rs * p.t4_stride, spool, fac, lds_raw);
   }
 }
 
@@ -1008,13 +1085,25 @@ __global__ __launch_bounds__(256, 1) void h2_column_twisted4_kernel(const Kernel
 // sls_device.h (twisted4_record_bytes).  The lists follow CSR order, skip entries outside the index set and stored zeros, and
 // are never cut: the capacities are the structural row maxima.  Every lane writes its own column of every list, padding
 // included, so the record needs no clear.
-__global__ __launch_bounds__(64) void twisted4_prepare_kernel(const KernelParams p, unsigned char* __restrict__ pool) {
+// With a pool (p.t4_static, TR = the class's tile rows; TR = 0: none) the kernel then builds what else a launch would rebuild from
+// the same inputs every time: δ (into the record's tail) and the static blocks S_k the helpers read (twisted4_slot_read), in the
+// helper's register layout (sls_device.h: twisted4_static_doubles), with the launch's own arithmetic (twisted4_static_block).
+// Wave 0 does the symbolic part while waves 1 … 3 lay out weights and weight tables; the slots are dealt round over the four waves.
+template <int TR>
+__global__ __launch_bounds__(256) void twisted4_prepare_kernel(const KernelParams p, unsigned char* __restrict__ pool) {
   constexpr int NPL = 32;
+  constexpr int LDT = 40, NR = TR > 0 ? 8 * TR : 8, TT = TR > 0 ? TR * TR : 1, TQ = TR * (TR + 1) / 2;
   __shared__ int32_t sx[NPL];
   __shared__ int32_t su[64];
-  const int lane = threadIdx.x;
+  __shared__ unsigned long long sbits[2];
+  __shared__ int32_t snz[4];
+  __shared__ double sdelta;
+  extern __shared__ __attribute__((aligned(16))) unsigned char prep_lds[];
+  const int wv = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   const SubDesc sd = p.subs[p.order[p.order_off + blockIdx.x]];
   const int n = sd.n, m = sd.m, nm = n + m, T = p.T;
+  const int MC = p.w_mcap;
   const int capA = p.w_nzA, capAc = p.w_nzAc, capB = p.w_nzB, capBc = p.w_nzBc;
   unsigned char* rec = pool + (int64_t)blockIdx.x * p.t4_stride;
   double* arow_v = reinterpret_cast<double*>(rec + kT4RecHeader);
@@ -1025,89 +1114,211 @@ __global__ __launch_bounds__(64) void twisted4_prepare_kernel(const KernelParams
   int32_t* acol_c = arow_c + capA * NPL;
   int32_t* brow_c = acol_c + capAc * NPL;
   int32_t* bcol_c = brow_c + capB * NPL;
-  if (lane < NPL) sx[lane] = (lane < n) ? p.idx_pool[sd.off_sx + lane] : 0x7fffffff;
-  su[lane] = (lane < m) ? p.idx_pool[sd.off_su + lane] : 0x7fffffff;
-  __syncthreads();
-  int cntA = 0, cntB = 0, cntAc = 0, cntBc = 0;
-  if (lane < n) {
-    const int g = sx[lane];
-    for (int e = p.A_rowptr[g]; e < p.A_rowptr[g + 1]; ++e) {
-      const double v = p.A_val[e];
-      const int loc = (v != 0.0) ? wbsearch(sx, n, p.A_colidx[e]) : -1;
-      if (loc >= 0 && cntA < capA) { arow_c[cntA * NPL + lane] = loc; arow_v[cntA * NPL + lane] = v; ++cntA; }
-    }
-    for (int e = p.B_rowptr[g]; e < p.B_rowptr[g + 1]; ++e) {
-      const double v = p.B_val[e];
-      const int loc = (v != 0.0) ? wbsearch(su, m, p.B_colidx[e]) : -1;
-      if (loc >= 0 && cntB < capB) { brow_c[cntB * NPL + lane] = loc; brow_v[cntB * NPL + lane] = v; ++cntB; }
-    }
-    for (int e = p.At_rowptr[g]; e < p.At_rowptr[g + 1]; ++e) {
-      const double v = p.At_val[e];
-      const int loc = (v != 0.0) ? wbsearch(sx, n, p.At_colidx[e]) : -1;
-      if (loc >= 0 && cntAc < capAc) { acol_c[cntAc * NPL + lane] = loc; acol_v[cntAc * NPL + lane] = v; ++cntAc; }
-    }
-  }
-  if (lane < m) {
-    const int g = su[lane];
-    for (int e = p.Bt_rowptr[g]; e < p.Bt_rowptr[g + 1]; ++e) {
-      const double v = p.Bt_val[e];
-      const int loc = (v != 0.0) ? wbsearch(sx, n, p.Bt_colidx[e]) : -1;
-      if (loc >= 0 && cntBc < capBc) { bcol_c[cntBc * 64 + lane] = loc; bcol_v[cntBc * 64 + lane] = v; ++cntBc; }
-    }
-  }
-  if (lane < NPL) {
-    for (int e = cntA; e < capA; ++e) { arow_c[e * NPL + lane] = 0; arow_v[e * NPL + lane] = 0.0; }
-    for (int e = cntB; e < capB; ++e) { brow_c[e * NPL + lane] = 0; brow_v[e * NPL + lane] = 0.0; }
-    for (int e = cntAc; e < capAc; ++e) { acol_c[e * NPL + lane] = 0; acol_v[e * NPL + lane] = 0.0; }
-  }
-  for (int e = cntBc; e < capBc; ++e) { bcol_c[e * 64 + lane] = 0; bcol_v[e * 64 + lane] = 0.0; }
-  const int a0 = wave_max_i32(cntA), a1 = wave_max_i32(cntAc), a2 = wave_max_i32(cntB), a3 = wave_max_i32(cntBc);
-  // mask-repeat bits: block k (2 ≤ k ≤ T−1, k < 64) may reuse the static part of the block produced before it — ko = k−1 upward,
-  // k+1 downward, ko ≤ T−1 — when the masks of (k, k−1) equal those of (ko, ko−1) on all n + m rows.  Every lane walks its rows
-  // down the time steps once (independent loads): d1 bit k = steps k and k−1 agree, d2 bit k = steps k+1 and k agree (bit 0 of
-  // either word is scratch); then upward = d1[k] ∧ d1[k−1], downward = d2[k] ∧ d1[k].
   const uint8_t* mask = p.mask_pool + sd.off_mask;
-  unsigned long long d1 = ~0ull, d2 = ~0ull;
-  const int klast = min(T - 1, 64);
-  for (int r = lane; r < nm; r += 64) {
-    uint8_t prev = mask[r];
+  // dynamic LDS (twisted4_prepare_lds_bytes; only with a pool): the images the static build reads, as the launch lays them out
+  double* Ad = reinterpret_cast<double*>(prep_lds);
+  double* Bd = Ad + NR * LDT;
+  double* wxt = Bd + NPL * MC;
+  double* wut = wxt + (T + 1) * NPL;
+  double* hx = wut + T * MC;
+  double* hu = hx + NPL;
+  if (wv == 0) {
+    if (lane < NPL) sx[lane] = (lane < n) ? p.idx_pool[sd.off_sx + lane] : 0x7fffffff;
+    su[lane] = (lane < m) ? p.idx_pool[sd.off_su + lane] : 0x7fffffff;
+    WSYNC();
+    int cntA = 0, cntB = 0, cntAc = 0, cntBc = 0;
+    if (lane < n) {
+      const int g = sx[lane];
+      for (int e = p.A_rowptr[g]; e < p.A_rowptr[g + 1]; ++e) {
+        const double v = p.A_val[e];
+        const int loc = (v != 0.0) ? wbsearch(sx, n, p.A_colidx[e]) : -1;
+        if (loc >= 0 && cntA < capA) { arow_c[cntA * NPL + lane] = loc; arow_v[cntA * NPL + lane] = v; ++cntA; }
+      }
+      for (int e = p.B_rowptr[g]; e < p.B_rowptr[g + 1]; ++e) {
+        const double v = p.B_val[e];
+        const int loc = (v != 0.0) ? wbsearch(su, m, p.B_colidx[e]) : -1;
+        if (loc >= 0 && cntB < capB) { brow_c[cntB * NPL + lane] = loc; brow_v[cntB * NPL + lane] = v; ++cntB; }
+      }
+      for (int e = p.At_rowptr[g]; e < p.At_rowptr[g + 1]; ++e) {
+        const double v = p.At_val[e];
+        const int loc = (v != 0.0) ? wbsearch(sx, n, p.At_colidx[e]) : -1;
+        if (loc >= 0 && cntAc < capAc) { acol_c[cntAc * NPL + lane] = loc; acol_v[cntAc * NPL + lane] = v; ++cntAc; }
+      }
+    }
+    if (lane < m) {
+      const int g = su[lane];
+      for (int e = p.Bt_rowptr[g]; e < p.Bt_rowptr[g + 1]; ++e) {
+        const double v = p.Bt_val[e];
+        const int loc = (v != 0.0) ? wbsearch(sx, n, p.Bt_colidx[e]) : -1;
+        if (loc >= 0 && cntBc < capBc) { bcol_c[cntBc * 64 + lane] = loc; bcol_v[cntBc * 64 + lane] = v; ++cntBc; }
+      }
+    }
+    if (lane < NPL) {
+      for (int e = cntA; e < capA; ++e) { arow_c[e * NPL + lane] = 0; arow_v[e * NPL + lane] = 0.0; }
+      for (int e = cntB; e < capB; ++e) { brow_c[e * NPL + lane] = 0; brow_v[e * NPL + lane] = 0.0; }
+      for (int e = cntAc; e < capAc; ++e) { acol_c[e * NPL + lane] = 0; acol_v[e * NPL + lane] = 0.0; }
+    }
+    for (int e = cntBc; e < capBc; ++e) { bcol_c[e * 64 + lane] = 0; bcol_v[e * 64 + lane] = 0.0; }
+    const int a0 = wave_max_i32(cntA), a1 = wave_max_i32(cntAc), a2 = wave_max_i32(cntB), a3 = wave_max_i32(cntBc);
+    // mask-repeat bits: block k (2 ≤ k ≤ T−1, k < 64) may reuse the static part of the block produced before it — ko = k−1 upward,
+    // k+1 downward, ko ≤ T−1 — when the masks of (k, k−1) equal those of (ko, ko−1) on all n + m rows.  Every lane walks its rows
+    // down the time steps once (independent loads): d1 bit k = steps k and k−1 agree, d2 bit k = steps k+1 and k agree (bit 0 of
+    // either word is scratch); then upward = d1[k] ∧ d1[k−1], downward = d2[k] ∧ d1[k].
+    unsigned long long d1 = ~0ull, d2 = ~0ull;
+    const int klast = min(T - 1, 64);
+    for (int r = lane; r < nm; r += 64) {
+      uint8_t prev = mask[r];
 #pragma unroll 8
-    for (int k = 1; k <= klast; ++k) {
-      const uint8_t cur = mask[k * nm + r];
-      const unsigned long long ne = (cur != prev) ? 1ull : 0ull;
-      d1 &= ~(ne << (k & 63));
-      d2 &= ~(ne << (k - 1));
-      prev = cur;
+      for (int k = 1; k <= klast; ++k) {
+        const uint8_t cur = mask[k * nm + r];
+        const unsigned long long ne = (cur != prev) ? 1ull : 0ull;
+        d1 &= ~(ne << (k & 63));
+        d2 &= ~(ne << (k - 1));
+        prev = cur;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { d1 &= __shfl_xor(d1, off); d2 &= __shfl_xor(d2, off); }
+    auto bit_range = [](int lo, int hi) -> unsigned long long {            // bits lo … hi, hi ≤ 63
+      return hi < lo ? 0ull : ((hi >= 63 ? ~0ull : ((1ull << (hi + 1)) - 1)) & ~((1ull << lo) - 1));
+    };
+    unsigned long long bits[2];
+    bits[0] = d1 & (d1 << 1) & bit_range(2, min(T - 1, 63));
+    bits[1] = d2 & d1 & bit_range(2, min(T - 2, 63));
+    if (lane == 0) {
+      reinterpret_cast<unsigned long long*>(rec)[0] = bits[0];
+      reinterpret_cast<unsigned long long*>(rec)[1] = bits[1];
+      int32_t* cnt = reinterpret_cast<int32_t*>(rec + 16);
+      cnt[0] = a0; cnt[1] = a1; cnt[2] = a2; cnt[3] = a3;
+      sbits[0] = bits[0]; sbits[1] = bits[1];
+      snz[0] = a0; snz[1] = a1; snz[2] = a2; snz[3] = a3;
+    }
+  } else if constexpr (TR > 0) {
+    // weights and weight tables exactly as the launch's setup makes them; the dense images start from zero
+    if (wv == 1) {
+      if (lane < NPL) hx[lane] = (lane < n) ? (sd.has_w ? p.w_pool[sd.off_w + lane] : 1.0) : 0.0;
+      hu[lane] = (lane < m) ? (sd.has_w ? p.w_pool[sd.off_w + n + lane] : 1.0) : 0.0;
+      WSYNC();
+      for (int i = lane; i < (T + 1) * NPL; i += 64) {
+        const int k = i / NPL, jj = i % NPL;
+        wxt[i] = (k < T && jj < n && mask[k * nm + jj]) ? hx[jj] : 0.0;
+      }
+      for (int i = lane; i < T * MC; i += 64) {
+        const int k = i / MC, q = i % MC;
+        wut[i] = (q < m && mask[k * nm + n + q]) ? hu[q] : 0.0;
+      }
+    } else if (wv == 2) {
+      for (int i = lane; i < NR * LDT; i += 64) Ad[i] = 0.0;
+    } else {
+      for (int i = lane; i < NPL * MC; i += 64) Bd[i] = 0.0;
     }
   }
+  if constexpr (TR > 0) {
+    __syncthreads();              // the record (written by wave 0) is read back below by all four waves
+    const int nzA = snz[0], nzB = snz[2];
+    if (wv == 0) {
+      // δ: the launch's reduction, operation for operation (rebuild instantiation, setup)
+      double sc = 0.0;
+      if (lane < n) {
+        sc = hx[lane];
+        for (int e = 0; e < nzA; ++e) { const double v = arow_v[e * NPL + lane]; sc = __builtin_fma(v * v, hx[arow_c[e * NPL + lane]], sc); }
+        for (int e = 0; e < nzB; ++e) { const double v = brow_v[e * NPL + lane]; sc = __builtin_fma(v * v, hu[brow_c[e * NPL + lane]], sc); }
+      }
+      const double dl_ = p.delta_rel * wave_max_f64(sc);
+      if (lane == 0) { sdelta = dl_; *reinterpret_cast<double*>(rec + twisted4_record_tail(capA, capAc, capB, capBc)) = dl_; }
+    } else if (wv == 1) {
+      if (lane < n) {
+        for (int e = 0; e < nzB; ++e) {
+          const double v = brow_v[e * NPL + lane];
+          if (v != 0.0) Bd[lane * MC + brow_c[e * NPL + lane]] = v;
+        }
+      }
+    } else if (wv == 2) {
+      if (lane < n) {
+        for (int e = 0; e < nzA; ++e) {
+          const double v = arow_v[e * NPL + lane];
+          if (v != 0.0) Ad[lane * LDT + arow_c[e * NPL + lane]] += v;
+        }
+      }
+    }
+    __syncthreads();
+    const double delta = sdelta;
+    const int c = twisted4_middle(T);
+    const unsigned long long up = (SLS_T4_SAME != 0) ? sbits[0] : 0ull, down = (SLS_T4_SAME != 0) ? sbits[1] : 0ull;
+    uint8_t* valid = rec + twisted4_record_tail(capA, capAc, capB, capBc) + 8;
+    for (int k = threadIdx.x; k <= T; k += 256) valid[k] = twisted4_slot_read(k, T, c, up, down) ? 1 : 0;
+    // this lane's rows of the lists, as the helper holds them
+    constexpr int KH = 4, KB = 2;
+    const int ta = lane >> 3, tb = lane & 7;
+    int hac[TR][KH], hbc[TR][KB];
+    double hav[TR][KH], hbv[TR][KB];
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { d1 &= __shfl_xor(d1, off); d2 &= __shfl_xor(d2, off); }
-  auto bit_range = [](int lo, int hi) -> unsigned long long {            // bits lo … hi, hi ≤ 63
-    return hi < lo ? 0ull : ((hi >= 63 ? ~0ull : ((1ull << (hi + 1)) - 1)) & ~((1ull << lo) - 1));
-  };
-  unsigned long long bits[2];
-  bits[0] = d1 & (d1 << 1) & bit_range(2, min(T - 1, 63));
-  bits[1] = d2 & d1 & bit_range(2, min(T - 2, 63));
-  if (lane == 0) {
-    reinterpret_cast<unsigned long long*>(rec)[0] = bits[0];
-    reinterpret_cast<unsigned long long*>(rec)[1] = bits[1];
-    int32_t* cnt = reinterpret_cast<int32_t*>(rec + 16);
-    cnt[0] = a0; cnt[1] = a1; cnt[2] = a2; cnt[3] = a3;
+    for (int ri = 0; ri < TR; ++ri) {
+      const int i = ta + 8 * ri;
+#pragma unroll
+      for (int e = 0; e < KH; ++e) { const bool ok = e < capA; hac[ri][e] = ok ? arow_c[e * NPL + i] : 0; hav[ri][e] = ok ? arow_v[e * NPL + i] : 0.0; }
+#pragma unroll
+      for (int e = 0; e < KB; ++e) { const bool ok = e < capB; hbc[ri][e] = ok ? brow_c[e * NPL + i] : 0; hbv[ri][e] = ok ? brow_v[e * NPL + i] : 0.0; }
+    }
+    const double GA[KH][TR][TR] = {}, GB[KB][TR][TR] = {};      // (not read: the gathers come from the LDS images)
+    double* col = p.t4_static + (int64_t)blockIdx.x * p.t4_static_stride;
+    int turn = 0;
+    for (int slot = 0; slot <= T; ++slot) {
+      if (!twisted4_slot_read(slot, T, c, up, down)) continue;
+      if ((turn++ & 3) != wv) continue;
+      const int k = slot == 0 ? 1 : slot;
+      double Sw[TT];
+      twisted4_static_block<TR, false, KH, KB, NPL, LDT>(Sw, delta, wxt + k * NPL, wxt + (k - 1) * NPL, wut + (k - 1) * MC, slot == 0,
+                                                         ta, tb, nzA, nzB, MC, hac, hav, hbc, hbv, GA, GB,
+                                                         arow_c, arow_v, brow_c, brow_v, Ad, Bd);
+      double* dst = col + (int64_t)slot * (TQ * 64) + lane;
+      int q = 0;
+#pragma unroll
+      for (int ri = 0; ri < TR; ++ri) {
+#pragma unroll
+        for (int cj = ri; cj < TR; ++cj) dst[64 * q++] = Sw[ri * TR + cj];
+      }
+    }
   }
 }
 
-hipError_t launch_twisted4_prepare(const KernelParams& p, unsigned char* pool, hipStream_t st) {
-  if (p.nsub <= 0) return hipSuccess;
-  hipLaunchKernelGGL(twisted4_prepare_kernel, dim3(p.nsub), dim3(64), 0, st, p, pool);
+// dynamic LDS of twisted4_prepare_kernel<TR> with a pool: Ã and B̃ images, the two weight tables, hx, hu (less than the solve kernel's)
+static inline size_t twisted4_prepare_lds_bytes(int TR, int T, int mcap) {
+  return sizeof(double) * ((size_t)8 * TR * 40 + (size_t)32 * mcap + (size_t)(T + 1) * 32 + (size_t)T * mcap + 32 + 64);
+}
+
+template <int TR>
+static hipError_t launch_one_twisted4_prepare(const KernelParams& p, unsigned char* pool, size_t lds, hipStream_t st) {
+  if (lds > 32768) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&twisted4_prepare_kernel<TR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((twisted4_prepare_kernel<TR>), dim3(p.nsub), dim3(TR > 0 ? 256 : 64), lds, st, p, pool);
   return hipGetLastError();
+}
+
+// cls: the launch's size class (2 … 5); p.t4_static / p.t4_static_stride: the launch's part of the pool, or NULL for none
+hipError_t launch_twisted4_prepare(int cls, const KernelParams& p, unsigned char* pool, hipStream_t st) {
+  if (p.nsub <= 0) return hipSuccess;
+  if (p.t4_static == nullptr) return launch_one_twisted4_prepare<0>(p, pool, 0, st);      // one wave: the symbolic part alone
+  const int TR = twisted4_tile_rows(cls);
+  const size_t lds = twisted4_prepare_lds_bytes(TR, p.T, p.w_mcap);
+  return TR == 3 ? launch_one_twisted4_prepare<3>(p, pool, lds, st) : launch_one_twisted4_prepare<4>(p, pool, lds, st);
 }
 
 template <int NPL, int RPL>
 static hipError_t launch_one_twisted4(const KernelParams& p, int grid, size_t lds, hipStream_t st) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&h2_column_twisted4_kernel<NPL, RPL>),
+  if (p.t4_static == nullptr) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&h2_column_twisted4_kernel<NPL, RPL, false>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((h2_column_twisted4_kernel<NPL, RPL, false>), dim3(grid), dim3(256), lds, st, p);
+    return hipGetLastError();
+  }
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&h2_column_twisted4_kernel<NPL, RPL, true>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((h2_column_twisted4_kernel<NPL, RPL>), dim3(grid), dim3(256), lds, st, p);
+  hipLaunchKernelGGL((h2_column_twisted4_kernel<NPL, RPL, true>), dim3(grid), dim3(256), lds, st, p);
   return hipGetLastError();
 }
 

@@ -324,6 +324,25 @@ class Plan:
             o += int(cap) * w
         return out
 
+    def twisted4_static(self):
+        """sls_plan_debug_twisted4_static: the plan-time static blocks of the plan's four-wave columns, in col_status order, as a
+        dict — `delta` [n], `valid` [n, T + 1] (uint8: slots the prepare kernel filled) and `blocks`, a list of n arrays
+        [T + 1, TQ, 64] (slot, stored tile q, lane; layout: include/sls_mi355x_debug.h).  Raises SLSError when the plan has no
+        four-wave launch or keeps no pool."""
+        f = self._lib.sls_plan_debug_twisted4_static
+        i32p, i64p, dp, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        n = C.c_int64(); ns = C.c_int32()
+        _capi.check(f(self.handle, C.byref(n), C.byref(ns), None, None, None, None), self.ctx.handle)
+        n, ns = n.value, ns.value
+        off = np.zeros(n + 1, dtype=np.int64)
+        _capi.check(f(self.handle, C.byref(C.c_int64()), None, off.ctypes.data_as(i64p), None, None, None), self.ctx.handle)
+        delta = np.zeros(n, dtype=np.float64); valid = np.zeros((n, ns), dtype=np.uint8)
+        blocks = np.zeros(max(int(off[-1]), 1), dtype=np.float64)
+        _capi.check(f(self.handle, C.byref(C.c_int64()), None, None, delta.ctypes.data_as(dp), valid.ctypes.data_as(u8p),
+                      blocks.ctypes.data_as(dp)), self.ctx.handle)
+        return {"delta": delta, "valid": valid,
+                "blocks": [blocks[off[i]:off[i + 1]].reshape(ns, -1, 64).copy() for i in range(n)]}
+
     def kernel_time_ms(self):
         avg = C.c_double(); n = C.c_int64()
         _capi.check(self._lib.sls_plan_kernel_time_ms(self.handle, C.byref(avg), C.byref(n)), self.ctx.handle)

@@ -44,8 +44,9 @@ def compile_listing(defines):
     return text
 
 
-def kernel_body(text, rpl):
-    sym = f"_ZN3sls25h2_column_twisted4_kernelILi32ELi{rpl}EEEvNS_12KernelParamsE"
+def kernel_body(text, rpl, pre=1):
+    """pre = 1: the instantiation that reads the plan-time static blocks, 0: the one that rebuilds them in the launch"""
+    sym = f"_ZN3sls25h2_column_twisted4_kernelILi32ELi{rpl}ELb{pre}EEEvNS_12KernelParamsE"
     beg = text.index(f"\n{sym}:")
     end = text.index(".Lfunc_end", beg)
     res = {}
@@ -95,9 +96,9 @@ def main(argv):
         else:
             rpls.append(int(argv[i])); i += 1
     text = compile_listing(defines)
-    for rpl in rpls or [10, 12]:
-        body, res = kernel_body(text, rpl)
-        print(f"twisted4<32,{rpl}>: {res['num_vgpr']} VGPRs + {res['num_agpr']} AGPRs, scratch {res['scratch']} B/lane")
+    for rpl, pre in [(r, q) for r in (rpls or [10, 12]) for q in (1, 0)]:
+        body, res = kernel_body(text, rpl, pre)
+        print(f"twisted4<32,{rpl}> ({'plan-time blocks' if pre else 'rebuild'}): {res['num_vgpr']} VGPRs + {res['num_agpr']} AGPRs, scratch {res['scratch']} B/lane")
         for mark in ("chain-pivot", "helper-pivot"):
             sp = spans(body, mark)
             if not sp:
