@@ -353,6 +353,36 @@ int  sls_plan_clear_dirty(sls_plan* plan, void* hip_stream);
 int  sls_plan_objective(sls_plan* plan, void* hip_stream, const double* d_values, int packed,
                         double* d_col_objective, double* d_total);
 int  sls_plan_fetch_objective(sls_plan* plan, const double* d_values, int packed, double* col_objective, double* total);
+/* ---- achievability residual of every column against the FULL plant, evaluated on the device from the written Φ -------------
+ * sls_plan_fetch_status reports ‖Ez − f‖∞ of the reduced problem: the constraints restricted to the rows of s_x.  This is the
+ * defect of the system-level identities Φx[1] = I, Φx[t+1] = A·Φx[t] + B2·Φu[t], 0 = A·Φx[T] + B2·Φu[T] on ALL rows of the plant,
+ * per subproblem (global column c, 0-based t), against the values of A and B2 the plan holds NOW (sls_plan_update_plant):
+ *     Δ[0] = Φx[0][:,c] − e_c,   Δ[t+1] = Φx[t+1][:,c] − A·Φx[t][:,c] − B2·Φu[t][:,c]  (t = 0 … T−2),
+ *     Δ[T] = −A·Φx[T−1][:,c] − B2·Φu[T−1][:,c].
+ * Φ is read through the subproblem's mask and destination table, like sls_plan_objective (a stored-false mask entry reads as
+ * 0.0).  Rows of s_x are the LOCAL part; the HALO H(q) is the set of rows r ∉ s_x with A[r,j] stored for some j ∈ s_x or B2[r,k]
+ * stored for some k ∈ s_u (by pattern, like the index sets) — rows the reduced problem never constrained: a mask wider at an
+ * earlier step than at the last, or an actuator whose B2 column leaves s_x, puts a defect there that the status cannot show.
+ * Row c belongs to H(q) when c ∉ s_x, so a SLS_COL_TRIVIAL column (Φ = 0) reports 1.0: against the full system that is its defect.
+ * Per subproblem, in col_status order (a coupled or multi-column group reports one value per column, each a column of Φ):
+ *     res_inf  = max |Δ[t][r]| over local and halo rows;   halo_inf = the same over halo rows only (exactly 0.0: H(q) empty);
+ *     res_l1   = Σ_t Σ_r |Δ[t][r]|;
+ * totals[0] = max res_inf, totals[1] = max res_l1 — the 𝓔₁ norm of Δ; robust SLS needs it below 1 to use the Φ of infeasible
+ * (least-squares) columns.  Both objectives.  A NaN in Φ gives +inf.  Bit-identical from call to call and between the two
+ * layouts (fixed summation order, no floating-point atomics).  A read-only pass of its own (csrc/sls_residual.hip): it reports
+ * whatever was written last, an attached refinement included; a shard plan reports its own subproblems.  Plans of
+ * sls_h2_sf_plan_localized are supported.  SLS_EINVAL for a NULL d_values.
+ * sls_plan_residual: enqueue on hip_stream behind whatever wrote d_values and whatever sls_plan_update_plant enqueued there
+ *   (layout `packed` as in sls_plan_execute); DEVICE outputs d_res_inf / d_halo_inf / d_res_l1 [n_subproblems] and d_totals[2],
+ *   each may be NULL.  Asynchronous like sls_plan_execute, EXCEPT on first use per plan: the halo lists are built once on the host
+ *   from the plan's index sets (read back from the device) and uploaded — synchronous copies; their buffers are the feature's
+ *   own and not part of workspace_bytes.
+ * sls_plan_fetch_residual: the same on the plan's stream (which first waits for the plan's last execute AND last update) into
+ *   plan-owned buffers, waits, copies to the HOST arrays res_inf / halo_inf / res_l1 [n_subproblems] / totals[2] (each nullable). */
+int  sls_plan_residual(sls_plan* plan, void* hip_stream, const double* d_values, int packed,
+                       double* d_res_inf, double* d_halo_inf, double* d_res_l1, double* d_totals);
+int  sls_plan_fetch_residual(sls_plan* plan, const double* d_values, int packed,
+                             double* res_inf, double* halo_inf, double* res_l1, double* totals);
 /* One-shot calls: opt in per context (default off: the one-shot calls do exactly what they do today).  With the option on,
  * sls_h2_sf_solve, sls_h2_sf_solve_batch (composite order: plant 0's columns, then plant 1's, …) and
  * sls_h2_sf_solve_localized evaluate on each device after the last launch (refinement included) and before the download.

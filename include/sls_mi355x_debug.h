@@ -82,6 +82,19 @@ int sls_debug_objective_host(const sls_dims* dims, const sls_plant* P, const sls
                              const double* ridge_u, const double* const* phix_vals, const double* const* phiu_vals,
                              double* col_objective, double* total, int64_t* col_terms, double* col_abs);
 
+/* Host twin of sls_plan_residual (csrc/sls_residual.cpp): the host symbolic pass with explicit tables over all groups, then
+ * the same formulas from HOST value arrays (phix_vals[t] / phiu_vals[t] as sls_h2_sf_solve fills them) against P's A and B2 in
+ * one serial loop, accumulated in long double.  Needs no device.  Outputs, each nullable, [n_subproblems] in col_status order
+ * unless noted: res_inf, halo_inf, res_l1, totals[2]; what a summation-order bound 2·N·2⁻⁵³·S needs — ent_terms / ent_abs: the
+ * largest N and the largest S over the entries Δ[t][r] of the column (bounds res_inf and halo_inf), l1_terms / l1_abs: N and S
+ * of res_l1; halo_ptr[n_subproblems + 1] and halo_rows[halo_ptr[n_subproblems]] (halo_cap: its capacity; 0-based, ascending per
+ * subproblem): H(q).  Call with halo_rows = NULL first for the length. */
+int sls_debug_residual_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                            int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, const double* const* phix_vals,
+                            const double* const* phiu_vals, double* res_inf, double* halo_inf, double* res_l1, double* totals,
+                            int64_t* ent_terms, double* ent_abs, int64_t* l1_terms, double* l1_abs, int64_t* halo_ptr,
+                            int32_t* halo_rows, int64_t halo_cap);
+
 /* Host twin of sls_plan_update_plant (csrc/sls_symbolic.cpp: apply_operator_update): the four operator value arrays a plan of
  * (A, B2) holds — A_val / B_val in row order, At_val / Bt_val in the CSC order — after an update with A_nzval / B2_nzval
  * (either NULL = unchanged), plus the value map row_pos[nnz(A) + nnz(B2)] and the plan-time-zero marks.  Needs no device.

@@ -11,7 +11,7 @@
 module SLSMI355X
 
 using SparseArrays
-export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, track_changes!, execute_dirty!
+export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, track_changes!, execute_dirty!, residual
 
 const LIB = get(ENV, "SLS_MI355X_LIB", "libsls_mi355x.so")
 
@@ -114,6 +114,24 @@ function update_plant!(plan::Ptr{Cvoid}, A, B2; stream::Ptr{Cvoid}=C_NULL, wait:
     rc = ccall((:sls_plan_update_result, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), plan, n)
     rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
     return n[]
+end
+
+"""
+    r = residual(plan, d_values, nsub; packed=false)
+
+`sls_plan_fetch_residual` on a resident plan (a `Ptr{Cvoid}` from `sls_h2_sf_plan`, `nsub` = its `n_subproblems`): the defect of
+`Φₓ[1] = I`, `Φₓ[t+1] = A Φₓ[t] + B₂ Φᵤ[t]`, `0 = A Φₓ[T] + B₂ Φᵤ[T]` on ALL rows of the plant, per subproblem, evaluated on the
+device from the value array `d_values` and the values of `A`, `B₂` the plan holds now (after `update_plant!`: the new ones, whether
+or not the columns were solved again).  Returns a named tuple: `res_inf` (max |Δ| over the rows of s_x and the halo rows outside
+it), `halo_inf` (the halo rows alone), `res_l1` (Σ|Δ|), each of length `nsub`, and `max_inf`, `e1_norm` = their maxima over the
+subproblems — the latter is the 𝓔₁ norm robust SLS needs below 1.  Waits for the plan's last execute and last update.
+"""
+function residual(plan::Ptr{Cvoid}, d_values::Ptr{Cvoid}, nsub::Integer; packed::Bool=false)
+    res_inf = zeros(Float64, nsub);  halo_inf = zeros(Float64, nsub);  res_l1 = zeros(Float64, nsub);  totals = zeros(Float64, 2)
+    rc = ccall((:sls_plan_fetch_residual, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+               plan, d_values, packed ? 1 : 0, res_inf, halo_inf, res_l1, totals)
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    return (res_inf=res_inf, halo_inf=halo_inf, res_l1=res_l1, max_inf=totals[1], e1_norm=totals[2])
 end
 
 """

@@ -89,6 +89,7 @@ EXPORTS = [
     "sls_plan_objective", "sls_plan_fetch_objective", "sls_ctx_want_objective", "sls_ctx_last_objective",
     "sls_plan_update_plant", "sls_plan_update_result", "sls_plan_fetch_plant",
     "sls_plan_execute_columns", "sls_plan_track_changes", "sls_plan_execute_dirty", "sls_plan_fetch_dirty", "sls_plan_clear_dirty",
+    "sls_plan_residual", "sls_plan_fetch_residual",
 ]
 
 _lib = None
@@ -190,7 +191,11 @@ def load_library(path: str | None = None):
     lib.sls_plan_execute_dirty.restype = C.c_int; lib.sls_plan_execute_dirty.argtypes = [vp, vp, vp, C.c_int, i64p]
     lib.sls_plan_fetch_dirty.restype = C.c_int; lib.sls_plan_fetch_dirty.argtypes = [vp, u8p]
     lib.sls_plan_clear_dirty.restype = C.c_int; lib.sls_plan_clear_dirty.argtypes = [vp, vp]
+    lib.sls_plan_residual.restype = C.c_int; lib.sls_plan_residual.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    lib.sls_plan_fetch_residual.restype = C.c_int; lib.sls_plan_fetch_residual.argtypes = [vp, vp, C.c_int, dp, dp, dp, dp]
     # diagnostics outside the public header
+    lib.sls_debug_residual_host.restype = C.c_int
+    lib.sls_debug_residual_host.argtypes = common + [dpp, dpp, dp, dp, dp, dp, i64p, dp, i64p, dp, i64p, i32p, C.c_int64]
     lib.sls_debug_objective_host.restype = C.c_int
     lib.sls_debug_objective_host.argtypes = common + [dp, dp, dpp, dpp, dp, dp, i64p, dp]
     lib.sls_debug_operator_update_host.restype = C.c_int

@@ -25,6 +25,7 @@
 #include "sls_device.h"
 #include "sls_internal.h"
 #include "sls_objective.h"
+#include "sls_residual.h"
 #include "sls_routing.h"
 #include "sls_symbolic.h"
 
@@ -45,6 +46,7 @@ hipError_t launch_column_tables(const ColumnTableParams& p, bool fill, int grid,
 hipError_t launch_level_prefix(const int32_t* cntx, const int32_t* cntu, int Nx, int K1, int64_t* prex, int64_t* preu, int64_t* totx,
                                int64_t* totu, hipStream_t stream);
 hipError_t launch_objective(const ObjectiveParams& p, int lds_doubles, double* d_total, hipStream_t stream);
+hipError_t launch_residual(const ResidualParams& p, double* d_totals, hipStream_t stream);
 hipError_t launch_tile_invert(const double* d_A, int n, double* d_ws, double* d_out, bool mlds, hipStream_t stream);
 hipError_t launch_operator_update(const OperatorUpdateParams& p, hipStream_t stream);
 }  // namespace sls
@@ -171,6 +173,16 @@ struct sls_plan {
     std::vector<int32_t> h_count;
     std::vector<uint8_t> h_marks;
   } part;
+  // achievability residual (sls_plan_residual): the halo lists, the subproblems' global columns and the plan-owned
+  // result buffer of sls_plan_fetch_residual (three arrays of n_subproblems values, then the two totals) — one device allocation
+  // made by the first call (residual_ensure), not counted in workspace_bytes
+  struct Residual {
+    bool ready = false;
+    const int32_t* sub_col = nullptr;
+    const int64_t* halo_ptr = nullptr;
+    const int32_t* halo_rows = nullptr;
+    double* out = nullptr;            // [3 · nsub + 2]
+  } resid;
 };
 
 namespace {
@@ -1910,6 +1922,134 @@ int sls_debug_objective_host(const sls_dims* dims, const sls_plant* P, const sls
   }
   rc = objective_host(S, (dims->flags & SLS_SOLVE_SUM_OF_NORMS) ? 1 : 0, vals.data(), col_objective, total, col_terms, col_abs, msg);
   if (rc) return fail(nullptr, rc, msg);
+  return 0;
+}
+
+// ---- achievability residual against the full plant: sls_plan_residual, sls_plan_fetch_residual ----
+
+// The device buffers of the residual pass, made by the first call that needs them.  The halo H(q) follows from the index sets
+// and the CSC halves of the operator's pattern (build_halo_rows); the host copy of the index sets is gone after plan creation
+// (and never existed for sls_h2_sf_plan_localized), so they are read back from the device once — a host wait, first use only.
+static int residual_ensure(sls_plan* plan) {
+  sls_plan::Residual& rs = plan->resid;
+  if (rs.ready) return 0;
+  const Symbolic& S = plan->sym;
+  const size_t ns = (size_t)plan->kp.nsub;
+  if (S.subs.size() != ns || S.sub_col.size() != ns) return fail(plan->ctx, SLS_EUNSUPPORTED, "sls_plan_residual: this plan keeps no column list");
+  int64_t nidx = 0;
+  for (const SubDesc& sd : S.subs) nidx = std::max<int64_t>(nidx, std::max(sd.off_sx + sd.n, sd.off_su + sd.m));
+  std::vector<int32_t> idx((size_t)std::max<int64_t>(nidx, 1), 0);
+  if (nidx > 0) HIPCHK(plan->ctx, hipMemcpy(idx.data(), plan->kp.idx_pool, (size_t)nidx * sizeof(int32_t), hipMemcpyDeviceToHost));
+  std::vector<int64_t> hp;
+  std::vector<int32_t> hr;
+  build_halo_rows(S.At_csr, S.Bt_csr, S.subs.data(), (int64_t)ns, idx.data(), S.sub_col.data(), hp, hr);
+  auto al = [](size_t b) { return (std::max<size_t>(b, 16) + 255) / 256 * 256; };
+  const size_t o_col = 0, o_ptr = o_col + al(4 * ns), o_rows = o_ptr + al(8 * (ns + 1)), o_out = o_rows + al(4 * hr.size()),
+               total = o_out + al(8 * (3 * ns + 2));
+  unsigned char* base = nullptr;
+  HIPCHK(plan->ctx, hipMalloc(reinterpret_cast<void**>(&base), total));
+  plan->dev_allocs.push_back(base);
+  HIPCHK(plan->ctx, hipMemcpy(base + o_col, S.sub_col.data(), 4 * ns, hipMemcpyHostToDevice));
+  HIPCHK(plan->ctx, hipMemcpy(base + o_ptr, hp.data(), 8 * (ns + 1), hipMemcpyHostToDevice));
+  if (!hr.empty()) HIPCHK(plan->ctx, hipMemcpy(base + o_rows, hr.data(), 4 * hr.size(), hipMemcpyHostToDevice));
+  rs.sub_col = reinterpret_cast<const int32_t*>(base + o_col);
+  rs.halo_ptr = reinterpret_cast<const int64_t*>(base + o_ptr);
+  rs.halo_rows = reinterpret_cast<const int32_t*>(base + o_rows);
+  rs.out = reinterpret_cast<double*>(base + o_out);
+  rs.ready = true;
+  return 0;
+}
+
+int sls_plan_residual(sls_plan* plan, void* hip_stream, const double* d_values, int packed, double* d_res_inf, double* d_halo_inf,
+                      double* d_res_l1, double* d_totals) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  if (!d_values) return fail(plan->ctx, SLS_EINVAL, "null device value pointer");
+  if (packed && !plan->d_pdest) return fail(plan->ctx, SLS_EINVAL, "this plan was built without the packed layout");
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  if (plan->kp.nsub == 0) {
+    if (d_totals) HIPCHK(plan->ctx, hipMemsetAsync(d_totals, 0, 2 * sizeof(double), st));
+    return 0;
+  }
+  if (int rc = residual_ensure(plan)) return rc;
+  const KernelParams& kp = plan->kp;
+  const size_t n = (size_t)kp.nsub;
+  ResidualParams rp{};
+  rp.subs = kp.subs; rp.nsub = kp.nsub; rp.T = kp.T;
+  rp.idx_pool = kp.idx_pool; rp.mask_pool = kp.mask_pool; rp.dest = packed ? plan->d_pdest : plan->d_dest;
+  rp.A_rowptr = kp.A_rowptr; rp.A_colidx = kp.A_colidx; rp.A_val = kp.A_val;
+  rp.B_rowptr = kp.B_rowptr; rp.B_colidx = kp.B_colidx; rp.B_val = kp.B_val;
+  rp.sub_col = plan->resid.sub_col; rp.halo_ptr = plan->resid.halo_ptr; rp.halo_rows = plan->resid.halo_rows;
+  rp.values = d_values;
+  rp.res_inf = d_res_inf ? d_res_inf : plan->resid.out;
+  rp.halo_inf = d_halo_inf ? d_halo_inf : plan->resid.out + n;
+  rp.res_l1 = d_res_l1 ? d_res_l1 : plan->resid.out + 2 * n;
+  hipError_t e = launch_residual(rp, d_totals, st);
+  if (e != hipSuccess) return hipfail(plan->ctx, e, "launch residual kernels");
+  return 0;
+}
+
+int sls_plan_fetch_residual(sls_plan* plan, const double* d_values, int packed, double* res_inf, double* halo_inf, double* res_l1,
+                            double* totals) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  if (!d_values) return fail(plan->ctx, SLS_EINVAL, "null device value pointer");
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  const size_t n = (size_t)plan->kp.nsub;
+  if (n == 0) { if (totals) totals[0] = totals[1] = 0.0; return 0; }
+  hipStream_t st = plan->stream;
+  // the execute that wrote d_values and the update that wrote the operator may have run on other streams
+  if (plan->last_done) HIPCHK(plan->ctx, hipStreamWaitEvent(st, plan->last_done, 0));
+  if (plan->upd_recorded) HIPCHK(plan->ctx, hipStreamWaitEvent(st, plan->ev_upd, 0));
+  if (int rc = residual_ensure(plan)) return rc;
+  double* out = plan->resid.out;
+  if (int rc = sls_plan_residual(plan, st, d_values, packed, out, out + n, out + 2 * n, out + 3 * n)) return rc;
+  const size_t bytes = (3 * n + 2) * sizeof(double);
+  std::vector<double> stage_v;
+  double* stage = reinterpret_cast<double*>(slot_pinned(plan->ctx, plan->slot, bytes));
+  if (!stage) { stage_v.resize(3 * n + 2); stage = stage_v.data(); }
+  HIPCHK(plan->ctx, hipMemcpyAsync(stage, out, bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(plan->ctx, hipStreamSynchronize(st));
+  if (res_inf) std::memcpy(res_inf, stage, n * sizeof(double));
+  if (halo_inf) std::memcpy(halo_inf, stage + n, n * sizeof(double));
+  if (res_l1) std::memcpy(res_l1, stage + 2 * n, n * sizeof(double));
+  if (totals) std::memcpy(totals, stage + 3 * n, 2 * sizeof(double));
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): the host twin of sls_plan_residual — symbolic pass with explicit tables, then the
+   same formulas from host arrays in one serial loop (csrc/sls_residual.cpp).  Needs no device. */
+int sls_debug_residual_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                            int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, const double* const* phix_vals,
+                            const double* const* phiu_vals, double* res_inf, double* halo_inf, double* res_l1, double* totals,
+                            int64_t* ent_terms, double* ent_abs, int64_t* l1_terms, double* l1_abs, int64_t* halo_ptr,
+                            int32_t* halo_rows, int64_t halo_cap) {
+  Inputs in{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
+  std::string msg;
+  int rc = validate_inputs(in, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  if (!phix_vals || !phiu_vals) return fail(nullptr, SLS_EINVAL, "null value arrays");
+  Symbolic S;
+  S.want_packed = false; S.compact = false;
+  std::vector<int64_t> gptr, gcols;
+  normalise_groups(in, gptr, gcols);
+  rc = build_symbolic(in, 0, (int64_t)gptr.size() - 1, S, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  std::vector<double> vals((size_t)std::max<int64_t>(S.n_values, 1), 0.0);
+  for (int64_t t = 0; t < S.T; ++t) {
+    const int64_t nx = S.off_x[t + 1] - S.off_x[t], nu = S.off_u[t + 1] - S.off_u[t];
+    if ((nx > 0 && !phix_vals[t]) || (nu > 0 && !phiu_vals[t])) return fail(nullptr, SLS_EINVAL, "null phix_vals[t]/phiu_vals[t]");
+    if (nx > 0) std::copy(phix_vals[t], phix_vals[t] + nx, vals.begin() + S.off_x[t]);
+    if (nu > 0) std::copy(phiu_vals[t], phiu_vals[t] + nu, vals.begin() + S.off_u[t]);
+  }
+  std::vector<int64_t> hp;
+  std::vector<int32_t> hr;
+  rc = residual_host(S, vals.data(), res_inf, halo_inf, res_l1, totals, ent_terms, ent_abs, l1_terms, l1_abs, &hp, &hr, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  if (halo_ptr) std::copy(hp.begin(), hp.end(), halo_ptr);
+  if (halo_rows) {
+    if (halo_cap < (int64_t)hr.size()) return fail(nullptr, SLS_EINVAL, "sls_debug_residual_host: halo_rows is shorter than halo_ptr[n_subproblems]");
+    std::copy(hr.begin(), hr.end(), halo_rows);
+  }
   return 0;
 }
 

@@ -228,6 +228,30 @@ int mark_affected_host(const Symbolic& S, const OperatorValueMap& M, const uint8
   return 0;
 }
 
+void build_halo_rows(const HostCsr& At, const HostCsr& Bt, const SubDesc* subs, int64_t nsub, const int32_t* idx_pool,
+                     const int32_t* sub_col, std::vector<int64_t>& halo_ptr, std::vector<int32_t>& halo_rows) {
+  halo_ptr.assign((size_t)nsub + 1, 0);
+  halo_rows.clear();
+  std::vector<int32_t> rows;
+  for (int64_t q = 0; q < nsub; ++q) {
+    const SubDesc& sd = subs[q];
+    const int32_t* sx = idx_pool + sd.off_sx;
+    const int32_t* su = idx_pool + sd.off_su;
+    rows.clear();
+    // column j of A is row j of At_csr: its stored rows, whatever their values (by pattern, like the index sets)
+    for (int32_t i = 0; i < sd.n; ++i)
+      for (int32_t e = At.ptr[(size_t)sx[i]]; e < At.ptr[(size_t)sx[i] + 1]; ++e) rows.push_back(At.idx[(size_t)e]);
+    for (int32_t k = 0; k < sd.m; ++k)
+      for (int32_t e = Bt.ptr[(size_t)su[k]]; e < Bt.ptr[(size_t)su[k] + 1]; ++e) rows.push_back(Bt.idx[(size_t)e]);
+    rows.push_back(sub_col[sd.out_index]);      // the impulse row: part of the halo when the column lies outside its own s_x
+    std::sort(rows.begin(), rows.end());
+    rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+    for (int32_t r : rows)
+      if (!std::binary_search(sx, sx + sd.n, r)) halo_rows.push_back(r);
+    halo_ptr[(size_t)q + 1] = (int64_t)halo_rows.size();
+  }
+}
+
 int validate_inputs(const Inputs& in, std::string& msg) {
   if (!in.dims || !in.P) { msg = "null dims/plant"; return SLS_EINVAL; }
   const sls_dims& d = *in.dims;

@@ -192,6 +192,14 @@ int apply_operator_update(Symbolic& S, const OperatorValueMap& M, const double* 
 int mark_affected_host(const Symbolic& S, const OperatorValueMap& M, const uint8_t* changed_A, const uint8_t* changed_B2, uint8_t* dirty,
                        std::string& msg);
 
+// ---- achievability residual (sls_residual.h): the halo H(q) of every subproblem ----
+// H(q) = rows r ∉ s_x that A·Φx[t][:,c] + B2·Φu[t][:,c] can reach: A[r,j] stored for some j ∈ s_x or B2[r,k] stored for some
+// k ∈ s_u — by pattern, like the index sets — plus the column's own row c when c ∉ s_x (the impulse of Δ[0]).  At / Bt: the CSC
+// halves of the operator (At_csr, Bt_csr; only ptr and idx are read), sub_col by out_index.  Subproblem q's rows are
+// halo_rows[halo_ptr[q] .. halo_ptr[q + 1]), ascending.
+void build_halo_rows(const HostCsr& At, const HostCsr& Bt, const SubDesc* subs, int64_t nsub, const int32_t* idx_pool,
+                     const int32_t* sub_col, std::vector<int64_t>& halo_ptr, std::vector<int32_t>& halo_rows);
+
 // predicted cost per group (Σ over its columns of (T+1)·ñx³)
 int group_costs(const Inputs& in, std::vector<double>& cost, std::string& msg);
 

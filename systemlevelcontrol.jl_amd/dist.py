@@ -289,6 +289,30 @@ class ColumnShardedH2:
             return colv, float(tot.item())
         return col.cpu().numpy(), float(tot.item())
 
+    def residual(self):
+        """`synthesis.Residual` of the last `step` against the full plant (Plan.residual_async): every rank evaluates its own
+        shard on the device, from the array its solve wrote, and reports its own subproblems' `res_inf`, `halo_inf`, `res_l1`;
+        the two totals (`max_inf`, `e1_norm`) are one all_reduce(MAX) of two doubles, so every rank holds the values of the
+        whole Φ.  After `step_async`, call `flush()` first."""
+        from .synthesis import Residual
+        torch = self.torch
+        if not hasattr(self.local, "plan"):
+            raise RuntimeError("residual needs the HIP local solver (a device plan)")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self._direct():
+            ri, hi, l1, tot = self.local.plan.residual_async(self.values.data_ptr(), packed=False, stream=stream)
+        else:
+            src = self.packed if self._pipe is None else self._pipe["packed"][(self._pipe["k"] - 1) & 1]
+            ri, hi, l1, tot = self.local.plan.residual_async(src.data_ptr(), packed=True, stream=stream)
+        if self.world > 1:
+            if self.dist.get_backend(self.pg) == "gloo":          # tests only: a gloo group cannot move device memory
+                torch.cuda.current_stream(self.device).synchronize()
+                ht = tot.cpu(); self.dist.all_reduce(ht, op=self.dist.ReduceOp.MAX, group=self.pg); tot = ht
+            else:
+                self.dist.all_reduce(tot, op=self.dist.ReduceOp.MAX, group=self.pg)
+        tot = tot.cpu().numpy()
+        return Residual(ri.cpu().numpy(), hi.cpu().numpy(), l1.cpu().numpy(), float(tot[0]), float(tot[1]))
+
     def flush(self):
         """Make the current stream wait for everything `step_async` has in flight."""
         if self._pipe is not None:

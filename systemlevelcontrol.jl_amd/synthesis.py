@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import sys
+import typing
 import warnings
 
 import numpy as np
@@ -296,6 +297,38 @@ class Plan:
                     self.ctx.handle)
         return col[: self.info["n_subproblems"]], tot
 
+    def residual(self, d_values, packed=False, stream=None):
+        """`Residual` record of the achievability residual of every subproblem of this plan against the FULL plant, evaluated
+        on the device from the value array `d_values` (layout `packed` as in `execute`) and the values of A and B2 the plan
+        holds now (sls_plan_fetch_residual; definition: include/sls_mi355x.h).  Waits for the plan's last execute
+        and last `update_plant`.  With `stream` the evaluation is enqueued there instead (sls_plan_residual, behind what the
+        caller put on it) and that stream is waited for."""
+        n = self.info["n_subproblems"]
+        dp = C.POINTER(C.c_double)
+        if stream is not None:
+            ri, hi, l1, tot = self.residual_async(d_values, packed=packed, stream=stream)
+            self.synchronize(stream)
+            tot = tot.cpu().numpy()
+            return Residual(ri.cpu().numpy(), hi.cpu().numpy(), l1.cpu().numpy(), float(tot[0]), float(tot[1]))
+        out = [np.zeros(max(n, 1), dtype=np.float64) for _ in range(3)]
+        tot = np.zeros(2, dtype=np.float64)
+        _capi.check(self._lib.sls_plan_fetch_residual(self.handle, d_values, int(packed), *[a.ctypes.data_as(dp) for a in out],
+                                                      tot.ctypes.data_as(dp)), self.ctx.handle)
+        return Residual(out[0][:n], out[1][:n], out[2][:n], float(tot[0]), float(tot[1]))
+
+    def residual_async(self, d_values, packed=False, stream=None):
+        """sls_plan_residual into fresh torch tensors on the plan's device: (res_inf, halo_inf, res_l1 [n_subproblems],
+        totals[2] = max res_inf, max res_l1), enqueued on `stream` (None = the null stream); nothing waits for the device
+        (the plan's first call builds the halo lists on the host and does wait)."""
+        import torch
+        dev = torch.device("cuda", self.info["device"])
+        n = self.info["n_subproblems"]
+        out = [torch.empty(max(n, 1), dtype=torch.float64, device=dev) for _ in range(3)]
+        tot = torch.empty(2, dtype=torch.float64, device=dev)          # written by the call (zeroed there when the plan is empty)
+        _capi.check(self._lib.sls_plan_residual(self.handle, stream, d_values, int(packed), *[a.data_ptr() for a in out],
+                                                tot.data_ptr()), self.ctx.handle)
+        return out[0][:n], out[1][:n], out[2][:n], tot
+
     def describe(self):
         buf = C.create_string_buffer(4096)
         _capi.check(self._lib.sls_plan_describe(self.handle, buf, len(buf)))
@@ -377,6 +410,16 @@ class Plan:
             pass
 
 
+class Residual(typing.NamedTuple):
+    """What `Plan.residual` returns: per subproblem, in col_status order, `res_inf` (max |Δ| over local and halo rows), `halo_inf`
+    (the same over halo rows only) and `res_l1` (Σ|Δ|); `max_inf` = max res_inf and `e1_norm` = max res_l1, the 𝓔₁ norm of Δ."""
+    res_inf: np.ndarray
+    halo_inf: np.ndarray
+    res_l1: np.ndarray
+    max_inf: float
+    e1_norm: float
+
+
 def _torch():
     import torch
     return torch
@@ -455,6 +498,48 @@ def objective_values_host(P, S, vals_x, vals_u, I=None, *, ridge=None, objective
     if return_bound:
         return col[:n], tot.value, cn[:n], cabs[:n]
     return col[:n], tot.value
+
+
+def residual_host(P, S, vals_x, vals_u, I=None, *, index_base=0, return_bound=False, return_halo=False):
+    """Host twin of `Plan.residual` (sls_debug_residual_host; needs no device): the host symbolic pass over all groups, then the
+    same formulas from host value arrays — vals_x[t] / vals_u[t] in the masks' CSC order — against P.A and P.B2, accumulated in
+    long double.  Returns a `Residual`; with return_bound also a dict of what a summation-order bound 2·N·2⁻⁵³·S needs, per
+    column: `ent_terms` / `ent_abs` (N and S that bound every entry of Δ, hence res_inf and halo_inf) and `l1_terms` / `l1_abs`
+    (N and S of res_l1); with return_halo also the list of halo row arrays H(q) (0-based, ascending)."""
+    lib = _capi.load_library()
+    Sx, Su = S
+    m = _capi.Marshalled(P, Sx, Su, None if I is None else [list(g) for g in I], index_base=index_base)
+    T = len(Sx)
+    dp, i64p = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    vx = [np.ascontiguousarray(v, dtype=np.float64) for v in vals_x]
+    vu = [np.ascontiguousarray(v, dtype=np.float64) for v in vals_u]
+    if [v.size for v in vx] != m.nnz_x or [v.size for v in vu] != m.nnz_u:
+        raise ValueError("value arrays do not match the masks' nnz")
+    pad = np.zeros(1)
+    px = (dp * T)(*[(a if a.size else pad).ctypes.data_as(dp) for a in vx])
+    pu = (dp * T)(*[(a if a.size else pad).ctypes.data_as(dp) for a in vu])
+    n = m.n_sub
+    out = [np.zeros(max(n, 1)) for _ in range(3)]
+    tot = np.zeros(2)
+    et, lt = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64)
+    ea, la = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    hp = np.zeros(n + 1, dtype=np.int64)
+
+    def call(rows):
+        _capi.check(lib.sls_debug_residual_host(*m.common_args(), px, pu, *[a.ctypes.data_as(dp) for a in out], tot.ctypes.data_as(dp),
+                                                et.ctypes.data_as(i64p), ea.ctypes.data_as(dp), lt.ctypes.data_as(i64p),
+                                                la.ctypes.data_as(dp), hp.ctypes.data_as(i64p),
+                                                None if rows is None else rows.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                0 if rows is None else rows.size))
+    call(None)
+    res = [Residual(out[0][:n], out[1][:n], out[2][:n], float(tot[0]), float(tot[1]))]
+    if return_bound:
+        res.append({"ent_terms": et[:n], "ent_abs": ea[:n], "l1_terms": lt[:n], "l1_abs": la[:n]})
+    if return_halo:
+        rows = np.zeros(max(int(hp[n]), 1), dtype=np.int32)
+        call(rows)
+        res.append([rows[hp[q]:hp[q + 1]].copy() for q in range(n)])
+    return res[0] if len(res) == 1 else tuple(res)
 
 
 def assemble_phi(Sx, Su, vals_x, vals_u, dropzeros=True):
