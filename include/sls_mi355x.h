@@ -294,7 +294,8 @@ int  sls_plan_refine(sls_plan* plan, const sls_dims* dims, const sls_plant* P,
  * nor B2) stays correct.  Which columns are near-singular depends on the values: an update detaches and frees a refinement
  * attached by sls_plan_refine (waiting for the plan's last execute first); run sls_plan_refine again with the new plant.  Works
  * for every plan kind (sls_h2_sf_plan, sls_h2_sf_plan_localized, both objectives, either layout).  A closed-loop simulator
- * (sls_closed_loop_plan) keeps its own copy of the plant and is not updated.                                                   */
+ * (sls_closed_loop_plan) keeps its own copy of the plant; to run the new Φ against another plant than the design model, step
+ * the stand-alone controller (sls_controller_*), which holds no plant.                                                          */
 int  sls_plan_update_plant(sls_plan* plan, void* hip_stream, const double* A_nzval, const double* B2_nzval, int on_device);
 int  sls_plan_update_result(sls_plan* plan, int64_t* n_rejected);
 /* The operator values the plan holds now, as CSC nzval arrays in the plan's order (HOST outputs of nnz(A) / nnz(B2) doubles,
@@ -493,6 +494,43 @@ int  sls_closed_loop_last_ms(sls_loop* loop, double* ms);
 /* stored-true Φ entries one time step reads (12 B each: the HBM traffic model of the step kernel) */
 int  sls_closed_loop_entries(const sls_loop* loop, int64_t* n_entries);
 void sls_closed_loop_destroy(sls_loop* loop);
+
+/* ---- stand-alone controller: one step from a measured state to u (csrc/sls_controller.hip) ----
+ * What an SLS user deploys.  sls_closed_loop_* fuses the controller with ONE fixed linear plant; here the state comes from
+ * outside, so the plant may differ from the design model, be non-linear or simulated elsewhere, or be measured, and Φ may be
+ * swapped under a running controller (gain scheduling: sls_plan_update_plant, sls_plan_execute, sls_controller_load, next step).
+ * Steps are numbered k = 0, 1, … since the last reset; step k takes x_k of `nscen` scenarios and gives
+ *     ŵ_k     = x_k − β_k                                   (β_0 = 0; ŵ_j = 0 for j < 0)
+ *     u_k     = Σ_{τ=1..T}   Φu[τ]   · ŵ_{k+1−τ}
+ *     β_{k+1} = Σ_{τ=1..T−1} Φx[τ+1] · ŵ_{k+1−τ}
+ * (τ and the Φ indices 1-based as in the reference README.md:62-72; row k of the simulator's x, u arrays is step k here; a
+ * non-zero x_0 acts as a disturbance at time 0, the SLS meaning of an initial condition; Φx[1] is not part of the operator and
+ * stored-false mask entries are never read, as in the simulator).  Fed the x of a simulator run, the steps return that run's u
+ * bit for bit in rows 0 … steps−2 (the simulator's last u row is the README's never-assigned zero; the controller computes it).
+ * sls_controller_plan: masks only — Nx, Nu, T, index_base of dims are read; Sx[t] is Nx×Nx, Su[t] Nu×Nx.  nscen is fixed here
+ *   and every buffer is allocated here: the row-ordered Φ, β (two copies) and the history of ŵ (a ring of 2^⌈log₂T⌉ slots, each
+ *   stored twice); the controller starts in the reset state.  SLS_EUNSUPPORTED when (T+1)·Nx exceeds int32 (an entry's history
+ *   offset is an int32) or nscen exceeds 65535·64.
+ * sls_controller_load: d_values = Φ in the mask-order value array sls_plan_execute(packed = 0) fills (DEVICE), gathered into
+ *   row order; β, the history and the step counter are NOT touched.
+ * sls_controller_reset: β = 0, history = 0, k = 0.
+ * sls_controller_step: d_x [Nx][nscen] (DEVICE), d_u [Nu][nscen] (DEVICE, written; may be NULL when Nu = 0), d_what [Nx][nscen]
+ *   (DEVICE, written: ŵ_k) or NULL; scenario innermost, like the simulator's arrays.  One kernel launch.
+ * load, reset and step allocate nothing and never wait for the device: they enqueue on `hip_stream` (NULL = null stream) and
+ * return, like sls_plan_execute.  The step counter lives on the host and advances at enqueue; the caller issues the calls of
+ * one controller on one stream or orders them with events.  SLS_EINVAL: a step before the first load, a null d_x, a null d_u
+ * with Nu > 0, nscen < 1, a dev_slot out of range; the controller stays usable.  A step on a stream that is being captured
+ * (hipStreamIsCapturing) returns SLS_EUNSUPPORTED: the ring position is a launch argument and a graph would freeze it.
+ * sls_controller_info (each output nullable): stored-true Φ entries one step reads (12 B each), steps enqueued since the
+ * last reset, and the device bytes of β and the history (what a reset clears). */
+typedef struct sls_controller sls_controller;
+int  sls_controller_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                         int64_t nscen, sls_controller** out);
+int  sls_controller_load(sls_controller* ctl, void* hip_stream, const double* d_values);
+int  sls_controller_reset(sls_controller* ctl, void* hip_stream);
+int  sls_controller_step(sls_controller* ctl, void* hip_stream, const double* d_x, double* d_u, double* d_what);
+int  sls_controller_info(const sls_controller* ctl, int64_t* n_entries, int64_t* steps_done, int64_t* state_bytes);
+void sls_controller_destroy(sls_controller* ctl);
 
 /* Symbolic pass only (replaces reference src/reduction.jl:11-27 for one group):
  * fills s_x / s_u (index_base of dims), returns their lengths.  Pure host.           */

@@ -112,6 +112,21 @@ int sls_debug_affected_host(const sls_dims* dims, const sls_plant* P, const sls_
                             const int64_t* group_ptr, const int64_t* group_cols, const uint8_t* changed_A, const uint8_t* changed_B2,
                             uint8_t* dirty);
 
+/* The tables of the stand-alone controller (sls_controller_plan) from the masks (dims: Nx, Nu, T, index_base are read), built
+ * on the host by the routine the plan uses (csrc/sls_symbolic.cpp: build_controller_operator).  *n_entries: stored-true entries of
+ * Sx[1..T−1] and Su[0..T−1]; row_ptr[Nx + Nu + 1]: the Nx β rows, then the Nu u rows; per entry, ascending in (lag, col) inside a
+ * row: lag[e] = τ (1-based: Φx[τ+1] in a β row, Φu[τ] in a u row), col[e] (0-based), perm[e] = its index in the mask-order value
+ * array.  Every output is nullable: call with only n_entries first for the length.  Needs no device. */
+int sls_debug_controller_tables(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, int64_t* n_entries,
+                                int32_t* row_ptr, int32_t* lag, int32_t* col, int32_t* perm);
+
+/* Host twin of sls_controller_step (csrc/sls_controller.cpp): `steps` steps from the reset state in one serial loop through the
+ * same tables, the same mirrored ring and β double buffer (csrc/sls_controller.h), rows accumulated in long double and rounded
+ * to double where the device stores one.  values: Φ in mask order (HOST); x [steps][Nx][nscen] (HOST); outputs, each nullable:
+ * u [steps][Nu][nscen], what [steps][Nx][nscen] (ŵ).  Needs no device. */
+int sls_debug_controller_host(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, const double* values,
+                              int64_t nscen, int64_t steps, const double* x, double* u, double* what);
+
 #ifdef __cplusplus
 }
 #endif

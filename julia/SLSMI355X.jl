@@ -11,7 +11,7 @@
 module SLSMI355X
 
 using SparseArrays
-export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, track_changes!, execute_dirty!, residual
+export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!
 
 const LIB = get(ENV, "SLS_MI355X_LIB", "libsls_mi355x.so")
 
@@ -158,6 +158,47 @@ function execute_dirty!(plan::Ptr{Cvoid}, d_values::Ptr{Cvoid}; packed::Bool=fal
                packed ? 1 : 0, n)
     rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
     return n[]
+end
+
+"""
+    c = Controller(ctx, Nx, Nu, [𝓢ₓ,𝓢ᵤ]; nscen=1, dev_slot=0)
+    load!(c, d_values; stream=C_NULL);  reset!(c; stream=C_NULL);  step!(c, d_x, d_u; d_what=C_NULL, stream=C_NULL)
+
+`sls_controller_*`: the stand-alone controller built from the masks alone — step `k` takes the measured state `d_x` (`[Nx][nscen]`
+on the device) and writes `u_k = Σ_τ Φᵤ[τ] ŵ_{k+1−τ}` to `d_u` (`[Nu][nscen]`), with `ŵ_k = x_k − β_k` (to `d_what` when given) and
+`β_{k+1} = Σ_τ Φₓ[τ+1] ŵ_{k+1−τ}` kept inside.  No plant is involved, so the state may come from any plant or from a measurement.
+`load!` gathers Φ from the mask-order device array an execute filled and keeps β and the history; `reset!` clears them.  All three
+enqueue on `stream` and return; the calls of one controller go to one stream.  `close(c)` frees it.  NOT EXECUTED in the build
+container, like the rest of this file.
+"""
+mutable struct Controller
+    handle::Ptr{Cvoid}
+    Nx::Int; Nu::Int; nscen::Int
+end
+function Controller(ctx::Ptr{Cvoid}, Nx::Integer, Nu::Integer, 𝓢::AbstractVector; nscen::Integer=1, dev_slot::Integer=0)
+    𝓢ₓ, 𝓢ᵤ = 𝓢
+    Sx = [SparseMatrixCSC{Bool,Int}(S) for S in 𝓢ₓ];  Su = [SparseMatrixCSC{Bool,Int}(S) for S in 𝓢ᵤ]
+    sx = [csc(S) for S in Sx];  su = [csc(S) for S in Su]
+    dims = Ref(Dims(Nx, Nu, Nx + Nu, Nx, length(Sx), 1, UInt32(0)))       # only Nx, Nu, T, index_base are read
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve Sx Su sx su begin
+        rc = ccall((:sls_controller_plan, LIB), Cint, (Ptr{Cvoid}, Cint, Ref{Dims}, Ptr{CscBool}, Ptr{CscBool}, Int64, Ref{Ptr{Cvoid}}),
+                   ctx, dev_slot, dims, sx, su, nscen, h)
+    end
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx)))
+    return Controller(h[], Nx, Nu, nscen)
+end
+_ctl_check(rc) = (rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL))); nothing)
+load!(c::Controller, d_values::Ptr{Cvoid}; stream::Ptr{Cvoid}=C_NULL) =
+    _ctl_check(ccall((:sls_controller_load, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), c.handle, stream, d_values))
+reset!(c::Controller; stream::Ptr{Cvoid}=C_NULL) =
+    _ctl_check(ccall((:sls_controller_reset, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), c.handle, stream))
+step!(c::Controller, d_x::Ptr{Cvoid}, d_u::Ptr{Cvoid}; d_what::Ptr{Cvoid}=C_NULL, stream::Ptr{Cvoid}=C_NULL) =
+    _ctl_check(ccall((:sls_controller_step, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     c.handle, stream, d_x, d_u, d_what))
+function Base.close(c::Controller)
+    c.handle != C_NULL && (ccall((:sls_controller_destroy, LIB), Cvoid, (Ptr{Cvoid},), c.handle); c.handle = C_NULL)
+    return nothing
 end
 
 """

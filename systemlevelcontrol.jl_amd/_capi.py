@@ -90,6 +90,8 @@ EXPORTS = [
     "sls_plan_update_plant", "sls_plan_update_result", "sls_plan_fetch_plant",
     "sls_plan_execute_columns", "sls_plan_track_changes", "sls_plan_execute_dirty", "sls_plan_fetch_dirty", "sls_plan_clear_dirty",
     "sls_plan_residual", "sls_plan_fetch_residual",
+    "sls_controller_plan", "sls_controller_load", "sls_controller_reset", "sls_controller_step", "sls_controller_info",
+    "sls_controller_destroy",
 ]
 
 _lib = None
@@ -193,7 +195,18 @@ def load_library(path: str | None = None):
     lib.sls_plan_clear_dirty.restype = C.c_int; lib.sls_plan_clear_dirty.argtypes = [vp, vp]
     lib.sls_plan_residual.restype = C.c_int; lib.sls_plan_residual.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp]
     lib.sls_plan_fetch_residual.restype = C.c_int; lib.sls_plan_fetch_residual.argtypes = [vp, vp, C.c_int, dp, dp, dp, dp]
+    masks = [C.POINTER(sls_dims), C.POINTER(sls_csc_bool), C.POINTER(sls_csc_bool)]
+    lib.sls_controller_plan.restype = C.c_int; lib.sls_controller_plan.argtypes = [vp, C.c_int] + masks + [C.c_int64, C.POINTER(vp)]
+    lib.sls_controller_load.restype = C.c_int; lib.sls_controller_load.argtypes = [vp, vp, vp]
+    lib.sls_controller_reset.restype = C.c_int; lib.sls_controller_reset.argtypes = [vp, vp]
+    lib.sls_controller_step.restype = C.c_int; lib.sls_controller_step.argtypes = [vp, vp, vp, vp, vp]
+    lib.sls_controller_info.restype = C.c_int; lib.sls_controller_info.argtypes = [vp, i64p, i64p, i64p]
+    lib.sls_controller_destroy.restype = None; lib.sls_controller_destroy.argtypes = [vp]
     # diagnostics outside the public header
+    lib.sls_debug_controller_tables.restype = C.c_int
+    lib.sls_debug_controller_tables.argtypes = masks + [i64p, i32p, i32p, i32p, i32p]
+    lib.sls_debug_controller_host.restype = C.c_int
+    lib.sls_debug_controller_host.argtypes = masks + [dp, C.c_int64, C.c_int64, dp, dp, dp]
     lib.sls_debug_residual_host.restype = C.c_int
     lib.sls_debug_residual_host.argtypes = common + [dpp, dpp, dp, dp, dp, dp, i64p, dp, i64p, dp, i64p, i32p, C.c_int64]
     lib.sls_debug_objective_host.restype = C.c_int
@@ -277,6 +290,21 @@ class Marshalled:
             self.n_sub = int(ptr[-1])
         self.nnz_x = [int(sp.csc_matrix(m).nnz) for m in Sx]
         self.nnz_u = [int(sp.csc_matrix(m).nnz) for m in Su]
+
+    @classmethod
+    def masks_only(cls, Nx, Nu, Sx, Su, index_base=0):
+        """dims and masks without a plant (the stand-alone controller reads Nx, Nu, T, index_base and the masks alone)"""
+        self = cls.__new__(cls)
+        self.keep, self.base, self.csc, self.nzval = [], int(index_base), {}, None
+        T = len(Sx)
+        if len(Su) != T:
+            raise ValueError("𝓢x and 𝓢u must have the same length T")
+        self.dims = sls_dims(int(Nx), int(Nu), int(Nx) + int(Nu), int(Nx), T, self.base, 0)
+        self.Sx = (sls_csc_bool * T)(*[self._bool(m) for m in Sx])
+        self.Su = (sls_csc_bool * T)(*[self._bool(m) for m in Su])
+        self.nnz_x = [int(sp.csc_matrix(m).nnz) for m in Sx]
+        self.nnz_u = [int(sp.csc_matrix(m).nnz) for m in Su]
+        return self
 
     def _csc_arrays(self, M):
         M = sp.csc_matrix(M)

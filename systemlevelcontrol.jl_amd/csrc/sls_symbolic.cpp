@@ -1113,19 +1113,12 @@ int build_symbolic(const Inputs& in, int64_t gbeg, int64_t gend, Symbolic& S, st
   return 0;
 }
 
-// README.md:62-72 — row-oriented FIR operators of the closed-loop simulation (see FirOperator)
-int build_fir_operator(const sls_dims* dims, const sls_csc_f64* A, const sls_csc_f64* B1, const sls_csc_f64* B2,
-                       const sls_csc_bool* Sx, const sls_csc_bool* Su, FirOperator& F, std::string& msg) {
-  if (!dims || !A || !B1 || !B2 || !Sx || !Su) { msg = "null argument"; return SLS_EINVAL; }
-  const sls_dims& d = *dims;
+namespace {
+
+// the row lists of a FirOperator (beta_ptr, u_ptr, hoff, perm, n_values) from the masks; dims already checked
+int fir_row_lists(const sls_dims& d, const sls_csc_bool* Sx, const sls_csc_bool* Su, FirOperator& F, std::string& msg) {
   const int base = d.index_base;
-  if (base != 0 && base != 1) { msg = "index_base must be 0 or 1"; return SLS_EINVAL; }
-  if (d.Nx <= 0 || d.Nu < 0 || d.Nw <= 0 || d.T <= 0) { msg = "Nx, Nw, T must be positive"; return SLS_EINVAL; }
-  if ((d.T + 1) * d.Nx > 0x7fffffffLL) { msg = "(T+1)·Nx exceeds int32"; return SLS_EUNSUPPORTED; }
   int rc;
-  if ((rc = check_csc(A, d.Nx, d.Nx, base, "A", msg))) return rc;
-  if ((rc = check_csc(B1, d.Nx, d.Nw, base, "B1", msg))) return rc;
-  if ((rc = check_csc(B2, d.Nx, d.Nu, base, "B2", msg))) return rc;
   int64_t nval = 0;
   std::vector<int64_t> off_x(d.T + 1), off_u(d.T + 1);
   for (int64_t t = 0; t < d.T; ++t) {
@@ -1139,10 +1132,7 @@ int build_fir_operator(const sls_dims* dims, const sls_csc_f64* A, const sls_csc
   }
   off_u[d.T] = nval;
   if (nval > 0x7fffffffLL) { msg = "value array exceeds int32 indexing"; return SLS_EUNSUPPORTED; }
-  F.Nx = d.Nx; F.Nu = d.Nu; F.Nw = d.Nw; F.T = d.T; F.n_values = nval;
-  csc_to_csr(A, base, F.A); csc_to_csr(B1, base, F.B1); csc_to_csr(B2, base, F.B2);
-  F.orphan.clear();
-  for (int64_t j = 0; j < d.Nu; ++j) if (B2->colptr[j + 1] == B2->colptr[j]) F.orphan.push_back((int32_t)j);
+  F.Nx = d.Nx; F.Nu = d.Nu; F.T = d.T; F.n_values = nval;
   // counting sort by row: slices in ascending lag, columns ascending inside a slice ⇒ rows come out ordered by (τ, c)
   auto each = [&](const sls_csc_bool* S, int64_t t0, int64_t t1, auto&& f) {
     for (int64_t t = t0; t < t1; ++t)
@@ -1168,6 +1158,40 @@ int build_fir_operator(const sls_dims* dims, const sls_csc_f64* A, const sls_csc
     F.hoff[e] = (int32_t)((t + 1) * d.Nx - c); F.perm[e] = (int32_t)(off_u[t] + k);
   });
   return 0;
+}
+
+}  // namespace
+
+// README.md:62-72 — row-oriented FIR operators of the closed-loop simulation (see FirOperator)
+int build_fir_operator(const sls_dims* dims, const sls_csc_f64* A, const sls_csc_f64* B1, const sls_csc_f64* B2,
+                       const sls_csc_bool* Sx, const sls_csc_bool* Su, FirOperator& F, std::string& msg) {
+  if (!dims || !A || !B1 || !B2 || !Sx || !Su) { msg = "null argument"; return SLS_EINVAL; }
+  const sls_dims& d = *dims;
+  const int base = d.index_base;
+  if (base != 0 && base != 1) { msg = "index_base must be 0 or 1"; return SLS_EINVAL; }
+  if (d.Nx <= 0 || d.Nu < 0 || d.Nw <= 0 || d.T <= 0) { msg = "Nx, Nw, T must be positive"; return SLS_EINVAL; }
+  if ((d.T + 1) * d.Nx > 0x7fffffffLL) { msg = "(T+1)·Nx exceeds int32"; return SLS_EUNSUPPORTED; }
+  int rc;
+  if ((rc = check_csc(A, d.Nx, d.Nx, base, "A", msg))) return rc;
+  if ((rc = check_csc(B1, d.Nx, d.Nw, base, "B1", msg))) return rc;
+  if ((rc = check_csc(B2, d.Nx, d.Nu, base, "B2", msg))) return rc;
+  if ((rc = fir_row_lists(d, Sx, Su, F, msg))) return rc;
+  F.Nw = d.Nw;
+  csc_to_csr(A, base, F.A); csc_to_csr(B1, base, F.B1); csc_to_csr(B2, base, F.B2);
+  F.orphan.clear();
+  for (int64_t j = 0; j < d.Nu; ++j) if (B2->colptr[j + 1] == B2->colptr[j]) F.orphan.push_back((int32_t)j);
+  return 0;
+}
+
+// the same row lists without a plant: the stand-alone controller (sls_controller.h)
+int build_controller_operator(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, FirOperator& F, std::string& msg) {
+  if (!dims || !Sx || !Su) { msg = "null argument"; return SLS_EINVAL; }
+  const sls_dims& d = *dims;
+  if (d.index_base != 0 && d.index_base != 1) { msg = "index_base must be 0 or 1"; return SLS_EINVAL; }
+  if (d.Nx <= 0 || d.Nu < 0 || d.T <= 0) { msg = "Nx, T must be positive"; return SLS_EINVAL; }
+  if ((d.T + 1) * d.Nx > 0x7fffffffLL) { msg = "(T+1)·Nx exceeds int32 (the entries' history offsets are int32)"; return SLS_EUNSUPPORTED; }
+  F = FirOperator();
+  return fir_row_lists(d, Sx, Su, F, msg);
 }
 
 }  // namespace sls

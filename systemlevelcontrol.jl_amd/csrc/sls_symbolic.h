@@ -218,5 +218,9 @@ struct FirOperator {
 };
 int build_fir_operator(const sls_dims* dims, const sls_csc_f64* A, const sls_csc_f64* B1, const sls_csc_f64* B2,
                        const sls_csc_bool* Sx, const sls_csc_bool* Su, FirOperator& out, std::string& msg);
+// The row lists alone, from the masks (dims: Nx, Nu, T, index_base are read): a FirOperator without a plant — Nw = 0, A / B1 /
+// B2 and orphan stay empty; beta_ptr, u_ptr, hoff, perm exactly as build_fir_operator leaves them (the stand-alone controller,
+// sls_controller.h).
+int build_controller_operator(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, FirOperator& out, std::string& msg);
 
 }  // namespace sls
