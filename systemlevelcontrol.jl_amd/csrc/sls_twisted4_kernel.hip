@@ -22,8 +22,13 @@
 // Hand-offs go through LDS flags (monotone sequence numbers; DS operations of one wave execute in program order, so a
 // flag written after the data is seen after the data): chain → helper per pivot, helper → chain per block.  All four waves
 // of the workgroup are resident (one workgroup per CU), every wait is on a wave that never waits for the waiter.
-// Everything else — setup, residual passes, output — is split four ways instead of two; sweeps, middle block, multiplier
-// iteration, status words and the P_k workspace layout are those of the two-wave kernel (bitwise the same mathematics).
+// Everything else — setup, residual passes, output — is split four ways instead of two; the order of the sweeps' vector operations,
+// the middle block, the multiplier iteration and the status words are those of the two-wave kernel.  The mat-vec inside the
+// sweeps is not, in the three-tile classes (<32,10>, <32,12>): P_k stays in the tile layout the Gauss–Jordan leaves it in —
+// in registers, in the workspace (nine rows of 64 per block) and in all four sweeps (matvec_tiles: Pᵀ·v, reduced over the
+// lane-grid rows by VALU cross-lane moves) — and the input vector of a block's fused sweep step, which has no P_k in it, is
+// formed one block ahead, before that block's elimination starts.  Same entries, same products; the additions come in another
+// order than in the two-wave kernel.  The four-tile classes keep its column layout and its mat-vec.
 // The symbolic part of the setup — the gather of Ã, Ãᵀ, B̃, B̃ᵀ from the shared CSR operator into row lists of local indices
 // and values (a binary search in the index set per entry), the list lengths, and which blocks repeat their predecessor's
 // masks — depends only on what a plan fixes.  twisted4_prepare_kernel (below) does it once per plan, one record per column in a
@@ -263,6 +268,25 @@ __device__ __forceinline__ void gj_tiles_publish(double (&Tt)[TR * TR], const in
     }
   });
 }
+
+// Pᵀ·v on the tiles where the Gauss–Jordan left them (three-tile classes): lane (a, b) multiplies its 3×3 tiles with the vector
+// entries of its tile ROWS, v_q = v[a + 8·q], and the three partial sums — entries b, b + 8, b + 16 of the product — are added
+// over a by VALU cross-lane moves only: no LDS image of the matrix, no LDS round trip in the reduction.  The waves are bound
+// by instruction issue, so the three sums share their moves (pairsum32 / pairsum16: one pair of swaps reduces two values, each
+// into one half): bit 2 of a for entries b and b + 8 together and for b + 16 alone, bit 1 for that pair, bit 0 by DPP — 14
+// instructions, where three separate three-stage sums take 39.  The complete sums land by a:
+//   a = 0, 1: entry b        a = 4, 5: entry b + 8        a = 2, 3, 6, 7: entry b + 16
+// and the caller's lanes a = 0, 4, 2 (twisted4_tile_slot) store the vector with one DS write by 24 lanes.
+// The sum runs over rows, as the column-layout mat-vec's does: the same entries of the computed inverse meet the same
+// entries of v, only the order of the additions differs.
+__device__ __forceinline__ double matvec_tiles(const double (&Tt)[9], const double v0, const double v1, const double v2) {
+  double r[3];
+#pragma unroll
+  for (int cj = 0; cj < 3; ++cj) r[cj] = __builtin_fma(Tt[6 + cj], v2, __builtin_fma(Tt[3 + cj], v1, Tt[cj] * v0));
+  return xsum8(pairsum16(pairsum32(r[0], r[1]), xsum32(r[2])));
+}
+// which third of the product (tile column cj) the lanes of lane-grid row a hold after matvec_tiles; the writers are a = 0, 4, 2
+__device__ __forceinline__ int twisted4_tile_slot(int ta) { return (ta & 2) ? 2 : (ta >> 2); }
 
 // The helper wave's side of the same elimination: X ← X − X[:,p]·(d·g[p,:]),  S ← S − (X[:,p]·d)·X[:,p]ᵀ for every pivot p the chain
 // wave has published (same lane grid; column p of X by ds_swizzle inside the 8-lane group, the same column as a row through the
@@ -631,27 +655,41 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
   };
   auto wx_of = [&](int k) -> double { return (k >= 0 && k <= T - 1 && j < n && mask[k * nm + j]) ? hx[j] : 0.0; };
 
-  auto matvec = [&](const double (&Pk)[RPL]) -> double {
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  // The three-tile classes keep P_k in the Gauss–Jordan's tile layout (lane (a, b): Pk[ri·TR + cj] = P[a + 8·ri][b + 8·cj]) — in
+  // registers, in the workspace (nine rows of 64 in the block's RPL·64 slot) and in every sweep: no conversion anywhere.  The
+  // four-tile classes keep the two-wave kernel's column layout (lane (h, j): rows HS·r + h of column j) — sixteen tiles would
+  // not fit the slot.  Either way the mat-vec reads its vector from tmp2 and gives entry `wi` of Pᵀ·tmp2 to the lanes `wr`, which
+  // write it back: lanes 0 … NPL − 1 with wi = lane in the column layout; 24 lanes in the tile layout (matvec_tiles).  The
+  // weight of entry wi comes from the table there (wxt[k·NPL + i] is wx_of(k) of lane i).
+  constexpr bool TILE = (TR == 3);
+  constexpr int PN = TILE ? TT : RPL;                      // registers (and workspace rows) per block
+  const int wi = TILE ? tb + 8 * twisted4_tile_slot(ta) : lane;
+  const bool wr = TILE ? ((0x15u >> ta) & 1u) != 0 : (lane < NPL);        // a = 0, 2, 4 (a shift, not three compares: no branches)
+  auto matvec = [&](const double (&Pk)[PN]) -> double {
+    if constexpr (TILE) {
+      return matvec_tiles(Pk, tmp2[ta], tmp2[ta + 8], tmp2[ta + 16]);
+    } else {
+      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
 #pragma unroll
-    for (int r = 0; r < RPL; ++r) {
-      const double y = tmp2[HS * r + h];
-      if ((r & 3) == 0) a0 = __builtin_fma(Pk[r], y, a0);
-      else if ((r & 3) == 1) a1 = __builtin_fma(Pk[r], y, a1);
-      else if ((r & 3) == 2) a2 = __builtin_fma(Pk[r], y, a2);
-      else a3 = __builtin_fma(Pk[r], y, a3);
+      for (int r = 0; r < RPL; ++r) {
+        const double y = tmp2[HS * r + h];
+        if ((r & 3) == 0) a0 = __builtin_fma(Pk[r], y, a0);
+        else if ((r & 3) == 1) a1 = __builtin_fma(Pk[r], y, a1);
+        else if ((r & 3) == 2) a2 = __builtin_fma(Pk[r], y, a2);
+        else a3 = __builtin_fma(Pk[r], y, a3);
+      }
+      double part = (a0 + a1) + (a2 + a3);
+      if (HS >= 2) part = xsum32(part);
+      return part;
     }
-    double part = (a0 + a1) + (a2 + a3);
-    if (HS >= 2) part = xsum32(part);
-    return part;
   };
-  auto load_P = [&](int k, double (&Pk)[RPL]) {
+  auto load_P = [&](int k, double (&Pk)[PN]) {
 #pragma unroll
-    for (int r = 0; r < RPL; ++r) Pk[r] = fac[((int64_t)k * RPL + r) * 64 + lane];
+    for (int r = 0; r < PN; ++r) Pk[r] = fac[((int64_t)k * RPL + r) * 64 + lane];
   };
-  auto store_P = [&](int k, const double (&Pk)[RPL]) {
+  auto store_P = [&](int k, const double (&Pk)[PN]) {
 #pragma unroll
-    for (int r = 0; r < RPL; ++r) fac[((int64_t)k * RPL + r) * 64 + lane] = Pk[r];
+    for (int r = 0; r < PN; ++r) fac[((int64_t)k * RPL + r) * 64 + lane] = Pk[r];
   };
 
   // r = f − E z(λ): x_t, u_t first (any order), then r_t = f_t − x_t + Ãx_{t−1} + B̃u_{t−1}; 4·HS time steps per round
@@ -744,8 +782,8 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
   }
   int iters = 0, status = 0;
 
-  // ---- chain-wave sweep steps (the two-wave kernel's, unchanged) ----
-  auto elim_up = [&](int k, const double (&Pk)[RPL], double wk) {
+  // ---- sweep steps of the later passes (the two-wave kernel's order of operations; the mat-vec is this kernel's own) ----
+  auto elim_up = [&](int k, const double (&Pk)[PN], double wk) {
     if (lane < NPL) {
       double a = rq[k * NPL + lane];
       if (k >= 1) a += dotA_row(tmp);                        // tmp = Wx_{k−1} q_{k−1}
@@ -753,10 +791,10 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
     }
     WSYNC();
     const double q = matvec(Pk);
-    if (lane < NPL) { rq[k * NPL + lane] = q; tmp[lane] = wk * q; }
+    if (wr) { rq[k * NPL + wi] = q; tmp[wi] = (TILE ? wxt[k * NPL + wi] : wk) * q; }
     WSYNC();
   };
-  auto elim_down = [&](int k, const double (&Pk)[RPL], double wk) {
+  auto elim_down = [&](int k, const double (&Pk)[PN], double wk) {
     if (lane < NPL) {
       double a = rq[k * NPL + lane];
       if (k < T) a += wk * dotA_col(tmp);                    // tmp = q_{k+1}
@@ -764,10 +802,10 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
     }
     WSYNC();
     const double q = matvec(Pk);
-    if (lane < NPL) { rq[k * NPL + lane] = q; tmp[lane] = q; }
+    if (wr) { rq[k * NPL + wi] = q; tmp[wi] = q; }
     WSYNC();
   };
-  auto middle = [&](const double (&Pc)[RPL]) {
+  auto middle = [&](const double (&Pc)[PN]) {
     if (lane < NPL) {
       double a = rq[c * NPL + lane];
       if (c >= 1) a += dotA_row(tmp);
@@ -776,11 +814,11 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
     }
     WSYNC();
     const double dl = matvec(Pc);
-    if (lane < NPL) { rq[c * NPL + lane] = dl; lam[c * NPL + lane] += dl; }
+    if (wr) { rq[c * NPL + wi] = dl; lam[c * NPL + wi] += dl; }
     WSYNC();
   };
   auto outward = [&]() {
-    double Pk[RPL];
+    double Pk[PN];
     if (wv == 0) {
       for (int k = c - 1; k >= 0; --k) {
         load_P(k, Pk);
@@ -790,8 +828,8 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
           tmp2[lane] = a;
         }
         WSYNC();
-        const double dl = matvec(Pk) + ((lane < NPL) ? rq[k * NPL + lane] : 0.0);
-        if (lane < NPL) { rq[k * NPL + lane] = dl; lam[k * NPL + lane] += dl; }
+        const double dl = matvec(Pk) + (wr ? rq[k * NPL + wi] : 0.0);
+        if (wr) { rq[k * NPL + wi] = dl; lam[k * NPL + wi] += dl; }
         WSYNC();
       }
     } else if (wv == 1) {
@@ -801,8 +839,8 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
         WSYNC();
         if (lane < NPL) tmp2[lane] = (lane < n) ? dotA_row(tmp) : 0.0;
         WSYNC();
-        const double dl = matvec(Pk) + ((lane < NPL) ? rq[k * NPL + lane] : 0.0);
-        if (lane < NPL) { rq[k * NPL + lane] = dl; lam[k * NPL + lane] += dl; }
+        const double dl = matvec(Pk) + (wr ? rq[k * NPL + wi] : 0.0);
+        if (wr) { rq[k * NPL + wi] = dl; lam[k * NPL + wi] += dl; }
         WSYNC();
       }
     }
@@ -810,25 +848,12 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
 
   unsigned long long ph[4] = {0, 0, 0, 0};      // diagnostics (SLS_PHASE_TIMERS ≥ 2): chain wave: hand-off waits / Gauss–Jordan / store + sweep; helper: static + border / elimination / of which waiting
   if (resid > p.tol) {
-    double M[RPL];
+    double M[PN];
     if (helper == 0) {
       // =================== chain wave: Gauss–Jordan + store + fused sweep per block; blocks arrive from the helper ===================
-      if (dir == 0) {
-        // block 0 is diagonal (δ + Wx_0): its inverse needs no elimination, and the helper folds it into block 1's weights
-        const double w0 = wx_of(0);
-#pragma unroll
-        for (int r = 0; r < RPL; ++r) M[r] = (HS * r + h == j && j < n) ? 1.0 / (delta + w0) : 0.0;
-        store_P(0, M);
-        elim_up(0, M, w0);
-      }
-      const int s_end = (dir == 0) ? c : T - c;
-      for (int s = 1; s <= s_end; ++s) {
-        const int k = (dir == 0) ? s : T - s + 1;
-        const bool mid = (dir == 0) && (s == c);
-        unsigned long long q0 = (SLS_T4_PHASES != 0) ? __builtin_amdgcn_s_memtime() : 0;
+      // the helper hands over the stored half (tiles ri ≤ cj of every lane); the other half is read at the mirror position
+      auto receive = [&](double (&Tt)[TT], int s, bool mid) {
         wait_flag(flagB, s);
-        // the helper hands over the stored half (tiles ri ≤ cj of every lane); the other half is read at the mirror position
-        double Tt[TT];
 #pragma unroll
         for (int ri = 0; ri < TR; ++ri) {
 #pragma unroll
@@ -844,22 +869,97 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
               Tt[ri * TR + cj] += (ri <= cj) ? hand_other[(ta + 8 * ri) * LDT + tb + 8 * cj] : hand_other[(tb + 8 * cj) * LDT + ta + 8 * ri];
           }
         }
-        if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[0] += q1 - q0; q0 = q1; }
-        gj_tiles_publish<NP, TR, RS>(Tt, lane, n, rowbuf, flagA, s * 64, mat);
-        if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { __builtin_amdgcn_sched_barrier(0); asm volatile("" :: "v"(Tt[0])); const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[1] += q1 - q0; q0 = q1; }
-        // tiles → column layout (lane (h, j): rows HS·r + h of column j) through the private image
+      };
+      const int s_end = (dir == 0) ? c : T - c;
+      if constexpr (TILE) {
+        // The sweep step of block k multiplies P_k with  rq[k] + Ã·(Wx_{k−1} q_{k−1})  (downward: rq[k] + Wx_k·Ãᵀ q_{k+1}), which has no
+        // P_k in it: it is formed and laid out in tmp2 at the end of the step BEFORE, and this lane's three entries of it (its tile
+        // rows) wait in registers through the Gauss–Jordan.  After the last pivot the tiles are used where they are: nine FMAs, the
+        // reduction over the lane-grid rows (matvec_tiles), one write — and the nine global stores, which nothing waits for.
+        double v[TR];
+        auto sweep_input = [&](int kn) {                    // elim_up's / elim_down's first half, for block kn
+          if (lane < NPL) {
+            double a = rq[kn * NPL + lane];
+            if (dir == 0) { if (kn >= 1) a += dotA_row(tmp); }                  // tmp = Wx_{kn−1} q_{kn−1}
+            else if (kn < T) a += wxt[kn * NPL + lane] * dotA_col(tmp);          // tmp = q_{kn+1}; the table's wx_of(kn)
+            tmp2[lane] = (lane < n) ? a : 0.0;
+          }
+          WSYNC();
 #pragma unroll
-        for (int ri = 0; ri < TR; ++ri) {
+          for (int q = 0; q < TR; ++q) v[q] = tmp2[ta + 8 * q];
+        };
+        auto sweep = [&](int k, double wk) {                // … and their second half; wk = Wx_k[wi]
+          const double q = matvec_tiles(M, v[0], v[1], v[2]);
+          if (wr) { rq[k * NPL + wi] = q; tmp[wi] = (dir == 0) ? wk * q : q; }
+          WSYNC();
+        };
+        sweep_input((dir == 0) ? 0 : T);                    // the first block of either chain has no predecessor
+        if (dir == 0) {
+          // block 0 is diagonal (δ + Wx_0): its inverse needs no elimination, and the helper folds it into block 1's weights
 #pragma unroll
-          for (int cj = 0; cj < TR; ++cj) mat[(ta + 8 * ri) * LDT + tb + 8 * cj] = Tt[ri * TR + cj];
+          for (int ri = 0; ri < TR; ++ri) {
+            const int i = ta + 8 * ri;
+            const double di = 1.0 / (delta + wxt[i]);       // wxt[i] = Wx_0[i]
+#pragma unroll
+            for (int cj = 0; cj < TR; ++cj) M[ri * TR + cj] = (i == tb + 8 * cj && i < n) ? di : 0.0;
+          }
+          store_P(0, M);
+          sweep(0, wxt[wi]);
+          if (c > 1) sweep_input(1);                        // (block c is the middle block: no fused step)
         }
-        WSYNC();
+        for (int s = 1; s <= s_end; ++s) {
+          const int k = (dir == 0) ? s : T - s + 1;
+          const bool mid = (dir == 0) && (s == c);
+          const bool more = (dir == 0) ? (s + 1 < c) : (s < s_end);      // the next block has a fused step
+          const double wk = wxt[k * NPL + wi];             // (the table: one read, no mask → weight chain)
+          unsigned long long q0 = (SLS_T4_PHASES != 0) ? __builtin_amdgcn_s_memtime() : 0;
+          receive(M, s, mid);
+          if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[0] += q1 - q0; q0 = q1; }
+          gj_tiles_publish<NP, TR, RS>(M, lane, n, rowbuf, flagA, s * 64, mat);
+          if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { __builtin_amdgcn_sched_barrier(0); asm volatile("" :: "v"(M[0])); const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[1] += q1 - q0; q0 = q1; }
+          SLS_ISA_MARK("chain-tail");
+          store_P(k, M);
+          if (!mid) {
+            sweep(k, wk);
+            if (more) sweep_input((dir == 0) ? k + 1 : k - 1);
+          }
+          SLS_ISA_MARK("chain-tail-end");
+          if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[2] += q1 - q0; q0 = q1; }
+        }
+      } else {
+        if (dir == 0) {
+          // block 0 is diagonal (δ + Wx_0): its inverse needs no elimination, and the helper folds it into block 1's weights
+          const double w0 = wx_of(0);
 #pragma unroll
-        for (int r = 0; r < RPL; ++r) M[r] = mat[(HS * r + h) * LDT + j];
-        WSYNC();
-        store_P(k, M);
-        if (!mid) { if (dir == 0) elim_up(k, M, wx_of(k)); else elim_down(k, M, wx_of(k)); }
-        if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[2] += q1 - q0; q0 = q1; }
+          for (int r = 0; r < RPL; ++r) M[r] = (HS * r + h == j && j < n) ? 1.0 / (delta + w0) : 0.0;
+          store_P(0, M);
+          elim_up(0, M, w0);
+        }
+        for (int s = 1; s <= s_end; ++s) {
+          const int k = (dir == 0) ? s : T - s + 1;
+          const bool mid = (dir == 0) && (s == c);
+          unsigned long long q0 = (SLS_T4_PHASES != 0) ? __builtin_amdgcn_s_memtime() : 0;
+          double Tt[TT];
+          receive(Tt, s, mid);
+          if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[0] += q1 - q0; q0 = q1; }
+          gj_tiles_publish<NP, TR, RS>(Tt, lane, n, rowbuf, flagA, s * 64, mat);
+          if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { __builtin_amdgcn_sched_barrier(0); asm volatile("" :: "v"(Tt[0])); const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[1] += q1 - q0; q0 = q1; }
+          SLS_ISA_MARK("chain-tail");
+          // tiles → column layout (lane (h, j): rows HS·r + h of column j) through the private image
+#pragma unroll
+          for (int ri = 0; ri < TR; ++ri) {
+#pragma unroll
+            for (int cj = 0; cj < TR; ++cj) mat[(ta + 8 * ri) * LDT + tb + 8 * cj] = Tt[ri * TR + cj];
+          }
+          WSYNC();
+#pragma unroll
+          for (int r = 0; r < RPL; ++r) M[r] = mat[(HS * r + h) * LDT + j];
+          WSYNC();
+          store_P(k, M);
+          if (!mid) { if (dir == 0) elim_up(k, M, wx_of(k)); else elim_down(k, M, wx_of(k)); }
+          SLS_ISA_MARK("chain-tail-end");
+          if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[2] += q1 - q0; q0 = q1; }
+        }
       }
     } else {
       // =================== helper wave: static part S_k, border X, elimination behind the chain wave's pivots ===================
@@ -1020,7 +1120,7 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
     for (int it = 1; it <= itmax; ++it) {
       iters = it;
       if (it > 1) {
-        double Pk[RPL];
+        double Pk[PN];
         if (wv == 0) {
           for (int k = 0; k < c; ++k) { load_P(k, Pk); elim_up(k, Pk, wx_of(k)); }
         } else if (wv == 1) {

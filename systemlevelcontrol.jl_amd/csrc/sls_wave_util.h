@@ -75,6 +75,29 @@ __device__ __forceinline__ double xsum16(double v) {
   return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
 }
 
+// v[lane] + v[lane ^ 8] with DPP row_ror:8 (a rotation by half of the 16-lane DPP row; 64-bit VALU operations take no DPP
+// control but row_newbcast, so the two halves move by v_mov_b32)
+__device__ __forceinline__ double xsum8(double v) {
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x128, 0xf, 0xf, false);      // (every lane has a source: no `old` value to set up)
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x128, 0xf, 0xf, false);
+  return v + __hiloint2double(hi, lo);
+}
+// Two sums for the price of one: the permlane swaps exchange halves of TWO registers, so one pair of them and one addition
+// reduce p and q together, each result landing in one half —
+//   pairsum32(p, q)[lane] = lane < 32      ? p[lane] + p[lane + 32] : q[lane − 32] + q[lane]
+//   pairsum16(p, q)[lane] = !(lane & 16)   ? p[lane] + p[lane + 16] : q[lane − 16] + q[lane]
+// (xsum32(v) = pairsum32(v, v), but that form needs a copy of v first).
+__device__ __forceinline__ double pairsum32(double p, double q) {
+  const auto a = __builtin_amdgcn_permlane32_swap(__double2loint(p), __double2loint(q), false, false);
+  const auto b = __builtin_amdgcn_permlane32_swap(__double2hiint(p), __double2hiint(q), false, false);
+  return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
+}
+__device__ __forceinline__ double pairsum16(double p, double q) {
+  const auto a = __builtin_amdgcn_permlane16_swap(__double2loint(p), __double2loint(q), false, false);
+  const auto b = __builtin_amdgcn_permlane16_swap(__double2hiint(p), __double2hiint(q), false, false);
+  return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
+}
+
 // compile-time loop: f(std::integral_constant<int, 0>{}), f(<1>), …  — gives every pivot a constexpr index, which the
 // immediate-pattern cross-lane instructions (ds_swizzle) need
 template <class F, int... Is>

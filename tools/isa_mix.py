@@ -5,7 +5,8 @@
 Compiles csrc/sls_twisted4_kernel.hip with `hipcc --cuda-device-only -S` and -DSLS_ISA_MARKS=1, which puts an assembler comment
 at the start of every unrolled pivot of the chain wave's Gauss-Jordan and of the helper wave's elimination (at a sched_barrier
 the code already has, so nothing moves).  The listing between two consecutive markers of the same kind is one pivot, its
-out-of-line wait loop included.  Prints the registers and scratch of each instantiation and, per loop, the median count of
+out-of-line wait loop included.  A third pair of markers, "chain-tail" … "chain-tail-end", brackets what the chain wave does per
+block after its last pivot (store + fused sweep step; one span per instantiated loop body, not per pivot).  Prints the registers and scratch of each instantiation and, per loop, the median count of
 each instruction class per pivot.  Needs hipcc only (no GPU).
 """
 import os
@@ -75,6 +76,36 @@ def spans(body, mark):
     return out
 
 
+def tail_spans(body):
+    """The chain wave's per-block tail, "chain-tail" … "chain-tail-end", one span per instantiated loop body.  The block placement
+    may rotate the loop so that the end marker precedes the start marker in the listing: the tail then runs from the start marker
+    to the first unconditional backward branch, and on from that branch's target to the end marker (side blocks placed behind the
+    branch — a few instructions of divergent regions — are not counted)."""
+    lines = [l.strip() for l in body.splitlines()]
+    is_op = lambda t: t and not t.startswith((";", ".")) and not t.endswith(":") and ":" not in t.split()[0]
+    label_at = {t.split(":")[0]: i for i, t in enumerate(lines) if t.startswith(".LBB") and ":" in t}
+    out = []
+    for i, t in enumerate(lines):
+        if t != "; isa-mark chain-tail":
+            continue
+        cur, j, done = [], i + 1, False
+        while j < len(lines) and not done:
+            u = lines[j]
+            if u == "; isa-mark chain-tail-end":
+                done = True
+            elif u.startswith("; isa-mark"):
+                break
+            elif is_op(u):
+                cur.append(u.split()[0])
+                tgt = u.split()[1] if u.startswith("s_branch") else None
+                if tgt in label_at and label_at[tgt] < i:          # the loop's back edge: go on at its target
+                    j = label_at[tgt]
+            j += 1
+        if done:
+            out.append(cur)
+    return out
+
+
 def mix(mn):
     c = {name: 0 for name, _ in CLASSES}
     for op in mn:
@@ -99,15 +130,15 @@ def main(argv):
     for rpl, pre in [(r, q) for r in (rpls or [10, 12]) for q in (1, 0)]:
         body, res = kernel_body(text, rpl, pre)
         print(f"twisted4<32,{rpl}> ({'plan-time blocks' if pre else 'rebuild'}): {res['num_vgpr']} VGPRs + {res['num_agpr']} AGPRs, scratch {res['scratch']} B/lane")
-        for mark in ("chain-pivot", "helper-pivot"):
-            sp = spans(body, mark)
+        for mark in ("chain-pivot", "helper-pivot", "chain-tail"):
+            sp = tail_spans(body) if mark == "chain-tail" else spans(body, mark)
             if not sp:
                 print(f"  {mark}: no markers found")
                 continue
             ms = [mix(s) for s in sp]
             keys = ["total"] + [name for name, _ in CLASSES]
             med = {k: statistics.median(m[k] for m in ms) for k in keys}
-            print(f"  {mark} ({len(sp)} pivots), median per pivot: " + ", ".join(f"{k} {med[k]:g}" for k in keys))
+            print(f"  {mark} ({len(sp)} {'loop bodies' if mark == 'chain-tail' else 'pivots'}), median per {'block' if mark == 'chain-tail' else 'pivot'}: " + ", ".join(f"{k} {med[k]:g}" for k in keys))
             print(f"  {mark}: agpr copies over all pivots {sum(m['agpr copy'] for m in ms)}")
 
 

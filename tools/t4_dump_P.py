@@ -1,5 +1,8 @@
 """Diagnostics: pivot blocks P_k of one column from the four-wave and the two-wave twisted kernels, block by block (T = 4 plants:
-both kernels put the middle at block 1, so every block is comparable).  usage: t4_dump_P.py seed col"""
+both kernels put the middle at block 1, so every block is comparable).  usage: t4_dump_P.py seed col
+The two-wave kernel and the four-tile classes of the four-wave kernel store a block in column layout (row r of the slot, lane
+(h, j): P[2r + h][j]); the three-tile classes <32,10> / <32,12> of the four-wave kernel store the Gauss-Jordan's nine tile
+registers (row ri*3 + cj of the slot, lane 8a + b: P[a + 8 ri][b + 8 cj]).  Both are brought to the same (2 RPL, 32) image."""
 import os, sys, ctypes as C
 os.environ["SLS_LAB"] = "1"; os.environ["SLS_T4_NMIN"] = "0"; os.environ["SLS_T4_TMIN"] = "0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,6 +20,16 @@ nbig = full.info["max_nx"]; full.close()
 # a partner with the largest index set forces the launch's 32-lane class
 sizes = [int(sum(M[:, c].nnz for M in S[0])) for c in range(P.Nx)]
 partner = int(np.argmax(sizes))
+def tiles_to_image(blk, RPL):
+    """(RPL, 64) slot of a three-tile class -> (2 RPL, 32) image; tile rows past 2 RPL - 1 are padding and are dropped"""
+    full = np.zeros((24, 32))
+    la, lb = np.divmod(np.arange(64), 8)
+    for ri in range(3):
+        for cj in range(3):
+            full[la + 8 * ri, lb + 8 * cj] = blk[ri * 3 + cj]
+    return full[:2 * RPL]
+
+
 res = {}
 for mode in ("1", "0"):
     os.environ["SLS_TWISTED4"] = mode
@@ -32,7 +45,10 @@ for mode in ("1", "0"):
     for b in range(2):
         buf = np.zeros(stride)
         assert lib.sls_plan_debug_read_workspace(plan.handle, b * stride, stride, buf.ctypes.data_as(C.POINTER(C.c_double))) == 0
-        bufs.append(buf.reshape(T + 1, RPL, 2, 32))
+        img = buf.reshape(T + 1, RPL, 2, 32)
+        if mode == "1" and RPL in (10, 12):
+            img = np.stack([tiles_to_image(blk, RPL) for blk in buf.reshape(T + 1, RPL, 64)]).reshape(T + 1, RPL, 2, 32)
+        bufs.append(img)
     res[mode] = (desc, st.copy(), rs.copy(), it.copy(), bufs, RPL)
     plan.close()
 print(meta, "col", col, "partner", partner)
