@@ -1,7 +1,8 @@
-// sls_api.cpp — implementation of include/sls_mi355x.h (the drop-in C ABI).
+// sls_api.cpp — implementation of include/sls_mi355x.h (the drop-in C ABI): the context and the resident plans.  The one-shot
+// calls built on them (sls_h2_sf_solve ≙ SLS_𝓗₂(P, 𝓢; 𝓘), src/synthesis.jl:11-32) are in sls_dropin.cpp, the exports of
+// include/sls_mi355x_debug.h in sls_debug.cpp.
 //
 // Host side of the path that replaces reference src/synthesis.jl:11-72:
-//   sls_h2_sf_solve      ≙ SLS_𝓗₂(P, 𝓢; 𝓘)                    (src/synthesis.jl:11-32)
 //   sls_h2_sf_plan       ≙ the per-column set-up the reference redoes inside the loop
 //                           (src/reduction.jl:11-27, src/synthesis.jl:40-43,57-60)
 //   sls_plan_execute     ≙ the @distributed loop body's solve   (src/synthesis.jl:46-62)
@@ -21,35 +22,14 @@
 #include <vector>
 
 #include "../../include/sls_mi355x.h"
-#include "../../include/sls_mi355x_debug.h"
 #include "sls_device.h"
+#include "sls_dropin_host.h"
 #include "sls_internal.h"
 #include "sls_objective.h"
+#include "sls_plan.h"
 #include "sls_residual.h"
 #include "sls_routing.h"
 #include "sls_symbolic.h"
-
-namespace sls {
-hipError_t launch_general(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool wide);
-hipError_t launch_scatter(const double* src, const int64_t* idx, int64_t n, double* dst, hipStream_t stream);
-hipError_t launch_wave(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream);
-hipError_t launch_twisted(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream);
-hipError_t launch_twisted4(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream);
-hipError_t launch_twisted4_prepare(int cls, const KernelParams& p, unsigned char* pool, hipStream_t stream);
-hipError_t launch_tile(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool mlds, bool two_per_cu,
-                       bool general_weights, bool big);
-hipError_t launch_expand_tables(const SubDesc* subs, int nsub, int T, const uint64_t* cmask, const int32_t* cbase, const int64_t* coff,
-                                uint8_t* mask_pool, int32_t* dest_pool, hipStream_t stream);
-hipError_t launch_mask_levels(const MaskParams& p, bool fill, int grid, size_t lds_bytes, hipStream_t stream);
-hipError_t launch_index_sets(const IndexSetParams& p, bool fill, int grid, size_t lds_bytes, hipStream_t stream);
-hipError_t launch_column_tables(const ColumnTableParams& p, bool fill, int grid, size_t lds_bytes, hipStream_t stream);
-hipError_t launch_level_prefix(const int32_t* cntx, const int32_t* cntu, int Nx, int K1, int64_t* prex, int64_t* preu, int64_t* totx,
-                               int64_t* totu, hipStream_t stream);
-hipError_t launch_objective(const ObjectiveParams& p, int lds_doubles, double* d_total, hipStream_t stream);
-hipError_t launch_residual(const ResidualParams& p, double* d_totals, hipStream_t stream);
-hipError_t launch_tile_invert(const double* d_A, int n, double* d_ws, double* d_out, bool mlds, hipStream_t stream);
-hipError_t launch_operator_update(const OperatorUpdateParams& p, hipStream_t stream);
-}  // namespace sls
 
 namespace {
 std::mutex g_err_mu;
@@ -61,9 +41,7 @@ std::set<const void*> g_live_ctx;   // a plan may outlive its context (host-lang
 namespace sls {
 int fail(sls_ctx* ctx, int code, const std::string& msg) {
   // a plan / loop object may report through a context that its owner has already destroyed (host-language GC order)
-  bool live = false;
-  if (ctx) { std::lock_guard<std::mutex> l(g_err_mu); live = g_live_ctx.count(ctx) > 0; }
-  if (live) ctx->err = msg;
+  if (ctx && ctx_is_live(ctx)) ctx->err = msg;
   set_global_error(msg);
   return code;
 }
@@ -74,118 +52,22 @@ bool ctx_is_live(const sls_ctx* ctx) {
   std::lock_guard<std::mutex> l(g_err_mu);
   return g_live_ctx.count(ctx) > 0;
 }
+double now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+int wait_plan_done(sls_plan* pl) {
+  if (pl->last_done) {
+    hipError_t e = hipEventSynchronize(pl->last_done);
+    if (e != hipSuccess) return hipfail(pl->ctx, e, "hipEventSynchronize (plan done)");
+  }
+  return 0;
+}
 }  // namespace sls
 
 using namespace sls;
 
 namespace {
-double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-constexpr int kEventPool = 64;
 constexpr int64_t kT4StaticBudget = 64ll << 20;   // bytes of plan-time static blocks a plan may hold (four-wave kernel)
-}  // namespace
-
-struct sls_plan {
-  sls_ctx* ctx = nullptr;
-  int dev = 0;
-  int slot = 0;
-  bool streams_borrowed = false, scratch_borrowed = false, arena_borrowed = false, stream_external = false, ltab_borrowed = false;
-  hipEvent_t ev_batch = nullptr, ev_batch_done = nullptr;     // sls_plan_execute_batch fork / join edges
-  void* own_scratch = nullptr;
-  Symbolic sym;            // host copy (pools are cleared after upload except what download needs; its operator values are the plan-time ones)
-  sls_plan_info info{};
-  hipStream_t stream = nullptr;
-  // device buffers
-  std::vector<void*> dev_allocs;
-  struct ArenaReq { const void* src; size_t bytes; void** out; size_t off; bool zero; };
-  std::vector<ArenaReq> arena_reqs;
-  KernelParams kp{};       // dest_pool / out are patched per execute
-  const int32_t* d_dest = nullptr;
-  const int32_t* d_pdest = nullptr;
-  int32_t* d_counters = nullptr;      // one work-queue counter per launch (tile kernel)
-  unsigned char* d_big = nullptr;     // big tile launches: their carve buffers (inside the scratch workspace)
-  bool has_tile = false;
-  // Prepared records of the four-wave columns (twisted4_prepare_kernel, layout: sls_device.h), written in plan_finish.
-  // They hold index lists AND the gathered values of A / B2, taken from the plan's own copy of the operator:
-  // sls_plan_update_plant reruns the kernel behind every change of that copy.
-  unsigned char* d_t4 = nullptr;
-  int64_t t4_stride = 0, t4_records = 0;
-  // The static blocks S_k of the same columns (layout: sls_device.h, twisted4_static_doubles), written by the same kernel from
-  // the same copy.  NULL — the launches rebuild the blocks themselves — when the pool would exceed kT4StaticBudget or with
-  // SLS_T4_PRESTATIC=0 (lab mode).
-  double* d_t4s = nullptr;
-  int64_t t4s_doubles = 0;
-  struct Launch : LaunchSpec {         // what kernel selection decided + what the launch runs on
-    explicit Launch(const LaunchSpec& spec) : LaunchSpec(spec) {}
-    hipStream_t stream = nullptr;      // aux stream (launch 0 runs on the caller's stream)
-    hipEvent_t done = nullptr;
-    int64_t t4_off = 0;                // four-wave launch: its first record in d_t4
-    int64_t t4s_off = 0, t4s_stride = 0;   // … its first double in d_t4s, doubles per column
-  };
-  std::vector<Launch> launches;
-  hipEvent_t ev_fork = nullptr;
-  hipEvent_t ev_done = nullptr;         // recorded on the caller's stream at the end of an execute that the event pool could not time
-  hipEvent_t last_done = nullptr;       // the end of the last execute: its ev_stop (timed) or ev_done (untimed); what status reads and downloads wait for
-  // event timing
-  hipEvent_t ev_start[kEventPool], ev_stop[kEventPool];
-  int ev_used = 0;
-  double ev_acc_ms = 0.0;
-  int64_t ev_acc_n = 0;
-  bool events_ok = false;
-  pool_vec<double> host_stage;      // D2H staging (small Φ only)
-  std::vector<int32_t> too_large_subs;  // subproblems beyond every kernel's LDS budget: never launched, status SLS_COL_UNSUPPORTED
-  std::vector<int32_t> status_init;     // initial content of the device status words
-  int64_t gbeg = 0, gend = 0, ngroups_in = 0;   // the shard of the caller's group list this plan covers
-  sls_plan* refine = nullptr;           // sls_plan_refine: the near-singular groups once more on the tile kernel, run after every execute
-  std::vector<int64_t> refine_dst;      // subproblem of this plan each subproblem of `refine` replaces
-  int64_t info_unsupported = 0;
-  // objective evaluation (sls_plan_objective): the records of Symbolic::obj_pool, the work list of the general build and the
-  // plan-owned result buffer of sls_plan_fetch_objective (n_subproblems values, then the total)
-  const double* d_obj = nullptr;
-  const int32_t* d_gen = nullptr;
-  double* d_colobj = nullptr;
-  std::vector<int32_t> obj_gen;
-  int obj_lds_doubles = 0;
-  // operator update (sls_plan_update_plant): the value map and plan-time-zero marks (host copy: the host path's check), their
-  // device copies, a staging array for host values (nnzA + nnzB doubles), the refusal counter of the device path and the end
-  // of the last update on the stream it was enqueued on
-  OperatorValueMap opmap;
-  const int32_t* d_upd_pos = nullptr;
-  const uint8_t* d_upd_zero = nullptr;
-  double* d_upd_stage = nullptr;
-  unsigned long long* d_upd_rejected = nullptr;
-  hipEvent_t ev_upd = nullptr;
-  bool upd_recorded = false;
-  // partial re-solve (sls_plan_execute_columns / _dirty, sls_plan_track_changes): one device allocation made by
-  // the first of those calls (partial_ensure) — a plan that never uses them holds none of it and reports the same
-  // workspace_bytes.  Layouts: sls_device.h (ChangedEntriesParams, MarkAffectedParams, CompactOrderParams).
-  struct Partial {
-    bool ready = false, track = false;
-    uint8_t* dirty = nullptr;         // [nsub] marks of the tracked updates
-    uint8_t* marks = nullptr;         // [nsub] the list of an sls_plan_execute_columns call
-    uint8_t* chg = nullptr;           // [nnzA + nnzB]
-    uint8_t* row_chg = nullptr;       // [Nx]
-    int32_t* sel_order = nullptr;     // [order entries]
-    int32_t* sel_pos = nullptr;
-    int32_t* count = nullptr;         // [2 · launches]
-    const int32_t* launch_tab = nullptr;   // [launches][3]
-    std::vector<int32_t> h_count;
-    std::vector<uint8_t> h_marks;
-  } part;
-  // achievability residual (sls_plan_residual): the halo lists, the subproblems' global columns and the plan-owned
-  // result buffer of sls_plan_fetch_residual (three arrays of n_subproblems values, then the two totals) — one device allocation
-  // made by the first call (residual_ensure), not counted in workspace_bytes
-  struct Residual {
-    bool ready = false;
-    const int32_t* sub_col = nullptr;
-    const int64_t* halo_ptr = nullptr;
-    const int32_t* halo_rows = nullptr;
-    double* out = nullptr;            // [3 · nsub + 2]
-  } resid;
-};
-
-namespace {
 
 // Device memory of a plan comes from ONE allocation: requests are recorded first and committed together (one hipMalloc,
 // one staged H2D copy).  A README-sized plan used to spend 2 ms in ~25 hipMalloc/hipMemcpy calls for a 0.2 ms solve.
@@ -221,9 +103,7 @@ hipError_t create_aux_stream(hipStream_t* st, bool low) {
 
 // The context slot's pinned staging memory (created on first use, 8 MiB): nullptr when unavailable or too small.
 unsigned char* slot_pinned(sls_ctx* ctx, int slot, size_t bytes) {
-  bool ctx_alive;
-  { std::lock_guard<std::mutex> l(g_err_mu); ctx_alive = g_live_ctx.count(ctx) > 0; }
-  if (!ctx_alive || slot < 0 || slot >= (int)ctx->slots.size() || sls_knob("SLS_PAGEABLE_D2H")) return nullptr;
+  if (!ctx_is_live(ctx) || slot < 0 || slot >= (int)ctx->slots.size() || sls_knob("SLS_PAGEABLE_D2H")) return nullptr;
   sls_ctx::Slot& sl = ctx->slots[slot];
   if (sl.pinned_pending) { (void)hipEventSynchronize(sl.pinned_busy); sl.pinned_pending = false; }   // an update's H2D copy still reads it
   constexpr size_t kBytes = 8u << 20;
@@ -243,9 +123,7 @@ int pinned_download(sls_ctx* ctx, int slot, int dev, const void* d_src, const st
   constexpr int64_t kChunk = (1ll << 20) / 8;          // elements per chunk
   const int64_t nsl = (int64_t)ptrs.size(), n_total = beg[nsl];
   if (n_total == 0) return 0;
-  bool ctx_alive;
-  { std::lock_guard<std::mutex> l(g_err_mu); ctx_alive = g_live_ctx.count(ctx) > 0; }
-  if (!ctx_alive || slot >= (int)ctx->slots.size() || sls_knob("SLS_PAGEABLE_D2H")) return 1;
+  if (!ctx_is_live(ctx) || slot >= (int)ctx->slots.size() || sls_knob("SLS_PAGEABLE_D2H")) return 1;
   sls_ctx::Slot& sl = ctx->slots[slot];
   (void)slot_pinned(ctx, slot, (size_t)kDlLanes * kChunk * 8);
   while (sl.pinned && (int)sl.dl_streams.size() < kDlLanes) {
@@ -294,9 +172,7 @@ int arena_commit(sls_plan* pl) {
   {
     // the context keeps one arena for reuse (a drop-in call builds and drops a plan per call: a hipMalloc + hipFree pair of
     // tens of MB costs ≈0.2 ms, of a few hundred KB ≈30 µs); a second live plan gets its own
-    bool ctx_alive;
-    { std::lock_guard<std::mutex> l(g_err_mu); ctx_alive = g_live_ctx.count(pl->ctx) > 0; }
-    sls_ctx::Slot* sl = (ctx_alive && pl->slot < (int)pl->ctx->slots.size()) ? &pl->ctx->slots[pl->slot] : nullptr;
+    sls_ctx::Slot* sl = (ctx_is_live(pl->ctx) && pl->slot < (int)pl->ctx->slots.size()) ? &pl->ctx->slots[pl->slot] : nullptr;
     const size_t want = std::max<size_t>(total, 256);
     if (sl && !sl->arena_in_use) {
       if (sl->arena_bytes < want || sl->arena_bytes > 4 * want + (64u << 20)) {      // too small, or wastefully large
@@ -374,16 +250,6 @@ int fold_events(sls_plan* pl, bool blocking = true) {
     pl->ev_acc_ms += ms; pl->ev_acc_n += 1;
   }
   pl->ev_used = kept;
-  return 0;
-}
-
-// Host waits for the plan's last execute (and for nothing else on the device: a status read or a download must not stall on
-// a collective or on another plan running on some other stream).
-int wait_plan_done(sls_plan* pl) {
-  if (pl->last_done) {
-    hipError_t e = hipEventSynchronize(pl->last_done);
-    if (e != hipSuccess) return hipfail(pl->ctx, e, "hipEventSynchronize (plan done)");
-  }
   return 0;
 }
 
@@ -730,21 +596,7 @@ int sls_shard_groups(const sls_dims* dims, const sls_plant* P, const sls_csc_boo
   std::vector<double> cost;
   rc = group_costs(in, cost, msg);
   if (rc) return fail(nullptr, rc, msg);
-  const int64_t ng = (int64_t)cost.size();
-  double total = 0; for (double c : cost) total += c;
-  cuts[0] = 0;
-  double acc = 0; int64_t g = 0;
-  for (int s = 1; s < nshards; ++s) {
-    const double target = total * s / nshards;
-    while (g < ng && acc + 0.5 * cost[g] < target) { acc += cost[g]; ++g; }
-    // leave at least one group for every remaining shard when possible
-    const int64_t max_g = ng - (nshards - s) > 0 ? ng - (nshards - s) : 0;
-    if (g > max_g) g = max_g;
-    if (g < cuts[s - 1]) g = cuts[s - 1];
-    cuts[s] = g;
-    acc = 0; for (int64_t q = 0; q < g; ++q) acc += cost[q];
-  }
-  cuts[nshards] = ng;
+  balanced_cuts(cost, nshards, cuts);
   return 0;
 }
 
@@ -773,14 +625,6 @@ int sls_h2_sf_packed_layout(const sls_dims* dims, const sls_plant* P, const sls_
   return 0;
 }
 
-// want_packed = false (the one-device drop-in call, which only ever runs packed = 0) skips the packed numbering on the host
-// and its 4 B/variable table on the device.  Everything that steers a plan's construction is an explicit argument (no
-// mutable context state, no environment writes): a flag left on by an early return would silently re-route later plans.
-struct PlanOpts {
-  bool force_tile = false;                          // every column on the tile kernel (the refinement pass)
-  const std::vector<int64_t>* pk_override = nullptr; // with force_tile: packed bases of the subproblems inside the refined plan's packed array
-  int host_tables = -1;                             // mask / destination tables: 1 built on the host, 0 expanded on the device, -1 = SLS_HOST_TABLES decides
-};
 struct DeviceTables {            // device-resident symbolic route: tables built on the device, owned by the plan
   const int32_t* d_idx = nullptr;
   const uint64_t* d_cmask = nullptr;
@@ -788,9 +632,6 @@ struct DeviceTables {            // device-resident symbolic route: tables built
   const int64_t* d_coff = nullptr;
   double t_symbolic_s = 0.0;     // device + host time of the symbolic route (replaces the host pass's share)
 };
-static int plan_create(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx,
-                       const sls_csc_bool* Su, int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols,
-                       int64_t group_begin, int64_t group_end, bool want_packed, const PlanOpts& opt, sls_plan** plan_out);
 static int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_plan* pl, double t0, bool want_packed, const PlanOpts& opt,
                        const DeviceTables* dt, sls_plan** plan_out);
 
@@ -800,9 +641,10 @@ int sls_h2_sf_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_p
   return plan_create(ctx, dev_slot, dims, P, Sx, Su, ngroups, group_ptr, group_cols, group_begin, group_end, true, PlanOpts{}, plan_out);
 }
 
-static int plan_create(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx,
-                       const sls_csc_bool* Su, int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols,
-                       int64_t group_begin, int64_t group_end, bool want_packed, const PlanOpts& opt, sls_plan** plan_out) {
+// (extern "C++": declared in sls_plan.h with C++ linkage, defined here inside the extern "C" block of the ABI)
+extern "C++" int sls::plan_create(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx,
+                                  const sls_csc_bool* Su, int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols,
+                                  int64_t group_begin, int64_t group_end, bool want_packed, const PlanOpts& opt, sls_plan** plan_out) {
   if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
   if (!plan_out) return fail(ctx, SLS_EINVAL, "null plan_out");
   *plan_out = nullptr;
@@ -1080,8 +922,8 @@ static int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_pla
 // sets per column (count pass), exclusive prefixes over the columns (the CSC positions), then index sets, compact bit masks
 // and first destinations (fill pass), expanded into the kernels' tables by the same expand_tables_kernel as the host route.
 // Over PCIe: the plant (KBs), 24 B per column of sizes coming back, 64 B per column of descriptors going up.
-static int plan_create_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, int64_t d, double alpha,
-                                 sls_plan** plan_out) {
+extern "C++" int sls::plan_create_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, int64_t d, double alpha,
+                                            sls_plan** plan_out) {
   if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
   if (!plan_out) return fail(ctx, SLS_EINVAL, "null plan_out");
   *plan_out = nullptr;
@@ -1298,76 +1140,6 @@ static int plan_create_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dim
 int sls_h2_sf_plan_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, int64_t d, double alpha,
                              sls_plan** plan_out) {
   return plan_create_localized(ctx, dev_slot, dims, P, d, alpha, plan_out);
-}
-
-int sls_h2_sf_solve_localized(sls_ctx* ctx, const sls_dims* dims, const sls_plant* P, int64_t d, double alpha,
-                              double* const* phix_vals, double* const* phiu_vals, int32_t* col_status, sls_stats* stats) {
-  if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
-  if (!phix_vals || !phiu_vals) return fail(ctx, SLS_EINVAL, "null output arrays");
-  sls_plan* pl = nullptr;
-  int rc = plan_create_localized(ctx, 0, dims, P, d, alpha, &pl);
-  if (rc) return rc;
-  double* dv = nullptr;
-  auto cleanup = [&]() { if (dv) sls_plan_free_values(pl, dv); sls_plan_destroy(pl); };
-  rc = sls_plan_alloc_values(pl, 0, &dv);
-  if (rc) { cleanup(); return rc; }
-  sls_stats st{};
-  st.n_devices = 1;
-  st.t_symbolic_s = pl->info.t_symbolic_s; st.t_upload_s = pl->info.t_upload_s;
-  const double t0 = now_s();
-  rc = sls_plan_execute(pl, pl->stream, dv, 0);
-  if (rc == 0) rc = sls_plan_synchronize(pl, pl->stream);
-  if (rc) { cleanup(); return rc; }
-  const double t1 = now_s();
-  st.t_solve_s = t1 - t0;
-  if (ctx->want_objective) {
-    ctx->obj_state = 0;
-    ctx->last_objective.assign((size_t)pl->info.n_subproblems, 0.0);
-    rc = sls_plan_fetch_objective(pl, dv, 0, ctx->last_objective.data(), &ctx->last_total);
-    if (rc) { cleanup(); return rc; }
-    ctx->obj_state = 1;
-  }
-  rc = sls_plan_download(pl, dv, phix_vals, phiu_vals);
-  if (rc) { cleanup(); return rc; }
-  const int64_t ns = pl->info.n_subproblems;
-  std::vector<int32_t> stt(ns), its(ns); std::vector<double> res(ns);
-  rc = sls_plan_fetch_status(pl, stt.data(), res.data(), its.data());
-  if (rc) { cleanup(); return rc; }
-  for (int64_t q = 0; q < ns; ++q) {
-    if (col_status) col_status[q] = stt[q];
-    if (stt[q] != SLS_COL_OK && stt[q] != SLS_COL_TRIVIAL) st.n_not_ok++;
-    else st.max_residual = std::max(st.max_residual, res[q]);
-    st.max_iters = std::max(st.max_iters, its[q]);
-  }
-  const Symbolic& S = pl->sym;
-  st.n_subproblems = ns; st.n_free = S.n_packed; st.n_values_x = S.off_x[S.T]; st.n_values_u = S.n_values - S.off_x[S.T];
-  st.max_nx = S.max_n; st.max_nu = S.max_m; st.flops_alg = S.flops_alg; st.bytes_alg = S.bytes_alg;
-  st.t_download_s = now_s() - t1;
-  cleanup();
-  if (stats) *stats = st;
-  return (int)std::min<int64_t>(st.n_not_ok, 0x7fffffff);
-}
-
-/* diagnostics (include/sls_mi355x_debug.h): the tables of a plan built by the device-resident route, for the bit-for-bit
-   comparison with the host route's (sls_debug_plan_tables) */
-int sls_debug_plan_tables_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, int64_t d, double alpha,
-                                    int64_t* md_total, uint8_t* mask_out, int32_t* dest_out, int64_t* n_idx, int32_t* idx_out) {
-  if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
-  sls_plan* pl = nullptr;
-  int rc = plan_create_localized(ctx, dev_slot, dims, P, d, alpha, &pl);
-  if (rc) return rc;
-  const int64_t n = pl->sym.md_total;
-  int64_t ni = 0;
-  for (const SubDesc& sd : pl->sym.subs) ni += sd.n + sd.m;
-  if (md_total) *md_total = n;
-  if (n_idx) *n_idx = ni;
-  hipError_t e = hipSuccess;
-  if (n > 0 && mask_out) e = hipMemcpy(mask_out, pl->kp.mask_pool, (size_t)n, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && n > 0 && dest_out) e = hipMemcpy(dest_out, pl->d_dest, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && ni > 0 && idx_out) e = hipMemcpy(idx_out, pl->kp.idx_pool, (size_t)ni * sizeof(int32_t), hipMemcpyDeviceToHost);
-  sls_plan_destroy(pl);
-  if (e != hipSuccess) return hipfail(ctx, e, "hipMemcpy D2H (tables)");
-  return 0;
 }
 
 int sls_plan_get_info(const sls_plan* plan, sls_plan_info* info) {
@@ -1789,8 +1561,6 @@ int sls_plan_packed_dest(const sls_plan* plan, int64_t* dest) {
   return 0;
 }
 
-static int fetch_status_raw(sls_plan* plan, int32_t* col_status, double* residual, int32_t* iters);
-
 int sls_plan_fetch_status(sls_plan* plan, int32_t* col_status, double* residual, int32_t* iters) {
   int rc = fetch_status_raw(plan, col_status, residual, iters);
   if (rc || !plan->refine) return rc;
@@ -1809,7 +1579,7 @@ int sls_plan_fetch_status(sls_plan* plan, int32_t* col_status, double* residual,
   return 0;
 }
 
-static int fetch_status_raw(sls_plan* plan, int32_t* col_status, double* residual, int32_t* iters) {
+extern "C++" int sls::fetch_status_raw(sls_plan* plan, int32_t* col_status, double* residual, int32_t* iters) {
   if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
   HIPCHK(plan->ctx, hipSetDevice(plan->dev));
   if (int rc = wait_plan_done(plan)) return rc;
@@ -1892,36 +1662,6 @@ int sls_ctx_last_objective(sls_ctx* ctx, double* col_objective, int64_t n, doubl
   if (n != (int64_t)ctx->last_objective.size()) return fail(ctx, SLS_EINVAL, "sls_ctx_last_objective: n is not the number of subproblems of the last solve");
   if (col_objective) std::copy(ctx->last_objective.begin(), ctx->last_objective.end(), col_objective);
   if (total) *total = ctx->last_total;
-  return 0;
-}
-
-/* diagnostics (include/sls_mi355x_debug.h): the host twin of the device evaluation — symbolic pass with explicit tables, then
-   the same formulas from host arrays in one serial loop (csrc/sls_objective.cpp).  Needs no device. */
-int sls_debug_objective_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
-                             int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, const double* ridge_x,
-                             const double* ridge_u, const double* const* phix_vals, const double* const* phiu_vals,
-                             double* col_objective, double* total, int64_t* col_terms, double* col_abs) {
-  Inputs in{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
-  std::string msg;
-  int rc = validate_inputs(in, msg);
-  if (rc) return fail(nullptr, rc, msg);
-  if (!phix_vals || !phiu_vals) return fail(nullptr, SLS_EINVAL, "null value arrays");
-  in.reg_x = ridge_x; in.reg_u = ridge_u;
-  Symbolic S;
-  S.want_packed = false; S.compact = false;
-  std::vector<int64_t> gptr, gcols;
-  normalise_groups(in, gptr, gcols);
-  rc = build_symbolic(in, 0, (int64_t)gptr.size() - 1, S, msg);
-  if (rc) return fail(nullptr, rc, msg);
-  std::vector<double> vals((size_t)std::max<int64_t>(S.n_values, 1), 0.0);
-  for (int64_t t = 0; t < S.T; ++t) {
-    const int64_t nx = S.off_x[t + 1] - S.off_x[t], nu = S.off_u[t + 1] - S.off_u[t];
-    if ((nx > 0 && !phix_vals[t]) || (nu > 0 && !phiu_vals[t])) return fail(nullptr, SLS_EINVAL, "null phix_vals[t]/phiu_vals[t]");
-    if (nx > 0) std::copy(phix_vals[t], phix_vals[t] + nx, vals.begin() + S.off_x[t]);
-    if (nu > 0) std::copy(phiu_vals[t], phiu_vals[t] + nu, vals.begin() + S.off_u[t]);
-  }
-  rc = objective_host(S, (dims->flags & SLS_SOLVE_SUM_OF_NORMS) ? 1 : 0, vals.data(), col_objective, total, col_terms, col_abs, msg);
-  if (rc) return fail(nullptr, rc, msg);
   return 0;
 }
 
@@ -2016,263 +1756,11 @@ int sls_plan_fetch_residual(sls_plan* plan, const double* d_values, int packed, 
   return 0;
 }
 
-/* diagnostics (include/sls_mi355x_debug.h): the host twin of sls_plan_residual — symbolic pass with explicit tables, then the
-   same formulas from host arrays in one serial loop (csrc/sls_residual.cpp).  Needs no device. */
-int sls_debug_residual_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
-                            int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, const double* const* phix_vals,
-                            const double* const* phiu_vals, double* res_inf, double* halo_inf, double* res_l1, double* totals,
-                            int64_t* ent_terms, double* ent_abs, int64_t* l1_terms, double* l1_abs, int64_t* halo_ptr,
-                            int32_t* halo_rows, int64_t halo_cap) {
-  Inputs in{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
-  std::string msg;
-  int rc = validate_inputs(in, msg);
-  if (rc) return fail(nullptr, rc, msg);
-  if (!phix_vals || !phiu_vals) return fail(nullptr, SLS_EINVAL, "null value arrays");
-  Symbolic S;
-  S.want_packed = false; S.compact = false;
-  std::vector<int64_t> gptr, gcols;
-  normalise_groups(in, gptr, gcols);
-  rc = build_symbolic(in, 0, (int64_t)gptr.size() - 1, S, msg);
-  if (rc) return fail(nullptr, rc, msg);
-  std::vector<double> vals((size_t)std::max<int64_t>(S.n_values, 1), 0.0);
-  for (int64_t t = 0; t < S.T; ++t) {
-    const int64_t nx = S.off_x[t + 1] - S.off_x[t], nu = S.off_u[t + 1] - S.off_u[t];
-    if ((nx > 0 && !phix_vals[t]) || (nu > 0 && !phiu_vals[t])) return fail(nullptr, SLS_EINVAL, "null phix_vals[t]/phiu_vals[t]");
-    if (nx > 0) std::copy(phix_vals[t], phix_vals[t] + nx, vals.begin() + S.off_x[t]);
-    if (nu > 0) std::copy(phiu_vals[t], phiu_vals[t] + nu, vals.begin() + S.off_u[t]);
-  }
-  std::vector<int64_t> hp;
-  std::vector<int32_t> hr;
-  rc = residual_host(S, vals.data(), res_inf, halo_inf, res_l1, totals, ent_terms, ent_abs, l1_terms, l1_abs, &hp, &hr, msg);
-  if (rc) return fail(nullptr, rc, msg);
-  if (halo_ptr) std::copy(hp.begin(), hp.end(), halo_ptr);
-  if (halo_rows) {
-    if (halo_cap < (int64_t)hr.size()) return fail(nullptr, SLS_EINVAL, "sls_debug_residual_host: halo_rows is shorter than halo_ptr[n_subproblems]");
-    std::copy(hr.begin(), hr.end(), halo_rows);
-  }
-  return 0;
-}
-
-/* diagnostics (include/sls_mi355x_debug.h): the host twin of sls_plan_update_plant — the operator arrays of a plan of (A, B2),
-   the value map and zero marks, then apply_operator_update with the new nzval arrays.  Needs no device. */
-int sls_debug_operator_update_host(const sls_dims* dims, const sls_csc_f64* A, const sls_csc_f64* B2, const double* A_nzval,
-                                   const double* B2_nzval, double* A_val, double* At_val, double* B_val, double* Bt_val,
-                                   int32_t* row_pos, uint8_t* zero) {
-  Symbolic S;
-  std::string msg;
-  int rc = operator_csr_checked(dims, A, B2, S, msg);
-  if (rc) return fail(nullptr, rc, msg);
-  OperatorValueMap M;
-  build_operator_value_map(S, M);
-  rc = apply_operator_update(S, M, A_nzval, B2_nzval, msg);
-  if (A_val) std::copy(S.A_csr.val.begin(), S.A_csr.val.end(), A_val);
-  if (At_val) std::copy(S.At_csr.val.begin(), S.At_csr.val.end(), At_val);
-  if (B_val) std::copy(S.B_csr.val.begin(), S.B_csr.val.end(), B_val);
-  if (Bt_val) std::copy(S.Bt_csr.val.begin(), S.Bt_csr.val.end(), Bt_val);
-  if (row_pos) std::copy(M.row_pos.begin(), M.row_pos.end(), row_pos);
-  if (zero) std::copy(M.zero.begin(), M.zero.end(), zero);
-  if (rc) return fail(nullptr, rc, msg);
-  return 0;
-}
-
-/* diagnostics (include/sls_mi355x_debug.h): the host twin of the marks sls_plan_track_changes keeps — the host symbolic pass
-   over all groups, then mark_affected_host with the caller's changed flags.  Needs no device. */
-int sls_debug_affected_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su, int64_t ngroups,
-                            const int64_t* group_ptr, const int64_t* group_cols, const uint8_t* changed_A, const uint8_t* changed_B2,
-                            uint8_t* dirty) {
-  if (!dirty) return fail(nullptr, SLS_EINVAL, "null argument");
-  Inputs in{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
-  std::string msg;
-  int rc = validate_inputs(in, msg);
-  if (rc) return fail(nullptr, rc, msg);
-  std::vector<int64_t> gptr, gcols;
-  normalise_groups(in, gptr, gcols);
-  Symbolic S;
-  S.want_packed = false; S.compact = false;
-  rc = build_symbolic(in, 0, (int64_t)gptr.size() - 1, S, msg);
-  if (rc) return fail(nullptr, rc, msg);
-  OperatorValueMap M;
-  build_operator_value_map(S, M);
-  std::fill(dirty, dirty + S.subs.size(), (uint8_t)0);
-  rc = mark_affected_host(S, M, changed_A, changed_B2, dirty, msg);
-  if (rc) return fail(nullptr, rc, msg);
-  return 0;
-}
-
 int sls_plan_describe(const sls_plan* plan, char* buf, int64_t buflen) {
   if (!plan || !buf || buflen <= 0) return fail(nullptr, SLS_EINVAL, "null argument");
   std::string d;
   for (const auto& L : plan->launches) d += describe_launch(L);
   std::snprintf(buf, (size_t)buflen, "%s", d.c_str());
-  return 0;
-}
-
-/* diagnostics (include/sls_mi355x_debug.h): the launch list sls_plan_describe would print for a plan of these inputs on a
- * device with `ncu` compute units — symbolic pass + kernel selection on the host, no context, no device */
-int sls_debug_describe_launches(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
-                                int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, int64_t group_begin,
-                                int64_t group_end, int ncu, char* buf, int64_t buflen) {
-  if (!buf || buflen <= 0 || ncu <= 0) return fail(nullptr, SLS_EINVAL, "bad argument");
-  Inputs in{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
-  std::string msg;
-  int rc = validate_inputs(in, msg);
-  if (rc) return fail(nullptr, rc, msg);
-  Symbolic S;
-  rc = build_symbolic(in, group_begin, group_end, S, msg);
-  if (rc) return fail(nullptr, rc, msg);
-  RoutingResult route;
-  rc = build_launch_list(S, (int)S.T, (dims->flags & SLS_SOLVE_SUM_OF_NORMS) ? 1 : 0, ncu, false, RoutingKnobs::from_env(), route, msg);
-  if (rc) return fail(nullptr, rc, msg);
-  std::string d;
-  for (const LaunchSpec& L : route.launches) d += describe_launch(L);
-  std::snprintf(buf, (size_t)buflen, "%s", d.c_str());
-  return 0;
-}
-
-/* diagnostics (include/sls_mi355x_debug.h): per-subproblem phase cycle counters when SLS_PHASE_TIMERS is set */
-int sls_plan_debug_phase_cycles(sls_plan* plan, unsigned long long* out /* n_subproblems*8 */) {
-  if (!plan || !out) return fail(nullptr, SLS_EINVAL, "null argument");
-  if (!plan->kp.dbg) return fail(plan->ctx, SLS_EINVAL, "phase timers are off (set SLS_PHASE_TIMERS=1 before planning)");
-  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
-  if (int rc = wait_plan_done(plan)) return rc;
-  HIPCHK(plan->ctx, hipMemcpy(out, plan->kp.dbg, (size_t)plan->kp.nsub * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-/* diagnostics (include/sls_mi355x_debug.h): invert one dense SPD matrix (host, n×n row-major) with the tile kernel's blocked
- * symmetric MFMA sweep — the unit test of the FP64 MFMA operand / result lane maps (tests/test_gpu_tile.py) */
-int sls_debug_tile_invert(sls_ctx* ctx, int dev_slot, int n, const double* h_A, double* h_out, int mlds) {
-  if (!ctx || !h_A || !h_out || n <= 0) return fail(ctx, SLS_EINVAL, "bad argument");
-  if (dev_slot < 0 || dev_slot >= (int)ctx->devs.size()) return fail(ctx, SLS_EINVAL, "dev_slot out of range");
-  HIPCHK(ctx, hipSetDevice(ctx->devs[dev_slot]));
-  const size_t nn = (size_t)n * n, wsd = (size_t)tile_ht(tile_nt(n)) * 256;
-  double *dA = nullptr, *dO = nullptr, *dW = nullptr;
-  HIPCHK(ctx, hipMalloc(&dA, nn * 8));
-  hipError_t e = hipMalloc(&dO, nn * 8);
-  if (e == hipSuccess) e = hipMalloc(&dW, wsd * 8);
-  if (e == hipSuccess) e = hipMemcpy(dA, h_A, nn * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = launch_tile_invert(dA, n, dW, dO, mlds != 0, nullptr);
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  if (e == hipSuccess) e = hipMemcpy(h_out, dO, nn * 8, hipMemcpyDeviceToHost);
-  (void)hipFree(dA); (void)hipFree(dO); (void)hipFree(dW);
-  if (e != hipSuccess) return hipfail(ctx, e, "sls_debug_tile_invert");
-  return 0;
-}
-
-/* diagnostics (include/sls_mi355x_debug.h): the mask / destination tables of a one-device plan as the solve kernels see them,
-   built on the host (host_tables = 1) or expanded on the device from the compact form (0).  Call with null outputs for the
-   length.  `was_compact` reports whether the device expansion actually ran (0 when some column is not regular). */
-int sls_debug_plan_tables(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx,
-                          const sls_csc_bool* Su, int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols,
-                          int host_tables, int64_t* md_total, uint8_t* mask_out, int32_t* dest_out, int32_t* was_compact) {
-  if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
-  sls_plan* pl = nullptr;
-  Inputs in{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
-  std::vector<int64_t> gptr, gcols;
-  std::string msg;
-  int rc = validate_inputs(in, msg);
-  if (rc) return fail(ctx, rc, msg);
-  normalise_groups(in, gptr, gcols);
-  PlanOpts opt; opt.host_tables = host_tables ? 1 : 0;
-  rc = plan_create(ctx, dev_slot, dims, P, Sx, Su, ngroups, group_ptr, group_cols, 0, (int64_t)gptr.size() - 1, false, opt, &pl);
-  if (rc) return rc;
-  const int64_t n = pl->sym.md_total;
-  if (md_total) *md_total = n;
-  if (was_compact) *was_compact = pl->sym.compact ? 1 : 0;
-  hipError_t e = hipSuccess;
-  if (n > 0 && mask_out) e = hipMemcpy(mask_out, pl->kp.mask_pool, (size_t)n, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && n > 0 && dest_out) e = hipMemcpy(dest_out, pl->d_dest, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
-  sls_plan_destroy(pl);
-  if (e != hipSuccess) return hipfail(ctx, e, "hipMemcpy D2H (tables)");
-  return 0;
-}
-
-/* diagnostics (include/sls_mi355x_debug.h): copy `count` doubles of the factor workspace, starting at `offset`, to the host */
-int sls_plan_debug_read_workspace(sls_plan* plan, int64_t offset, int64_t count, double* out) {
-  if (!plan || !out || offset < 0 || count < 0) return fail(nullptr, SLS_EINVAL, "bad argument");
-  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
-  if (int rc = wait_plan_done(plan)) return rc;
-  HIPCHK(plan->ctx, hipMemcpy(out, plan->kp.fac_ws + offset, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-/* diagnostics (include/sls_mi355x_debug.h): the prepared records of the four-wave columns, in col_status order */
-int sls_plan_debug_twisted4_tables(sls_plan* plan, int64_t* n_columns, int32_t* caps, int64_t* columns, int32_t* counts,
-                                   int32_t* indices, double* values, uint64_t* bits) {
-  if (!plan || !n_columns) return fail(nullptr, SLS_EINVAL, "null argument");
-  if (!plan->t4_records) return fail(plan->ctx, SLS_EINVAL, "this plan has no four-wave launch");
-  const KernelParams& kp = plan->kp;
-  *n_columns = plan->t4_records;
-  if (caps) { caps[0] = kp.w_nzA; caps[1] = kp.w_nzAc; caps[2] = kp.w_nzB; caps[3] = kp.w_nzBc; }
-  if (!columns && !counts && !indices && !values && !bits) return 0;
-  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
-  std::vector<unsigned char> host((size_t)(plan->t4_records * plan->t4_stride));
-  HIPCHK(plan->ctx, hipMemcpy(host.data(), plan->d_t4, host.size(), hipMemcpyDeviceToHost));
-  std::vector<std::pair<int64_t, int64_t>> by_col;          // (col_status index, record)
-  for (const auto& L : plan->launches) {
-    if (!(L.kind == LaunchKind::Twisted && L.four)) continue;
-    for (int s = 0; s < L.nsub; ++s)
-      by_col.emplace_back(plan->sym.subs[(size_t)plan->sym.order[(size_t)L.order_off + s]].out_index, L.t4_off + s);
-  }
-  std::sort(by_col.begin(), by_col.end());
-  const size_t ne = (size_t)twisted4_record_entries(kp.w_nzA, kp.w_nzAc, kp.w_nzB, kp.w_nzBc);
-  for (size_t i = 0; i < by_col.size(); ++i) {
-    const unsigned char* rec = host.data() + (size_t)by_col[i].second * plan->t4_stride;
-    if (columns) columns[i] = by_col[i].first;
-    if (bits) std::memcpy(bits + 2 * i, rec, 16);
-    if (counts) std::memcpy(counts + 4 * i, rec + 16, 16);
-    if (values) std::memcpy(values + ne * i, rec + kT4RecHeader, ne * 8);
-    if (indices) std::memcpy(indices + ne * i, rec + kT4RecHeader + ne * 8, ne * 4);
-  }
-  return 0;
-}
-
-/* diagnostics (include/sls_mi355x_debug.h): δ, slot flags and static blocks of the four-wave columns, in col_status order */
-int sls_plan_debug_twisted4_static(sls_plan* plan, int64_t* n_columns, int32_t* n_slots, int64_t* offsets, double* delta,
-                                   uint8_t* valid, double* blocks) {
-  if (!plan || !n_columns) return fail(nullptr, SLS_EINVAL, "null argument");
-  if (!plan->t4_records) return fail(plan->ctx, SLS_EINVAL, "this plan has no four-wave launch");
-  if (!plan->d_t4s) return fail(plan->ctx, SLS_EINVAL, "this plan keeps no static blocks (its launches rebuild them)");
-  const KernelParams& kp = plan->kp;
-  const int64_t slots = kp.T + 1;
-  *n_columns = plan->t4_records;
-  if (n_slots) *n_slots = (int32_t)slots;
-  struct Col { int64_t out_index, record, first, doubles; };
-  std::vector<Col> by_col;
-  for (const auto& L : plan->launches) {
-    if (!(L.kind == LaunchKind::Twisted && L.four)) continue;
-    for (int s = 0; s < L.nsub; ++s)
-      by_col.push_back({plan->sym.subs[(size_t)plan->sym.order[(size_t)L.order_off + s]].out_index, L.t4_off + s,
-                        L.t4s_off + s * L.t4s_stride, L.t4s_stride});
-  }
-  std::sort(by_col.begin(), by_col.end(), [](const Col& a, const Col& b) { return a.out_index < b.out_index; });
-  if (offsets) {
-    int64_t o = 0;
-    for (size_t i = 0; i < by_col.size(); ++i) { offsets[i] = o; o += by_col[i].doubles; }
-    offsets[by_col.size()] = o;
-  }
-  if (!delta && !valid && !blocks) return 0;
-  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
-  HIPCHK(plan->ctx, hipDeviceSynchronize());      // a plant update may still be rewriting the pool on the caller's stream
-  if (delta || valid) {
-    std::vector<unsigned char> host((size_t)(plan->t4_records * plan->t4_stride));
-    HIPCHK(plan->ctx, hipMemcpy(host.data(), plan->d_t4, host.size(), hipMemcpyDeviceToHost));
-    const size_t tail = (size_t)twisted4_record_tail(kp.w_nzA, kp.w_nzAc, kp.w_nzB, kp.w_nzBc);
-    for (size_t i = 0; i < by_col.size(); ++i) {
-      const unsigned char* rec = host.data() + (size_t)by_col[i].record * plan->t4_stride + tail;
-      if (delta) std::memcpy(delta + i, rec, 8);
-      if (valid) std::memcpy(valid + (size_t)slots * i, rec + 8, (size_t)slots);
-    }
-  }
-  if (blocks) {
-    std::vector<double> host((size_t)plan->t4s_doubles);
-    HIPCHK(plan->ctx, hipMemcpy(host.data(), plan->d_t4s, host.size() * sizeof(double), hipMemcpyDeviceToHost));
-    int64_t o = 0;
-    for (size_t i = 0; i < by_col.size(); ++i) {
-      std::memcpy(blocks + o, host.data() + by_col[i].first, (size_t)by_col[i].doubles * sizeof(double));
-      o += by_col[i].doubles;
-    }
-  }
   return 0;
 }
 
@@ -2357,8 +1845,7 @@ void sls_plan_destroy(sls_plan* plan) {
   if (!plan) return;
   if (plan->refine) { sls_plan_destroy(plan->refine); plan->refine = nullptr; }
   (void)hipSetDevice(plan->dev);
-  bool ctx_alive;
-  { std::lock_guard<std::mutex> l(g_err_mu); ctx_alive = g_live_ctx.count(plan->ctx) > 0; }
+  const bool ctx_alive = ctx_is_live(plan->ctx);
   // a stream lent by the context (slot stream, refinement stream) died with it: sls_destroy has waited for nothing, hipFree below does
   const bool stream_gone = !ctx_alive && (plan->streams_borrowed || plan->stream_external);
   if (plan->stream && !stream_gone) (void)hipStreamSynchronize(plan->stream);
@@ -2396,16 +1883,11 @@ int sls_scatter_f64(sls_ctx* ctx, int dev_slot, void* hip_stream, const double* 
   return 0;
 }
 
-// Refinement: columns the one-wave / twisted kernels left at a residual between 1e-11 and the acceptance level after four or
-// more passes sit on a near-singular constraint matrix — their plain multiplier iteration contracts slowly there, and Φ is
-// only determined to residual/σ_min (fuzz seed 77: residual 4e-10, σ_min 2e-6, |ΔΦ| 2e-4 with status OK).  The tile kernel's
-// minimal-residual iteration takes the same columns to 1e-13: their groups get a second plan on it (PlanOpts::force_tile), run
-// into the same device array after the first, and attached to `pl` so that later executes and status reads include it.
-// Waits for `stream`; costs one status read when nothing qualifies.
-static int attach_refinement(sls_plan* pl, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
-                             int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, hipStream_t stream,
-                             double* d_values, int64_t* n_refined, std::vector<int32_t>& stt, std::vector<double>& res,
-                             std::vector<int32_t>& its, int packed) {
+// Refinement (which columns and why: select_refinement_groups, sls_dropin_host.h; contract: sls_plan.h)
+extern "C++" int sls::attach_refinement(sls_plan* pl, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx,
+                                        const sls_csc_bool* Su, int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols,
+                                        hipStream_t stream, double* d_values, int64_t* n_refined, std::vector<int32_t>& stt,
+                                        std::vector<double>& res, std::vector<int32_t>& its, int packed) {
   sls_ctx* ctx = pl->ctx;
   *n_refined = 0;
   const int64_t ns = pl->info.n_subproblems;
@@ -2421,12 +1903,8 @@ static int attach_refinement(sls_plan* pl, const sls_dims* dims, const sls_plant
   normalise_groups(in0, gptr_all, gcols_all);
   if (pl->gend > (int64_t)gptr_all.size() - 1 || gptr_all[pl->gend] - gptr_all[pl->gbeg] != ns)
     return fail(ctx, SLS_EINVAL, "sls_plan_refine: the group list does not match the one this plan was built from");
-  std::vector<int64_t> rg_ptr{0}, rg_cols, rg_dst;
-  const int64_t q0 = gptr_all[pl->gbeg];
-  // columns of the twisted kernels (latency regime: at most one per CU): the two-ended elimination meets a near-singular
-  // direction in its middle block, where the multiplier iteration contracts worse than in the one-ended kernels (tools/fuzz_h2.py
-  // seed 235, column 52: residual 0.4–0.7 after six passes against 5e-9 in the one-wave kernel and 4e-10 in the tile kernel) —
-  // a column they flag infeasible gets the tile kernel's verdict
+  std::vector<int32_t> cls((size_t)ns);
+  for (int64_t q = 0; q < ns; ++q) cls[(size_t)q] = pl->sym.subs[q].cls;
   std::vector<char> on_twisted((size_t)ns, 0);
   for (const auto& L : pl->launches)
     if (L.kind == LaunchKind::Twisted)
@@ -2434,17 +1912,9 @@ static int attach_refinement(sls_plan* pl, const sls_dims* dims, const sls_plant
         const int64_t q = pl->sym.order[(size_t)L.order_off + i];
         if (q >= 0 && q < ns) on_twisted[(size_t)q] = 1;
       }
-  for (int64_t g = pl->gbeg; g < pl->gend; ++g) {
-    bool want = false;
-    for (int64_t q = gptr_all[g] - q0; q < gptr_all[g + 1] - q0; ++q) {
-      if (pl->sym.subs[q].cls < 0) continue;                     // solved by the tile kernel already: nothing to gain
-      want = want || (stt[q] == SLS_COL_NOTCONV) || (stt[q] == SLS_COL_OK && its[q] >= 4 && res[q] > 1e-11) ||
-             (stt[q] == SLS_COL_INFEASIBLE && its[q] >= 3 && (res[q] < 1e-6 || on_twisted[(size_t)q]));      // (flagged at the second pass: the residual did not move at all — a plain infeasible column, on any kernel)
-    }
-    if (!want) continue;
-    for (int64_t q = gptr_all[g]; q < gptr_all[g + 1]; ++q) { rg_cols.push_back(gcols_all[q] + dims->index_base); rg_dst.push_back(q - q0); }
-    rg_ptr.push_back((int64_t)rg_cols.size());
-  }
+  std::vector<int64_t> rg_ptr, rg_cols, rg_dst;
+  select_refinement_groups(pl->gbeg, pl->gend, gptr_all, gcols_all, dims->index_base, cls.data(), on_twisted.data(), stt.data(), its.data(),
+                           res.data(), rg_ptr, rg_cols, rg_dst);
   if (rg_dst.empty()) return 0;
   const int64_t nrg = (int64_t)rg_ptr.size() - 1;
   sls_plan* rp = nullptr;
@@ -2479,349 +1949,6 @@ int sls_plan_refine(sls_plan* plan, const sls_dims* dims, const sls_plant* P, co
   int rc = attach_refinement(plan, dims, P, Sx, Su, ngroups, group_ptr, group_cols, reinterpret_cast<hipStream_t>(hip_stream), d_values, &nr,
                              stt, res, its, packed);
   if (n_refined) *n_refined = nr;
-  return rc;
-}
-
-// A column listed in several groups: the reference solves it once per group, each time with that group's index sets, and ADDS
-// the contributions (Φ̃ += [Φₓ Φᵤ] per group and the (+) fold, src/synthesis.jl:24,67).  A plan gives every subproblem its own
-// destinations, so the drop-in call cuts such a group list into LAYERS in which every column appears at most once (a group
-// goes to the first layer none of its columns has been used in), solves the layers one after the other and sums them on the
-// host.  Returns -1000 when the list needs no layering (the caller goes on), else the result of the whole call.
-static int solve_overlapping_groups(sls_ctx* ctx, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
-                                    int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, double* const* phix_vals,
-                                    double* const* phiu_vals, int32_t* col_status, sls_stats* stats) {
-  constexpr int kNoLayers = -1000;
-  if (!dims || ngroups <= 0 || !group_ptr || !group_cols || !Sx || !Su || dims->Nx <= 0 || dims->T <= 0) return kNoLayers;
-  const int64_t Nx = dims->Nx, T = dims->T; const int b = dims->index_base;
-  std::vector<int32_t> next_layer((size_t)Nx, 0), layer_of((size_t)ngroups, 0);
-  int nlayers = 1;
-  for (int64_t g = 0; g < ngroups; ++g) {
-    if (group_ptr[g + 1] < group_ptr[g]) return kNoLayers;                 // malformed: the regular path reports it
-    int32_t lay = 0;
-    for (int64_t k = group_ptr[g]; k < group_ptr[g + 1]; ++k) {
-      const int64_t c = group_cols[k] - b;
-      if (c < 0 || c >= Nx) return kNoLayers;
-      lay = std::max(lay, next_layer[(size_t)c]);
-    }
-    for (int64_t k = group_ptr[g]; k < group_ptr[g + 1]; ++k) next_layer[(size_t)(group_cols[k] - b)] = lay + 1;
-    layer_of[(size_t)g] = lay; nlayers = std::max(nlayers, lay + 1);
-  }
-  if (nlayers == 1) return kNoLayers;
-  for (int64_t t = 0; t < T; ++t)
-    if (!Sx[t].colptr || !Su[t].colptr) return kNoLayers;
-  std::vector<int64_t> nnzx(T), nnzu(T);
-  for (int64_t t = 0; t < T; ++t) { nnzx[t] = Sx[t].colptr[Nx] - b; nnzu[t] = Su[t].colptr[Nx] - b; }
-  sls_stats tot{}; int64_t not_ok = 0;
-  std::vector<std::vector<double>> tx(T), tu(T);
-  std::vector<double*> px(T), pu(T);
-  for (int lay = 0; lay < nlayers; ++lay) {
-    std::vector<int64_t> lptr{0}, lcols, lstat_pos;
-    for (int64_t g = 0; g < ngroups; ++g) {
-      if (layer_of[(size_t)g] != lay) continue;
-      for (int64_t k = group_ptr[g]; k < group_ptr[g + 1]; ++k) { lcols.push_back(group_cols[k]); lstat_pos.push_back(k); }
-      lptr.push_back((int64_t)lcols.size());
-    }
-    double* const* ox = phix_vals; double* const* ou = phiu_vals;
-    if (lay > 0) {
-      for (int64_t t = 0; t < T; ++t) {
-        tx[t].assign((size_t)std::max<int64_t>(nnzx[t], 1), 0.0); tu[t].assign((size_t)std::max<int64_t>(nnzu[t], 1), 0.0);
-        px[t] = tx[t].data(); pu[t] = tu[t].data();
-      }
-      ox = px.data(); ou = pu.data();
-    }
-    std::vector<int32_t> lst(lcols.size(), 0);
-    sls_stats ls{};
-    const int rc = sls_h2_sf_solve(ctx, dims, P, Sx, Su, (int64_t)lptr.size() - 1, lptr.data(), lcols.data(), ox, ou, lst.data(), &ls);
-    if (rc < 0) return rc;
-    if (lay > 0)
-      for (int64_t t = 0; t < T; ++t) {
-        for (int64_t i = 0; i < nnzx[t]; ++i) phix_vals[t][i] += tx[t][(size_t)i];
-        for (int64_t i = 0; i < nnzu[t]; ++i) phiu_vals[t][i] += tu[t][(size_t)i];
-      }
-    if (col_status) for (size_t q = 0; q < lst.size(); ++q) col_status[lstat_pos[q]] = lst[q];
-    not_ok += ls.n_not_ok;
-    tot.n_subproblems += ls.n_subproblems; tot.n_not_ok += ls.n_not_ok; tot.n_free += ls.n_free; tot.n_refined += ls.n_refined;
-    tot.n_values_x = ls.n_values_x; tot.n_values_u = ls.n_values_u; tot.n_devices = ls.n_devices;
-    tot.max_nx = std::max(tot.max_nx, ls.max_nx); tot.max_nu = std::max(tot.max_nu, ls.max_nu); tot.max_iters = std::max(tot.max_iters, ls.max_iters);
-    tot.max_residual = std::max(tot.max_residual, ls.max_residual);
-    tot.flops_alg += ls.flops_alg; tot.bytes_alg += ls.bytes_alg; tot.t_symbolic_s += ls.t_symbolic_s; tot.t_upload_s += ls.t_upload_s;
-    tot.t_solve_s += ls.t_solve_s; tot.t_download_s += ls.t_download_s;
-  }
-  if (stats) *stats = tot;
-  return (int)std::min<int64_t>(not_ok, 0x7fffffff);
-}
-
-int sls_h2_sf_solve(sls_ctx* ctx, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx,
-                    const sls_csc_bool* Su, int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols,
-                    double* const* phix_vals, double* const* phiu_vals, int32_t* col_status, sls_stats* stats) {
-  if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
-  if (!phix_vals || !phiu_vals) return fail(ctx, SLS_EINVAL, "null output arrays");
-  {
-    const int lrc = solve_overlapping_groups(ctx, dims, P, Sx, Su, ngroups, group_ptr, group_cols, phix_vals, phiu_vals, col_status, stats);
-    if (lrc != -1000) {
-      if (ctx->want_objective) { ctx->obj_state = lrc >= 0 ? 2 : 0; ctx->last_objective.clear(); }   // a sum of layers: no per-column objective
-      return lrc;
-    }
-  }
-  const int ndev = (int)ctx->devs.size();
-  std::vector<int64_t> cuts(ndev + 1, 0);
-  int rc = sls_shard_groups(dims, P, Sx, Su, ngroups, group_ptr, group_cols, ndev, cuts.data());
-  if (rc) { ctx->err = sls_last_error(nullptr); return rc; }
-
-  sls_stats st{};
-  st.n_devices = ndev;
-  std::vector<sls_plan*> plans(ndev, nullptr);
-  std::vector<double*> dvals(ndev, nullptr);
-  auto cleanup = [&]() {
-    for (int i = 0; i < ndev; ++i) {
-      if (plans[i]) { if (dvals[i]) sls_plan_free_values(plans[i], dvals[i]); sls_plan_destroy(plans[i]); }
-    }
-  };
-  for (int i = 0; i < ndev; ++i) {
-    rc = plan_create(ctx, i, dims, P, Sx, Su, ngroups, group_ptr, group_cols, cuts[i], cuts[i + 1], ndev > 1, PlanOpts{}, &plans[i]);
-    if (rc) { cleanup(); return rc; }
-    st.t_symbolic_s += plans[i]->info.t_symbolic_s;
-    st.t_upload_s += plans[i]->info.t_upload_s;
-    // one device: the kernels write straight into the mask-order array (no unpack on the host); several devices: each
-    // shard comes back packed and is scattered into the caller's arrays
-    rc = sls_plan_alloc_values(plans[i], ndev == 1 ? 0 : 1, &dvals[i]);
-    if (rc) { cleanup(); return rc; }
-  }
-  const Symbolic& S0 = plans[0]->sym;
-  const int64_t T = S0.T;
-  // zero the caller's arrays (columns outside every group, masked-but-unowned entries)
-  for (int64_t t = 0; t < T; ++t) {
-    const int64_t nx = S0.off_x[t + 1] - S0.off_x[t], nu = S0.off_u[t + 1] - S0.off_u[t];
-    if ((nx > 0 && !phix_vals[t]) || (nu > 0 && !phiu_vals[t])) { cleanup(); return fail(ctx, SLS_EINVAL, "null phix_vals[t]/phiu_vals[t]"); }
-    if (ndev == 1) continue;        // one device: the whole (zero-initialised) device array is copied over them
-    if (nx > 0) std::memset(phix_vals[t], 0, (size_t)nx * sizeof(double));
-    if (nu > 0) std::memset(phiu_vals[t], 0, (size_t)nu * sizeof(double));
-  }
-  const double t0 = now_s();
-  for (int i = 0; i < ndev; ++i) {
-    rc = sls_plan_execute(plans[i], plans[i]->stream, dvals[i], ndev == 1 ? 0 : 1);   // each device on its own stream
-    if (rc) { cleanup(); return rc; }
-  }
-  for (int i = 0; i < ndev; ++i) {
-    rc = sls_plan_synchronize(plans[i], plans[i]->stream);
-    if (rc) { cleanup(); return rc; }
-  }
-  // Refinement (one device): columns the one-wave / twisted kernels left at a residual between 1e-11 and the acceptance level
-  // after four or more passes sit on a near-singular constraint matrix — their plain multiplier iteration contracts slowly
-  // there, and Φ is only determined to residual/σ_min (fuzz seed 77: residual 4e-10, σ_min 2e-6, |ΔΦ| 2e-4 with status OK).
-  // The tile kernel's minimal-residual iteration takes the same columns to 1e-13; their groups are solved once more on it,
-  // into the same device array, before anything is downloaded.  Costs one status read when nothing qualifies.
-  bool have_status0 = false;
-  const char* refine_env = sls_knob("SLS_REFINE");
-  std::vector<std::vector<int32_t>> stt_d(ndev), its_d(ndev); std::vector<std::vector<double>> res_d(ndev);
-  if (!(refine_env && refine_env[0] == '0') && !(dims->flags & SLS_SOLVE_SUM_OF_NORMS)) {
-    for (int i = 0; i < ndev; ++i) {
-      sls_plan* pl = plans[i];
-      int64_t nr = 0;
-      rc = attach_refinement(pl, dims, P, Sx, Su, ngroups, group_ptr, group_cols, pl->stream, dvals[i], &nr, stt_d[i], res_d[i], its_d[i], ndev > 1 ? 1 : 0);
-      if (rc) { cleanup(); return rc; }
-      st.n_refined += nr;
-    }
-    have_status0 = true;
-  }
-  const double t1 = now_s();
-  st.t_solve_s = t1 - t0;
-  if (ctx->want_objective) {
-    // after the last launch (refinement included), before the download: every device evaluates its shard, in col_status order
-    ctx->obj_state = 0;
-    ctx->last_objective.assign((size_t)S0.n_total_subproblems, 0.0);
-    double tot = 0.0;
-    for (int i = 0; i < ndev; ++i) {
-      double ti = 0.0;
-      rc = sls_plan_fetch_objective(plans[i], dvals[i], ndev == 1 ? 0 : 1, ctx->last_objective.data() + plans[i]->sym.first_sub_index, &ti);
-      if (rc) { cleanup(); return rc; }
-      tot += ti;
-    }
-    ctx->last_total = tot; ctx->obj_state = 1;
-  }
-  // D2H of each shard's packed values + host scatter into the per-t arrays
-  st.n_values_x = S0.off_x[T]; st.n_values_u = S0.n_values - S0.off_x[T];
-  std::vector<double> stage;
-  std::vector<int32_t> slice_of;          // value index → slice (t for Φx[t], T+t for Φu[t]); built once, several devices only
-  for (int i = 0; i < ndev; ++i) {
-    sls_plan* pl = plans[i];
-    const Symbolic& S = pl->sym;
-    if (ndev == 1) {
-      rc = sls_plan_download(pl, dvals[i], phix_vals, phiu_vals);
-      if (rc) { cleanup(); return rc; }
-    }
-    stage.resize((size_t)std::max<int64_t>(ndev == 1 ? 0 : S.n_packed, 1));
-    if (ndev > 1 && S.n_packed > 0) {
-      hipError_t e = hipSetDevice(pl->dev);
-      if (e == hipSuccess) e = hipMemcpy(stage.data(), dvals[i], (size_t)S.n_packed * sizeof(double), hipMemcpyDeviceToHost);
-      if (e != hipSuccess) { cleanup(); return hipfail(ctx, e, "hipMemcpy D2H"); }
-      // unpack: value index → slice as a flat table, one lookup per value (a binary search per value cost more than the solve)
-      if (slice_of.empty()) {
-        slice_of.resize((size_t)S.n_values);
-        for (int64_t t = 0; t < T; ++t) {
-          std::fill(slice_of.begin() + S.off_x[t], slice_of.begin() + S.off_x[t + 1], (int32_t)t);
-          std::fill(slice_of.begin() + S.off_u[t], slice_of.begin() + S.off_u[t + 1], (int32_t)(T + t));
-        }
-      }
-      for (int64_t k = 0; k < S.n_packed; ++k) {
-        const int64_t f = S.packed_to_final[k];
-        const int32_t sl = slice_of[f];
-        if (sl < T) phix_vals[sl][f - S.off_x[sl]] = stage[k];
-        else phiu_vals[sl - T][f - S.off_u[sl - T]] = stage[k];
-      }
-    }
-    // status
-    const int64_t ns = pl->info.n_subproblems;
-    std::vector<int32_t> stt(ns), its(ns);
-    std::vector<double> res(ns);
-    if (have_status0) { stt = stt_d[i]; its = its_d[i]; res = res_d[i]; }
-    else {
-      rc = sls_plan_fetch_status(pl, stt.data(), res.data(), its.data());
-      if (rc) { cleanup(); return rc; }
-    }
-    for (int64_t q = 0; q < ns; ++q) {
-      if (col_status) col_status[S.first_sub_index + q] = stt[q];
-      if (stt[q] != SLS_COL_OK && stt[q] != SLS_COL_TRIVIAL) st.n_not_ok++;
-      else st.max_residual = std::max(st.max_residual, res[q]);
-      st.max_iters = std::max(st.max_iters, its[q]);
-    }
-    st.n_subproblems += ns; st.n_free += S.n_packed;
-    st.max_nx = std::max(st.max_nx, S.max_n); st.max_nu = std::max(st.max_nu, S.max_m);
-    st.flops_alg += S.flops_alg; st.bytes_alg += S.bytes_alg;
-  }
-  st.t_download_s = now_s() - t1;
-  cleanup();
-  if (stats) *stats = st;
-  return (int)std::min<int64_t>(st.n_not_ok, 0x7fffffff);
-}
-
-int sls_h2_sf_solve_batch(sls_ctx* ctx, int nplants, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* const* Sx,
-                          const sls_csc_bool* const* Su, double* const* const* phix_vals, double* const* const* phiu_vals,
-                          int32_t* const* col_status, sls_stats* stats) {
-  if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
-  if (nplants <= 0 || !dims || !P || !Sx || !Su || !phix_vals || !phiu_vals) return fail(ctx, SLS_EINVAL, "null argument");
-  if (nplants == 1) return sls_h2_sf_solve(ctx, &dims[0], &P[0], Sx[0], Su[0], 0, nullptr, nullptr, phix_vals[0], phiu_vals[0],
-                                           col_status ? col_status[0] : nullptr, stats);
-  const int64_t T = dims[0].T;
-  const int base = dims[0].index_base;
-  std::vector<int64_t> xo(nplants + 1, 0), uo(nplants + 1, 0);
-  for (int i = 0; i < nplants; ++i) {
-    if (dims[i].T != T || dims[i].index_base != base || dims[i].flags != dims[0].flags)
-      return fail(ctx, SLS_EINVAL, "plants of one batch must share T, index_base and flags");
-    if (!Sx[i] || !Su[i] || !phix_vals[i] || !phiu_vals[i]) return fail(ctx, SLS_EINVAL, "null per-plant argument");
-    if (dims[i].Nz != dims[i].Nx + dims[i].Nu) return fail(ctx, SLS_ENOTSF, "Nz must equal Nx + Nu (state feedback with z = [x; u] rows)");
-    // each plant is validated as the single call would, so that an error names the plant and not a composite row
-    Inputs in{&dims[i], &P[i], Sx[i], Su[i], 0, nullptr, nullptr};
-    std::string msg;
-    if (int rc = validate_inputs(in, msg)) return fail(ctx, rc, "plant " + std::to_string(i) + ": " + msg);
-    xo[i + 1] = xo[i] + dims[i].Nx; uo[i + 1] = uo[i] + dims[i].Nu;
-  }
-  const int64_t NX = xo[nplants], NU = uo[nplants];
-  // block-diagonal composite in the caller's own index base.  Column blocks are laid side by side, rows shifted per plant;
-  // the z rows of C1 / D11 / D12 are [x of all plants; u of all plants] so that Nz = Nx + Nu keeps its meaning.
-  struct Csc { std::vector<int64_t> colptr, rowval; std::vector<double> val; std::vector<uint8_t> bval; };
-  auto cat_f64 = [&](auto pick, const std::vector<int64_t>& coff, int kind /*0: x rows, 1: z rows*/, Csc& out, sls_csc_f64& view,
-                     int64_t nrows) {
-    const int64_t ncols = coff[nplants];
-    out.colptr.assign(ncols + 1, base);
-    int64_t nnz = 0;
-    for (int i = 0; i < nplants; ++i) { const sls_csc_f64* M = pick(i); if (M) nnz += M->colptr[M->ncols] - base; }
-    out.rowval.resize(nnz); out.val.resize(nnz);
-    int64_t k = 0;
-    for (int i = 0; i < nplants; ++i) {
-      const sls_csc_f64* M = pick(i);
-      const int64_t nc = coff[i + 1] - coff[i];
-      for (int64_t c = 0; c < nc; ++c) {
-        if (M)
-          for (int64_t e = M->colptr[c] - base; e < M->colptr[c + 1] - base; ++e) {
-            const int64_t r = M->rowval[e] - base;
-            out.rowval[k] = base + (kind == 0 ? xo[i] + r : (r < dims[i].Nx ? xo[i] + r : NX + uo[i] + (r - dims[i].Nx)));
-            out.val[k] = M->nzval ? M->nzval[e] : 1.0;
-            ++k;
-          }
-        out.colptr[coff[i] + c + 1] = base + k;
-      }
-    }
-    view = sls_csc_f64{nrows, ncols, out.colptr.data(), out.rowval.data(), out.val.data()};
-  };
-  // NULL C1 / D12 = the default weights [C1 D12] = I (src/types/GeneralizedPlant.jl:105-110): all plants or none
-  int n_defw = 0;
-  for (int i = 0; i < nplants; ++i) {
-    if ((P[i].C1 == nullptr) != (P[i].D12 == nullptr)) return fail(ctx, SLS_EINVAL, "C1 and D12 must be given together");
-    if (!P[i].C1) ++n_defw;
-  }
-  if (n_defw != 0 && n_defw != nplants) return fail(ctx, SLS_EINVAL, "plants of one batch must all give C1, D12 or all leave them NULL");
-  Csc cA, cB1, cB2, cC1, cD11, cD12;
-  sls_csc_f64 vA, vB1, vB2, vC1, vD11, vD12;
-  cat_f64([&](int i) { return P[i].A; }, xo, 0, cA, vA, NX);
-  // B1 / D11: the path only ever reads column c of plant i for c < Nx_i (the default groups 1:Nx, src/synthesis.jl:15,42), and
-  // the symbolic pass addresses it as composite column xo[i] + c — so plant i's first Nx_i columns sit at xo[i]; surplus
-  // disturbance channels (Nw_i > Nx_i) belong to no subproblem and are left out
-  cat_f64([&](int i) { return P[i].B1; }, xo, 0, cB1, vB1, NX);
-  cat_f64([&](int i) { return P[i].B2; }, uo, 0, cB2, vB2, NX);
-  cat_f64([&](int i) { return P[i].C1; }, xo, 1, cC1, vC1, NX + NU);
-  cat_f64([&](int i) { return P[i].D11; }, xo, 1, cD11, vD11, NX + NU);
-  cat_f64([&](int i) { return P[i].D12; }, uo, 1, cD12, vD12, NX + NU);
-  sls_plant PP{&vA, &vB1, &vB2, n_defw ? nullptr : &vC1, &vD11, n_defw ? nullptr : &vD12};
-  std::vector<Csc> mx(T), mu(T);
-  std::vector<sls_csc_bool> vSx(T), vSu(T);
-  auto cat_bool = [&](const sls_csc_bool* const* Ms, int64_t t, const std::vector<int64_t>& roff, int64_t nrows, Csc& out, sls_csc_bool& view) {
-    out.colptr.assign(NX + 1, base);
-    int64_t nnz = 0;
-    for (int i = 0; i < nplants; ++i) nnz += Ms[i][t].colptr[dims[i].Nx] - base;
-    out.rowval.resize(nnz); out.bval.resize(nnz);
-    int64_t k = 0;
-    for (int i = 0; i < nplants; ++i) {
-      const sls_csc_bool& M = Ms[i][t];
-      for (int64_t c = 0; c < dims[i].Nx; ++c) {
-        for (int64_t e = M.colptr[c] - base; e < M.colptr[c + 1] - base; ++e) {
-          out.rowval[k] = base + roff[i] + (M.rowval[e] - base);
-          out.bval[k] = M.nzval ? M.nzval[e] : 1;
-          ++k;
-        }
-        out.colptr[xo[i] + c + 1] = base + k;
-      }
-    }
-    view = sls_csc_bool{nrows, NX, out.colptr.data(), out.rowval.data(), out.bval.data()};
-  };
-  for (int64_t t = 0; t < T; ++t) { cat_bool(Sx, t, xo, NX, mx[t], vSx[t]); cat_bool(Su, t, uo, NU, mu[t], vSu[t]); }
-  sls_dims D = dims[0];
-  D.Nx = NX; D.Nu = NU; D.Nw = NX; D.Nz = NX + NU;
-  // composite value arrays: plant i's values of slice t are one contiguous run (its columns are adjacent)
-  std::vector<std::vector<double>> bx(T), bu(T);
-  std::vector<double*> px(T), pu(T);
-  for (int64_t t = 0; t < T; ++t) {
-    bx[t].resize((size_t)std::max<int64_t>(1, (int64_t)mx[t].rowval.size())); bu[t].resize((size_t)std::max<int64_t>(1, (int64_t)mu[t].rowval.size()));
-    px[t] = bx[t].data(); pu[t] = bu[t].data();
-  }
-  std::vector<int32_t> st_all((size_t)NX, 0);
-  // the ridge term of sls_set_ridge has per-plant length: every plant of the batch gets it (concatenated for the composite)
-  struct RidgeGuard {
-    sls_ctx* c; std::vector<double> rx, ru; bool on = false;
-    ~RidgeGuard() { if (on) { c->ridge_x.swap(rx); c->ridge_u.swap(ru); } }
-  } rg{ctx, {}, {}, false};
-  if (!ctx->ridge_x.empty() || !ctx->ridge_u.empty()) {
-    for (int i = 0; i < nplants; ++i)
-      if ((!ctx->ridge_x.empty() && (int64_t)ctx->ridge_x.size() != dims[i].Nx) || (!ctx->ridge_u.empty() && (int64_t)ctx->ridge_u.size() != dims[i].Nu))
-        return fail(ctx, SLS_EINVAL, "sls_set_ridge: the weights' lengths do not match Nx / Nu of plant " + std::to_string(i) + " of the batch");
-    rg.rx = ctx->ridge_x; rg.ru = ctx->ridge_u; rg.on = true;
-    std::vector<double> cx, cu;
-    for (int i = 0; i < nplants; ++i) { cx.insert(cx.end(), rg.rx.begin(), rg.rx.end()); cu.insert(cu.end(), rg.ru.begin(), rg.ru.end()); }
-    ctx->ridge_x.swap(cx); ctx->ridge_u.swap(cu);
-  }
-  const int rc = sls_h2_sf_solve(ctx, &D, &PP, vSx.data(), vSu.data(), 0, nullptr, nullptr, px.data(), pu.data(), st_all.data(), stats);
-  if (rc < 0) return rc;
-  for (int64_t t = 0; t < T; ++t) {
-    for (int i = 0; i < nplants; ++i) {
-      const int64_t x0 = mx[t].colptr[xo[i]] - base, x1 = mx[t].colptr[xo[i + 1]] - base;
-      const int64_t u0 = mu[t].colptr[xo[i]] - base, u1 = mu[t].colptr[xo[i + 1]] - base;
-      if (x1 > x0) { if (!phix_vals[i][t]) return fail(ctx, SLS_EINVAL, "null phix_vals[i][t]"); std::memcpy(phix_vals[i][t], bx[t].data() + x0, (size_t)(x1 - x0) * sizeof(double)); }
-      if (u1 > u0) { if (!phiu_vals[i][t]) return fail(ctx, SLS_EINVAL, "null phiu_vals[i][t]"); std::memcpy(phiu_vals[i][t], bu[t].data() + u0, (size_t)(u1 - u0) * sizeof(double)); }
-    }
-  }
-  if (col_status)
-    for (int i = 0; i < nplants; ++i)
-      if (col_status[i]) std::copy(st_all.begin() + xo[i], st_all.begin() + xo[i + 1], col_status[i]);
   return rc;
 }
 

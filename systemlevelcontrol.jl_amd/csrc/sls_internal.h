@@ -7,6 +7,8 @@
 
 #include "../../include/sls_mi355x.h"
 #include "sls_device.h"
+#include "sls_objective.h"
+#include "sls_residual.h"
 
 struct sls_ctx {
   std::vector<int> devs;
@@ -46,6 +48,26 @@ int fail(sls_ctx* ctx, int code, const std::string& msg);
 int hipfail(sls_ctx* ctx, hipError_t e, const char* what);
 // a plan / loop object may outlive its context (host-language GC order): checked before touching it
 bool ctx_is_live(const sls_ctx* ctx);
+// the launchers of the .hip units
+hipError_t launch_general(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool wide);
+hipError_t launch_scatter(const double* src, const int64_t* idx, int64_t n, double* dst, hipStream_t stream);
+hipError_t launch_wave(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_twisted(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_twisted4(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_twisted4_prepare(int cls, const KernelParams& p, unsigned char* pool, hipStream_t stream);
+hipError_t launch_tile(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool mlds, bool two_per_cu,
+                       bool general_weights, bool big);
+hipError_t launch_expand_tables(const SubDesc* subs, int nsub, int T, const uint64_t* cmask, const int32_t* cbase, const int64_t* coff,
+                                uint8_t* mask_pool, int32_t* dest_pool, hipStream_t stream);
+hipError_t launch_mask_levels(const MaskParams& p, bool fill, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_index_sets(const IndexSetParams& p, bool fill, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_column_tables(const ColumnTableParams& p, bool fill, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_level_prefix(const int32_t* cntx, const int32_t* cntu, int Nx, int K1, int64_t* prex, int64_t* preu, int64_t* totx,
+                               int64_t* totu, hipStream_t stream);
+hipError_t launch_objective(const ObjectiveParams& p, int lds_doubles, double* d_total, hipStream_t stream);
+hipError_t launch_residual(const ResidualParams& p, double* d_totals, hipStream_t stream);
+hipError_t launch_tile_invert(const double* d_A, int n, double* d_ws, double* d_out, bool mlds, hipStream_t stream);
+hipError_t launch_operator_update(const OperatorUpdateParams& p, hipStream_t stream);
 // sls_partial.hip: the entries an update changes, the subproblems they touch, the compacted launch lists of a selected run
 hipError_t launch_changed_entries(const ChangedEntriesParams& p, hipStream_t stream);
 hipError_t launch_mark_affected(const MarkAffectedParams& p, hipStream_t stream);

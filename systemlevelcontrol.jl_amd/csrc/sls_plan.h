@@ -1,0 +1,146 @@
+// sls_plan.h — the resident plan as the units behind the C ABI see it: sls_api.cpp builds, runs and destroys it, sls_dropin.cpp
+// (the one-shot calls) and sls_debug.cpp (include/sls_mi355x_debug.h) are its clients.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "sls_internal.h"
+#include "sls_routing.h"
+#include "sls_symbolic.h"
+
+namespace sls {
+constexpr int kEventPool = 64;
+}  // namespace sls
+
+struct sls_plan {
+  sls_ctx* ctx = nullptr;
+  int dev = 0;
+  int slot = 0;
+  bool streams_borrowed = false, scratch_borrowed = false, arena_borrowed = false, stream_external = false, ltab_borrowed = false;
+  hipEvent_t ev_batch = nullptr, ev_batch_done = nullptr;     // sls_plan_execute_batch fork / join edges
+  void* own_scratch = nullptr;
+  sls::Symbolic sym;       // host copy (pools are cleared after upload except what download needs; its operator values are the plan-time ones)
+  sls_plan_info info{};
+  hipStream_t stream = nullptr;
+  // device buffers
+  std::vector<void*> dev_allocs;
+  struct ArenaReq { const void* src; size_t bytes; void** out; size_t off; bool zero; };
+  std::vector<ArenaReq> arena_reqs;
+  sls::KernelParams kp{};  // dest_pool / out are patched per execute
+  const int32_t* d_dest = nullptr;
+  const int32_t* d_pdest = nullptr;
+  int32_t* d_counters = nullptr;      // one work-queue counter per launch (tile kernel)
+  unsigned char* d_big = nullptr;     // big tile launches: their carve buffers (inside the scratch workspace)
+  bool has_tile = false;
+  // Prepared records of the four-wave columns (twisted4_prepare_kernel, layout: sls_device.h), written in plan_finish.
+  // They hold index lists AND the gathered values of A / B2, taken from the plan's own copy of the operator:
+  // sls_plan_update_plant reruns the kernel behind every change of that copy.
+  unsigned char* d_t4 = nullptr;
+  int64_t t4_stride = 0, t4_records = 0;
+  // The static blocks S_k of the same columns (layout: sls_device.h, twisted4_static_doubles), written by the same kernel from
+  // the same copy.  NULL — the launches rebuild the blocks themselves — when the pool would exceed kT4StaticBudget or with
+  // SLS_T4_PRESTATIC=0 (lab mode).
+  double* d_t4s = nullptr;
+  int64_t t4s_doubles = 0;
+  struct Launch : sls::LaunchSpec {    // what kernel selection decided + what the launch runs on
+    explicit Launch(const sls::LaunchSpec& spec) : sls::LaunchSpec(spec) {}
+    hipStream_t stream = nullptr;      // aux stream (launch 0 runs on the caller's stream)
+    hipEvent_t done = nullptr;
+    int64_t t4_off = 0;                // four-wave launch: its first record in d_t4
+    int64_t t4s_off = 0, t4s_stride = 0;   // … its first double in d_t4s, doubles per column
+  };
+  std::vector<Launch> launches;
+  hipEvent_t ev_fork = nullptr;
+  hipEvent_t ev_done = nullptr;         // recorded on the caller's stream at the end of an execute that the event pool could not time
+  hipEvent_t last_done = nullptr;       // the end of the last execute: its ev_stop (timed) or ev_done (untimed); what status reads and downloads wait for
+  // event timing
+  hipEvent_t ev_start[sls::kEventPool], ev_stop[sls::kEventPool];
+  int ev_used = 0;
+  double ev_acc_ms = 0.0;
+  int64_t ev_acc_n = 0;
+  bool events_ok = false;
+  sls::pool_vec<double> host_stage; // D2H staging (small Φ only)
+  std::vector<int32_t> too_large_subs;  // subproblems beyond every kernel's LDS budget: never launched, status SLS_COL_UNSUPPORTED
+  std::vector<int32_t> status_init;     // initial content of the device status words
+  int64_t gbeg = 0, gend = 0, ngroups_in = 0;   // the shard of the caller's group list this plan covers
+  sls_plan* refine = nullptr;           // sls_plan_refine: the near-singular groups once more on the tile kernel, run after every execute
+  std::vector<int64_t> refine_dst;      // subproblem of this plan each subproblem of `refine` replaces
+  int64_t info_unsupported = 0;
+  // objective evaluation (sls_plan_objective): the records of Symbolic::obj_pool, the work list of the general build and the
+  // plan-owned result buffer of sls_plan_fetch_objective (n_subproblems values, then the total)
+  const double* d_obj = nullptr;
+  const int32_t* d_gen = nullptr;
+  double* d_colobj = nullptr;
+  std::vector<int32_t> obj_gen;
+  int obj_lds_doubles = 0;
+  // operator update (sls_plan_update_plant): the value map and plan-time-zero marks (host copy: the host path's check), their
+  // device copies, a staging array for host values (nnzA + nnzB doubles), the refusal counter of the device path and the end
+  // of the last update on the stream it was enqueued on
+  sls::OperatorValueMap opmap;
+  const int32_t* d_upd_pos = nullptr;
+  const uint8_t* d_upd_zero = nullptr;
+  double* d_upd_stage = nullptr;
+  unsigned long long* d_upd_rejected = nullptr;
+  hipEvent_t ev_upd = nullptr;
+  bool upd_recorded = false;
+  // partial re-solve (sls_plan_execute_columns / _dirty, sls_plan_track_changes): one device allocation made by
+  // the first of those calls (partial_ensure) — a plan that never uses them holds none of it and reports the same
+  // workspace_bytes.  Layouts: sls_device.h (ChangedEntriesParams, MarkAffectedParams, CompactOrderParams).
+  struct Partial {
+    bool ready = false, track = false;
+    uint8_t* dirty = nullptr;         // [nsub] marks of the tracked updates
+    uint8_t* marks = nullptr;         // [nsub] the list of an sls_plan_execute_columns call
+    uint8_t* chg = nullptr;           // [nnzA + nnzB]
+    uint8_t* row_chg = nullptr;       // [Nx]
+    int32_t* sel_order = nullptr;     // [order entries]
+    int32_t* sel_pos = nullptr;
+    int32_t* count = nullptr;         // [2 · launches]
+    const int32_t* launch_tab = nullptr;   // [launches][3]
+    std::vector<int32_t> h_count;
+    std::vector<uint8_t> h_marks;
+  } part;
+  // achievability residual (sls_plan_residual): the halo lists, the subproblems' global columns and the plan-owned
+  // result buffer of sls_plan_fetch_residual (three arrays of n_subproblems values, then the two totals) — one device allocation
+  // made by the first call (residual_ensure), not counted in workspace_bytes
+  struct Residual {
+    bool ready = false;
+    const int32_t* sub_col = nullptr;
+    const int64_t* halo_ptr = nullptr;
+    const int32_t* halo_rows = nullptr;
+    double* out = nullptr;            // [3 · nsub + 2]
+  } resid;
+};
+
+namespace sls {
+
+// want_packed = false (the one-device drop-in call, which only ever runs packed = 0) skips the packed numbering on the host
+// and its 4 B/variable table on the device.  Everything that steers a plan's construction is an explicit argument (no
+// mutable context state, no environment writes): a flag left on by an early return would silently re-route later plans.
+struct PlanOpts {
+  bool force_tile = false;                          // every column on the tile kernel (the refinement pass)
+  const std::vector<int64_t>* pk_override = nullptr; // with force_tile: packed bases of the subproblems inside the refined plan's packed array
+  int host_tables = -1;                             // mask / destination tables: 1 built on the host, 0 expanded on the device, -1 = SLS_HOST_TABLES decides
+};
+
+// sls_api.cpp
+double now_s();
+int plan_create(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, int64_t group_begin, int64_t group_end,
+                bool want_packed, const PlanOpts& opt, sls_plan** plan_out);
+int plan_create_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, int64_t d, double alpha,
+                          sls_plan** plan_out);
+// Host waits for the plan's last execute (and for nothing else on the device: a status read or a download must not stall on
+// a collective or on another plan running on some other stream).
+int wait_plan_done(sls_plan* pl);
+// the plan's own status words, without those of an attached refinement (sls_plan_fetch_status merges the two)
+int fetch_status_raw(sls_plan* plan, int32_t* col_status, double* residual, int32_t* iters);
+// the groups select_refinement_groups (sls_dropin_host.h) names get a second plan on the tile kernel (PlanOpts::force_tile), run
+// into the same device array after the first and attached to `pl`, so that later executes and status reads include it; stt /
+// res / its come back merged.  Waits for `stream`; costs one status read when nothing qualifies.
+int attach_refinement(sls_plan* pl, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                      int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, hipStream_t stream, double* d_values,
+                      int64_t* n_refined, std::vector<int32_t>& stt, std::vector<double>& res, std::vector<int32_t>& its, int packed);
+
+}  // namespace sls

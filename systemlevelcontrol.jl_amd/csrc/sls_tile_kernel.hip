@@ -1439,7 +1439,7 @@ __global__ __launch_bounds__(TB) void tile_invert_kernel(const double* __restric
 
 }  // namespace sls
 
-// ---- launchers (called from sls_api.cpp through plain C++ declarations) ----
+// ---- launchers (declared in sls_internal.h; called from sls_api.cpp and, launch_tile_invert, from sls_debug.cpp) ----
 namespace sls {
 
 template <bool MLDS, int WPE, bool GW, bool BIG = false>
