@@ -532,6 +532,53 @@ int  sls_controller_step(sls_controller* ctl, void* hip_stream, const double* d_
 int  sls_controller_info(const sls_controller* ctl, int64_t* n_entries, int64_t* steps_done, int64_t* state_bytes);
 void sls_controller_destroy(sls_controller* ctl);
 
+/* ---- closed-loop 𝓛₁ and 𝓗∞ norms of a resident Φ (csrc/sls_norms.hip) ----
+ * The two norms SLS designs are judged by beside the 𝓗₂ cost.  Built from the masks alone, like the controller.  Rows are the Nx
+ * state rows followed by the Nu input rows, N = Nx + Nu; for t = 0 … T−1 (0-based)
+ *     G[t] = diag(cz) · [Φx[t]; Φu[t]] · diag(b)        N × Nx, real          G(ω) = Σ_t G[t] · e^{−iωt}
+ * cz [N] and b [Nx] are HOST vectors, NULL = all ones.  Unlike the controller, Φx[0] IS part of the operator (the identity block
+ * of the closed-loop response); a stored-false mask entry is not, and is never read.  With cz the diagonal of [C1 D12], b the
+ * diagonal of B1 and D11 = 0, G is the closed-loop map w → z; with both NULL it is Φ itself (the norms of the robust-SLS bounds).
+ * Non-diagonal weights are not supported.
+ * sls_norms_plan: Nx, Nu, T, index_base of dims are read.  Builds the entries twice — by rows (key t·Nx + col) and by columns
+ *   (key t·N + row), each with a permutation into the mask-order value array — and allocates every buffer: both value orders,
+ *   the work vectors of max_freq frequencies and the result buffer of the fetch calls.  SLS_EUNSUPPORTED when T·N exceeds int32
+ *   (the keys are int32) or max_freq exceeds 65535·64; SLS_EINVAL for max_freq < 1, a non-finite weight, a dev_slot out of range.
+ * sls_norms_load: d_values = Φ in the mask-order value array sls_plan_execute(packed = 0) fills (DEVICE); one gather launch
+ *   fills both value orders, the weights folded in: the stored entry is Φ·(cz[row]·b[col]).
+ * sls_norms_l1: outputs on the DEVICE, each may be NULL.  row_l1[i] = Σ_t Σ_j |G[t][i,j]| (N), col_l1[j] = Σ_t Σ_i |G[t][i,j]|
+ *   (Nx), totals[0] = max_i row_l1 — the 𝓛₁ norm, the induced ℓ∞ → ℓ∞ gain — and totals[1] = max_j col_l1, the 𝓔₁ norm (the
+ *   norm sls_plan_residual reports of Δ).  One wave per row or column, a fixed summation order, no floating-point atomics:
+ *   bit-identical from call to call.  A NaN in Φ gives +inf in its row and its column.
+ * sls_norms_hinf: omega = HOST array of nfreq ≤ max_freq angles in radians per sample.  cos(ω·t), sin(ω·t) are computed on the
+ *   host and copied up through the context's pinned buffer, ordered on the stream.  For every frequency f, independently,
+ *       v₀[j] = 1 + (uint32)(j·2654435761u)·2⁻³²            (then normalised)
+ *       repeat iters times:   y = G(ω_f)·v ;   v ← G(ω_f)ᴴ·y ;   v ← v/‖v‖₂
+ *       sigma[f] = ‖G(ω_f)·v‖₂
+ *   d_sigma [nfreq] and d_peak [2] on the DEVICE, each may be NULL.  sigma[f] is a LOWER bound of σ_max(G(ω_f)) that does not
+ *   decrease as iters grows (how fast it closes depends on the gap between the two largest singular values); the sigma of a
+ *   frequency does not depend on the other frequencies of the call.  peak[0] = max_f sigma[f], peak[1] = the index of the first
+ *   frequency that attains it, as a double.  THE PEAK IS A LOWER BOUND OF THE 𝓗∞ NORM ON THE CALLER'S GRID ONLY: a resonance
+ *   between two grid points is not seen, and refining the grid is the caller's business.  SLS_EINVAL: nfreq < 1 or > max_freq,
+ *   iters < 1, a non-finite ω, a call before the first load; the object stays usable.
+ * load, l1 and hinf allocate nothing and enqueue on `hip_stream` (NULL = null stream); hinf waits only for an earlier twiddle
+ * upload that still reads the pinned buffer.  The caller issues the calls of one object on one stream or orders them with events.
+ * sls_norms_fetch_l1 / sls_norms_fetch_hinf: the same passes into the plan-owned buffer on `hip_stream`, waited for and copied
+ *   to HOST arrays (each nullable), like sls_plan_fetch_objective.
+ * sls_norms_info (each output nullable): stored-true entries (a pass reads 12 B each), device bytes held, max_freq. */
+typedef struct sls_norms sls_norms;
+int  sls_norms_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                    const double* cz, const double* b, int64_t max_freq, sls_norms** out);
+int  sls_norms_load(sls_norms* norms, void* hip_stream, const double* d_values);
+int  sls_norms_l1(sls_norms* norms, void* hip_stream, double* d_row_l1, double* d_col_l1, double* d_totals);
+int  sls_norms_hinf(sls_norms* norms, void* hip_stream, const double* omega, int64_t nfreq, int64_t iters, double* d_sigma,
+                    double* d_peak);
+int  sls_norms_fetch_l1(sls_norms* norms, void* hip_stream, double* row_l1, double* col_l1, double* totals);
+int  sls_norms_fetch_hinf(sls_norms* norms, void* hip_stream, const double* omega, int64_t nfreq, int64_t iters, double* sigma,
+                          double* peak);
+int  sls_norms_info(const sls_norms* norms, int64_t* n_entries, int64_t* device_bytes, int64_t* max_freq);
+void sls_norms_destroy(sls_norms* norms);
+
 /* Symbolic pass only (replaces reference src/reduction.jl:11-27 for one group):
  * fills s_x / s_u (index_base of dims), returns their lengths.  Pure host.           */
 int  sls_sparsity_dim_reduction(const sls_dims* dims, const sls_csc_f64* A,

@@ -127,6 +127,22 @@ int sls_debug_controller_tables(const sls_dims* dims, const sls_csc_bool* Sx, co
 int sls_debug_controller_host(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, const double* values,
                               int64_t nscen, int64_t steps, const double* x, double* u, double* what);
 
+/* Both tables of the closed-loop norm passes (sls_norms_plan) from the masks (dims: Nx, Nu, T, index_base are read), built on the
+ * host by the routine the plan uses (csrc/sls_symbolic.cpp: build_norms_operator).  *n_entries: stored-true entries of Sx[0..T−1]
+ * and Su[0..T−1].  Rows (N = Nx + Nu: state rows, then input rows): row_ptr[N + 1], row_key[e] = t·Nx + col ascending inside a
+ * row; columns: col_ptr[Nx + 1], col_key[e] = t·N + row ascending inside a column; row_perm / col_perm: the entry's index in the
+ * mask-order value array.  Every output is nullable: call with only n_entries first for the length.  Needs no device. */
+int sls_debug_norms_tables(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, int64_t* n_entries, int32_t* row_ptr,
+                           int32_t* row_key, int32_t* row_perm, int32_t* col_ptr, int32_t* col_key, int32_t* col_perm);
+
+/* Host twin of sls_norms_load + sls_norms_l1 + sls_norms_hinf (csrc/sls_norms.cpp): the same tables, twiddles and per-entry
+ * operations in a plain loop order, in double.  values: Φ in mask order (HOST); cz [N], b [Nx]: NULL = ones.  Outputs, each
+ * nullable: row_l1 [N], col_l1 [Nx], totals [2], sigma [nfreq], peak [2]; omega, nfreq and iters are read only when sigma or peak
+ * is asked for.  Needs no device. */
+int sls_debug_norms_host(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, const double* values, const double* cz,
+                         const double* b, const double* omega, int64_t nfreq, int64_t iters, double* row_l1, double* col_l1,
+                         double* totals, double* sigma, double* peak);
+
 #ifdef __cplusplus
 }
 #endif

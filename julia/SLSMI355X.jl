@@ -11,7 +11,7 @@
 module SLSMI355X
 
 using SparseArrays
-export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!
+export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!, Norms, l1, hinf
 
 const LIB = get(ENV, "SLS_MI355X_LIB", "libsls_mi355x.so")
 
@@ -198,6 +198,58 @@ step!(c::Controller, d_x::Ptr{Cvoid}, d_u::Ptr{Cvoid}; d_what::Ptr{Cvoid}=C_NULL
                      c.handle, stream, d_x, d_u, d_what))
 function Base.close(c::Controller)
     c.handle != C_NULL && (ccall((:sls_controller_destroy, LIB), Cvoid, (Ptr{Cvoid},), c.handle); c.handle = C_NULL)
+    return nothing
+end
+
+"""
+    n = Norms(ctx, Nx, Nu, [𝓢ₓ,𝓢ᵤ]; cz=nothing, b=nothing, max_freq=64, dev_slot=0)
+    load!(n, d_values; stream=C_NULL);  row_l1, col_l1, totals = l1(n);  sigma, peak, argpeak = hinf(n, ω; iters=32)
+
+`sls_norms_*`: closed-loop 𝓛₁ and 𝓗∞ norms of the Φ on the device, built from the masks alone.  Rows are the `Nx` state rows
+followed by the `Nu` input rows; `G[t] = diag(cz)·[Φₓ[t]; Φᵤ[t]]·diag(b)` for every `t` (Φₓ[1] = I included), `cz` of length `Nx+Nu`
+and `b` of length `Nx`, `nothing` = ones (diagonal weights only).  `l1` returns the absolute row and column sums of `G` and
+`totals = (𝓛₁ norm, 𝓔₁ norm)`; `hinf` returns, per angle of `ω` (radians per sample, at most `max_freq` of them), a power-iteration
+lower bound of `σ_max(G(ω))`, their maximum and the 1-based index of the first angle that attains it.  The peak bounds the 𝓗∞ norm
+from below on the grid `ω` only: refining the grid is the caller's business.  Both wait for `stream`.  `close(n)` frees it.  NOT
+EXECUTED in the build container, like the rest of this file.
+"""
+mutable struct Norms
+    handle::Ptr{Cvoid}
+    Nx::Int; Nu::Int; max_freq::Int
+end
+function Norms(ctx::Ptr{Cvoid}, Nx::Integer, Nu::Integer, 𝓢::AbstractVector; cz::Union{Nothing,Vector{Float64}}=nothing,
+               b::Union{Nothing,Vector{Float64}}=nothing, max_freq::Integer=64, dev_slot::Integer=0)
+    𝓢ₓ, 𝓢ᵤ = 𝓢
+    Sx = [SparseMatrixCSC{Bool,Int}(S) for S in 𝓢ₓ];  Su = [SparseMatrixCSC{Bool,Int}(S) for S in 𝓢ᵤ]
+    sx = [csc(S) for S in Sx];  su = [csc(S) for S in Su]
+    cz === nothing || length(cz) == Nx + Nu || error("cz must have Nx + Nu entries")
+    b === nothing || length(b) == Nx || error("b must have Nx entries")
+    dims = Ref(Dims(Nx, Nu, Nx + Nu, Nx, length(Sx), 1, UInt32(0)))       # only Nx, Nu, T, index_base are read
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve Sx Su sx su cz b begin
+        rc = ccall((:sls_norms_plan, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Ref{Dims}, Ptr{CscBool}, Ptr{CscBool}, Ptr{Float64}, Ptr{Float64}, Int64, Ref{Ptr{Cvoid}}),
+                   ctx, dev_slot, dims, sx, su, cz === nothing ? C_NULL : pointer(cz), b === nothing ? C_NULL : pointer(b), max_freq, h)
+    end
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx)))
+    return Norms(h[], Nx, Nu, max_freq)
+end
+load!(n::Norms, d_values::Ptr{Cvoid}; stream::Ptr{Cvoid}=C_NULL) =
+    _ctl_check(ccall((:sls_norms_load, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), n.handle, stream, d_values))
+function l1(n::Norms; stream::Ptr{Cvoid}=C_NULL)
+    row = zeros(Float64, n.Nx + n.Nu);  col = zeros(Float64, n.Nx);  totals = zeros(Float64, 2)
+    _ctl_check(ccall((:sls_norms_fetch_l1, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                     n.handle, stream, row, col, totals))
+    return row, col, totals
+end
+function hinf(n::Norms, ω::AbstractVector{<:Real}; iters::Integer=32, stream::Ptr{Cvoid}=C_NULL)
+    om = Vector{Float64}(ω);  sigma = zeros(Float64, length(om));  peak = zeros(Float64, 2)
+    _ctl_check(ccall((:sls_norms_fetch_hinf, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
+                     n.handle, stream, om, length(om), iters, sigma, peak))
+    return sigma, peak[1], Int(peak[2]) + 1
+end
+function Base.close(n::Norms)
+    n.handle != C_NULL && (ccall((:sls_norms_destroy, LIB), Cvoid, (Ptr{Cvoid},), n.handle); n.handle = C_NULL)
     return nothing
 end
 

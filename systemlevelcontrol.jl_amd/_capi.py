@@ -92,6 +92,8 @@ EXPORTS = [
     "sls_plan_residual", "sls_plan_fetch_residual",
     "sls_controller_plan", "sls_controller_load", "sls_controller_reset", "sls_controller_step", "sls_controller_info",
     "sls_controller_destroy",
+    "sls_norms_plan", "sls_norms_load", "sls_norms_l1", "sls_norms_hinf", "sls_norms_fetch_l1", "sls_norms_fetch_hinf", "sls_norms_info",
+    "sls_norms_destroy",
 ]
 
 _lib = None
@@ -202,7 +204,19 @@ def load_library(path: str | None = None):
     lib.sls_controller_step.restype = C.c_int; lib.sls_controller_step.argtypes = [vp, vp, vp, vp, vp]
     lib.sls_controller_info.restype = C.c_int; lib.sls_controller_info.argtypes = [vp, i64p, i64p, i64p]
     lib.sls_controller_destroy.restype = None; lib.sls_controller_destroy.argtypes = [vp]
+    lib.sls_norms_plan.restype = C.c_int; lib.sls_norms_plan.argtypes = [vp, C.c_int] + masks + [dp, dp, C.c_int64, C.POINTER(vp)]
+    lib.sls_norms_load.restype = C.c_int; lib.sls_norms_load.argtypes = [vp, vp, vp]
+    lib.sls_norms_l1.restype = C.c_int; lib.sls_norms_l1.argtypes = [vp, vp, vp, vp, vp]
+    lib.sls_norms_hinf.restype = C.c_int; lib.sls_norms_hinf.argtypes = [vp, vp, dp, C.c_int64, C.c_int64, vp, vp]
+    lib.sls_norms_fetch_l1.restype = C.c_int; lib.sls_norms_fetch_l1.argtypes = [vp, vp, dp, dp, dp]
+    lib.sls_norms_fetch_hinf.restype = C.c_int; lib.sls_norms_fetch_hinf.argtypes = [vp, vp, dp, C.c_int64, C.c_int64, dp, dp]
+    lib.sls_norms_info.restype = C.c_int; lib.sls_norms_info.argtypes = [vp, i64p, i64p, i64p]
+    lib.sls_norms_destroy.restype = None; lib.sls_norms_destroy.argtypes = [vp]
     # diagnostics outside the public header
+    lib.sls_debug_norms_tables.restype = C.c_int
+    lib.sls_debug_norms_tables.argtypes = masks + [i64p, i32p, i32p, i32p, i32p, i32p, i32p]
+    lib.sls_debug_norms_host.restype = C.c_int
+    lib.sls_debug_norms_host.argtypes = masks + [dp, dp, dp, dp, C.c_int64, C.c_int64, dp, dp, dp, dp, dp]
     lib.sls_debug_controller_tables.restype = C.c_int
     lib.sls_debug_controller_tables.argtypes = masks + [i64p, i32p, i32p, i32p, i32p]
     lib.sls_debug_controller_host.restype = C.c_int

@@ -101,8 +101,10 @@ hipError_t create_aux_stream(hipStream_t* st, bool low) {
   return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
 }
 
+}  // namespace
+
 // The context slot's pinned staging memory (created on first use, 8 MiB): nullptr when unavailable or too small.
-unsigned char* slot_pinned(sls_ctx* ctx, int slot, size_t bytes) {
+unsigned char* sls::slot_pinned(sls_ctx* ctx, int slot, size_t bytes) {
   if (!ctx_is_live(ctx) || slot < 0 || slot >= (int)ctx->slots.size() || sls_knob("SLS_PAGEABLE_D2H")) return nullptr;
   sls_ctx::Slot& sl = ctx->slots[slot];
   if (sl.pinned_pending) { (void)hipEventSynchronize(sl.pinned_busy); sl.pinned_pending = false; }   // an update's H2D copy still reads it
@@ -113,6 +115,8 @@ unsigned char* slot_pinned(sls_ctx* ctx, int slot, size_t bytes) {
   }
   return bytes <= sl.pinned_bytes ? static_cast<unsigned char*>(sl.pinned) : nullptr;
 }
+
+namespace {
 
 // Device → host copy of a flat array of 8-byte elements into the caller's pageable slices (slice i = elements
 // [beg[i], beg[i+1]) → ptrs[i]): 1 MiB chunks through kDlLanes lanes, each a host thread with its own stream and pinned chunk —

@@ -48,6 +48,10 @@ int fail(sls_ctx* ctx, int code, const std::string& msg);
 int hipfail(sls_ctx* ctx, hipError_t e, const char* what);
 // a plan / loop object may outlive its context (host-language GC order): checked before touching it
 bool ctx_is_live(const sls_ctx* ctx);
+// The context slot's pinned staging memory (created on first use, 8 MiB): nullptr when unavailable or too small.  Waits first
+// for an asynchronous H2D copy that still reads it (Slot::pinned_pending); whoever leaves such a copy behind records
+// Slot::pinned_busy after it and sets pinned_pending.
+unsigned char* slot_pinned(sls_ctx* ctx, int slot, size_t bytes);
 // the launchers of the .hip units
 hipError_t launch_general(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool wide);
 hipError_t launch_scatter(const double* src, const int64_t* idx, int64_t n, double* dst, hipStream_t stream);

@@ -1194,4 +1194,53 @@ int build_controller_operator(const sls_dims* dims, const sls_csc_bool* Sx, cons
   return fir_row_lists(d, Sx, Su, F, msg);
 }
 
+// the row and the column lists of G[t] = [Φx[t]; Φu[t]], t = 0 … T−1 (closed-loop norms, sls_norms.h)
+int build_norms_operator(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, NormsOperator& Op, std::string& msg) {
+  if (!dims || !Sx || !Su) { msg = "null argument"; return SLS_EINVAL; }
+  const sls_dims& d = *dims;
+  const int base = d.index_base;
+  if (base != 0 && base != 1) { msg = "index_base must be 0 or 1"; return SLS_EINVAL; }
+  if (d.Nx <= 0 || d.Nu < 0 || d.T <= 0) { msg = "Nx, T must be positive"; return SLS_EINVAL; }
+  const int64_t N = d.Nx + d.Nu;
+  if (d.Nx > 0x7fffffffLL || N > 0x7fffffffLL || d.T > 0x7fffffffLL / N) { msg = "T·(Nx+Nu) exceeds int32 (the entries' keys are int32)"; return SLS_EUNSUPPORTED; }
+  Op = NormsOperator();
+  int rc;
+  int64_t nval = 0;
+  std::vector<int64_t> off_x(d.T), off_u(d.T);
+  for (int64_t t = 0; t < d.T; ++t) {
+    if ((rc = check_csc(&Sx[t], d.Nx, d.Nx, base, "Sx[t]", msg))) return rc;
+    off_x[t] = nval; nval += Sx[t].colptr[d.Nx] - base;
+  }
+  for (int64_t t = 0; t < d.T; ++t) {
+    if ((rc = check_csc(&Su[t], d.Nu, d.Nx, base, "Su[t]", msg))) return rc;
+    off_u[t] = nval; nval += Su[t].colptr[d.Nx] - base;
+  }
+  if (nval > 0x7fffffffLL) { msg = "value array exceeds int32 indexing"; return SLS_EUNSUPPORTED; }
+  Op.Nx = d.Nx; Op.Nu = d.Nu; Op.T = d.T; Op.n_values = nval;
+  // every stored-true entry once, in the order (t, column, x rows then u rows): a counting sort by row leaves rows ascending in
+  // (t, col), one by column leaves columns ascending in (t, row)
+  auto each = [&](auto&& f) {
+    for (int64_t t = 0; t < d.T; ++t)
+      for (int64_t c = 0; c < d.Nx; ++c) {
+        for (int64_t k = Sx[t].colptr[c] - base; k < Sx[t].colptr[c + 1] - base; ++k)
+          if (!Sx[t].nzval || Sx[t].nzval[k]) f(t, c, Sx[t].rowval[k] - base, off_x[t] + k);
+        for (int64_t k = Su[t].colptr[c] - base; k < Su[t].colptr[c + 1] - base; ++k)
+          if (!Su[t].nzval || Su[t].nzval[k]) f(t, c, d.Nx + Su[t].rowval[k] - base, off_u[t] + k);
+      }
+  };
+  Op.row_ptr.assign(N + 1, 0); Op.col_ptr.assign(d.Nx + 1, 0);
+  each([&](int64_t, int64_t c, int64_t r, int64_t) { Op.row_ptr[r + 1]++; Op.col_ptr[c + 1]++; });
+  for (int64_t r = 0; r < N; ++r) Op.row_ptr[r + 1] += Op.row_ptr[r];
+  for (int64_t c = 0; c < d.Nx; ++c) Op.col_ptr[c + 1] += Op.col_ptr[c];
+  const int64_t nent = Op.row_ptr[N];
+  Op.row_key.resize(nent); Op.row_perm.resize(nent); Op.col_key.resize(nent); Op.col_perm.resize(nent);
+  std::vector<int32_t> wr(Op.row_ptr.begin(), Op.row_ptr.end() - 1), wc(Op.col_ptr.begin(), Op.col_ptr.end() - 1);
+  each([&](int64_t t, int64_t c, int64_t r, int64_t pos) {
+    const int32_t er = wr[r]++, ec = wc[c]++;
+    Op.row_key[er] = (int32_t)(t * d.Nx + c); Op.row_perm[er] = (int32_t)pos;
+    Op.col_key[ec] = (int32_t)(t * N + r); Op.col_perm[ec] = (int32_t)pos;
+  });
+  return 0;
+}
+
 }  // namespace sls

@@ -223,4 +223,17 @@ int build_fir_operator(const sls_dims* dims, const sls_csc_f64* A, const sls_csc
 // sls_controller.h).
 int build_controller_operator(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, FirOperator& out, std::string& msg);
 
+// ---- closed-loop norms (sls_norms.h): G[t] = [Φx[t]; Φu[t]], t = 0 … T−1 (0-based; Φx[0] included), by ROWS and by COLUMNS.
+// Rows are the Nx state rows followed by the Nu input rows, N = Nx + Nu.  Both tables list the stored-true entries of all
+// Sx[t], Su[t], each pointing back into the mask-order value array: row i holds its entries ascending in (t, col) with
+// key = t·Nx + col, column j ascending in (t, row) with key = t·N + row.  A sibling of the FirOperator lists above (which skip
+// Φx[0] and address a history); it shares nothing with them but the mask checks.
+struct NormsOperator {
+  int64_t Nx = 0, Nu = 0, T = 0, n_values = 0;
+  std::vector<int32_t> row_ptr, row_key, row_perm;   // N+1, n_entries, n_entries
+  std::vector<int32_t> col_ptr, col_key, col_perm;   // Nx+1, n_entries, n_entries
+};
+// dims: Nx, Nu, T, index_base are read.  SLS_EUNSUPPORTED when T·N or the value array exceeds int32.
+int build_norms_operator(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, NormsOperator& out, std::string& msg);
+
 }  // namespace sls
