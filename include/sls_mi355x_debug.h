@@ -46,6 +46,13 @@ int sls_plan_debug_twisted4_tables(sls_plan* plan, int64_t* n_columns, int32_t* 
  * the order q = (0,0), (0,1), … (0,TR−1), (1,1), … — the upper block triangle of the symmetric S_k, rows and columns beyond ñx
  * included (δ on their diagonal).  Every output but n_columns may be NULL.  SLS_EINVAL when the plan has no four-wave launch
  * or keeps no pool (SLS_T4_PRESTATIC=0 in lab mode, or a pool beyond the plan's byte budget). */
+/* The setup images of the same columns (the third thing twisted4_prepare_kernel builds, kept exactly when the static blocks
+ * are), in col_status order: per column first the dense image of Ã the launch holds in LDS — ad_doubles[i] = 8·TR·40 doubles, row
+ * i of Ã at [40·i … 40·i + ñx), zero elsewhere — then the weight table Wx, (T + 1) rows of 32: row k holds mask_k ⊙ H⁻¹ on the
+ * column's ñx state rows, zero beyond them and in row T.  offsets[n + 1]: column i's doubles are images[offsets[i] … offsets[i + 1]).
+ * Every output but n_columns may be NULL.  SLS_EINVAL when the plan has no four-wave launch or keeps no pool. */
+int sls_plan_debug_twisted4_images(sls_plan* plan, int64_t* n_columns, int64_t* offsets, int32_t* ad_doubles, double* images);
+
 int sls_plan_debug_twisted4_static(sls_plan* plan, int64_t* n_columns, int32_t* n_slots, int64_t* offsets, double* delta,
                                    uint8_t* valid, double* blocks);
 

@@ -236,6 +236,8 @@ def load_library(path: str | None = None):
     lib.sls_plan_debug_twisted4_tables.argtypes = [vp, i64p, i32p, i64p, i32p, i32p, dp, C.POINTER(C.c_uint64)]
     lib.sls_plan_debug_twisted4_static.restype = C.c_int
     lib.sls_plan_debug_twisted4_static.argtypes = [vp, i64p, i32p, i64p, dp, u8p, dp]
+    lib.sls_plan_debug_twisted4_images.restype = C.c_int
+    lib.sls_plan_debug_twisted4_images.argtypes = [vp, i64p, i64p, i32p, dp]
     lib.sls_debug_plan_tables.restype = C.c_int
     lib.sls_debug_plan_tables.argtypes = [vp, C.c_int, C.POINTER(sls_dims), C.POINTER(sls_plant), C.POINTER(sls_csc_bool),
                                           C.POINTER(sls_csc_bool), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,

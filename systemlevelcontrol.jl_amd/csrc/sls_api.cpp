@@ -265,6 +265,7 @@ hipError_t launch_twisted4_prepares(sls_plan* pl, hipStream_t stream) {
     q.order_off = L.order_off; q.nsub = L.nsub; q.t4_stride = pl->t4_stride;
     q.w_mcap = L.mcap;
     q.t4_static = pl->d_t4s ? pl->d_t4s + L.t4s_off : nullptr; q.t4_static_stride = L.t4s_stride;
+    q.t4_images = pl->d_t4s ? pl->d_t4i + L.t4i_off : nullptr; q.t4_images_stride = L.t4i_stride;
     hipError_t e = launch_twisted4_prepare(L.cls, q, pl->d_t4 + L.t4_off * pl->t4_stride, stream);
     if (e != hipSuccess) return e;
   }
@@ -876,16 +877,19 @@ static int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_pla
       L.t4_off = pl->t4_records; pl->t4_records += L.nsub;
       L.t4s_stride = twisted4_static_doubles(L.cls, kp.T);
       L.t4s_off = pl->t4s_doubles; pl->t4s_doubles += L.t4s_stride * L.nsub;
+      L.t4i_stride = twisted4_image_doubles(L.cls, kp.T);
+      L.t4i_off = pl->t4i_doubles; pl->t4i_doubles += L.t4i_stride * L.nsub;
     }
   if (pl->t4_records) {
     pl->t4_stride = twisted4_record_bytes(kp.w_nzA, kp.w_nzAc, kp.w_nzB, kp.w_nzBc, kp.T);
     if ((rc = dalloc(pl, (size_t)(pl->t4_records * pl->t4_stride), &pl->d_t4))) return bail(rc);
     // A four-wave launch has at most one column per compute unit, a column (T + 1) slots of 3 or 5 KiB: the README chain takes
     // 5.3 MiB, 256 columns at T = 29 take 23 MiB.  Beyond the budget (256 columns: horizons past 84 in the three-tile classes,
-    // past 50 in the four-tile ones) the plan keeps no pool and its launches use the rebuild instantiation.
+    // past 50 in the four-tile ones) the plan keeps no pool and its launches use the rebuild instantiation.  The setup images
+    // (15 KiB a column on the README chain: 0.9 MiB) belong to the same decision and the same budget.
     const char* pre = sls_knob("SLS_T4_PRESTATIC");
-    if (!(pre && pre[0] == '0') && pl->t4s_doubles * (int64_t)sizeof(double) <= kT4StaticBudget)
-      if ((rc = dalloc(pl, (size_t)pl->t4s_doubles, &pl->d_t4s))) return bail(rc);
+    if (!(pre && pre[0] == '0') && (pl->t4s_doubles + pl->t4i_doubles) * (int64_t)sizeof(double) <= kT4StaticBudget)
+      if ((rc = dalloc(pl, (size_t)pl->t4s_doubles, &pl->d_t4s)) || (rc = dalloc(pl, (size_t)pl->t4i_doubles, &pl->d_t4i))) return bail(rc);
   }
   tick("launch list + requests");
   if ((rc = arena_commit(pl))) return bail(rc);
@@ -1202,6 +1206,7 @@ static int enqueue_launches(sls_plan* plan, const KernelParams& kp, hipStream_t 
         q.t4_rec = plan->d_t4 + L.t4_off * plan->t4_stride; q.t4_stride = plan->t4_stride;
         q.t4_pos = sel ? sel->pos + L.order_off : nullptr;
         q.t4_static = plan->d_t4s ? plan->d_t4s + L.t4s_off : nullptr; q.t4_static_stride = L.t4s_stride;
+        q.t4_images = plan->d_t4s ? plan->d_t4i + L.t4i_off : nullptr; q.t4_images_stride = L.t4i_stride;
       }
       e = (L.kind == LaunchKind::Twisted) ? (L.four ? launch_twisted4(L.cls, q, grid, L.lds, ls) : launch_twisted(L.cls, q, grid, L.lds, ls))
                         : launch_wave(L.cls, q, grid, L.lds, ls);

@@ -325,4 +325,39 @@ int sls_plan_debug_twisted4_static(sls_plan* plan, int64_t* n_columns, int32_t* 
   return 0;
 }
 
+/* diagnostics (include/sls_mi355x_debug.h): the setup images (Ã's dense image, then the weight table Wx) of the four-wave columns, in col_status order */
+int sls_plan_debug_twisted4_images(sls_plan* plan, int64_t* n_columns, int64_t* offsets, int32_t* ad_doubles, double* images) {
+  if (!plan || !n_columns) return fail(nullptr, SLS_EINVAL, "null argument");
+  if (!plan->t4_records) return fail(plan->ctx, SLS_EINVAL, "this plan has no four-wave launch");
+  if (!plan->d_t4s || !plan->d_t4i) return fail(plan->ctx, SLS_EINVAL, "this plan keeps no setup images (its launches build them)");
+  *n_columns = plan->t4_records;
+  struct Col { int64_t out_index, first, doubles; int32_t ad; };
+  std::vector<Col> by_col;
+  for (const auto& L : plan->launches) {
+    if (!(L.kind == LaunchKind::Twisted && L.four)) continue;
+    for (int s = 0; s < L.nsub; ++s)
+      by_col.push_back({plan->sym.subs[(size_t)plan->sym.order[(size_t)L.order_off + s]].out_index, L.t4i_off + s * L.t4i_stride,
+                        L.t4i_stride, (int32_t)twisted4_image_ad_doubles(twisted4_tile_rows(L.cls))});
+  }
+  std::sort(by_col.begin(), by_col.end(), [](const Col& a, const Col& b) { return a.out_index < b.out_index; });
+  int64_t o = 0;
+  for (size_t i = 0; i < by_col.size(); ++i) {
+    if (offsets) offsets[i] = o;
+    if (ad_doubles) ad_doubles[i] = by_col[i].ad;
+    o += by_col[i].doubles;
+  }
+  if (offsets) offsets[by_col.size()] = o;
+  if (!images) return 0;
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  HIPCHK(plan->ctx, hipDeviceSynchronize());      // a plant update may still be rewriting the pool on the caller's stream
+  std::vector<double> host((size_t)plan->t4i_doubles);
+  HIPCHK(plan->ctx, hipMemcpy(host.data(), plan->d_t4i, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+  o = 0;
+  for (size_t i = 0; i < by_col.size(); ++i) {
+    std::memcpy(images + o, host.data() + by_col[i].first, (size_t)by_col[i].doubles * sizeof(double));
+    o += by_col[i].doubles;
+  }
+  return 0;
+}
+
 }  // extern "C"

@@ -88,6 +88,9 @@ struct KernelParams {
   // like the records; NULL = the launch rebuilds them (twisted4_prepare_kernel then writes none either)
   double* t4_static;
   int64_t t4_static_stride;   // doubles per column
+  // the setup images of THIS launch's columns (twisted4_image_doubles below), indexed like the records; NULL together with t4_static
+  double* t4_images;
+  int64_t t4_images_stride;   // doubles per column
 };
 
 // LDS bytes the general kernel needs for given caps (must match the carve in the kernel).
@@ -235,6 +238,14 @@ static inline __host__ __device__ int twisted4_tile_rows(int cls) { return cls <
 static inline __host__ __device__ int64_t twisted4_static_doubles(int cls, int T) {
   const int64_t TR = twisted4_tile_rows(cls);
   return (int64_t)(T + 1) * (TR * (TR + 1) / 2) * 64;
+}
+// Setup images of one four-wave column, as the launch's LDS holds them: the dense image Ad of Ã (8·TR rows, leading dimension 40,
+// zero padded), then the weight table wxt ((T + 1) rows of 32: Wx_k of every block, row T = 0).  They depend only on the plan's
+// copy of A, the masks and the weights: twisted4_prepare_kernel writes them next to the static blocks, and the instantiation
+// that reads those copies them into LDS instead of building them.
+static inline __host__ __device__ int64_t twisted4_image_ad_doubles(int tile_rows) { return (int64_t)8 * tile_rows * 40; }
+static inline __host__ __device__ int64_t twisted4_image_doubles(int cls, int T) {
+  return twisted4_image_ad_doubles(twisted4_tile_rows(cls)) + (int64_t)(T + 1) * 32;
 }
 
 // ---- device mask recipe (sls_masks.hip) ----

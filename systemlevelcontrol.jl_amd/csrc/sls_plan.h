@@ -44,12 +44,17 @@ struct sls_plan {
   // SLS_T4_PRESTATIC=0 (lab mode).
   double* d_t4s = nullptr;
   int64_t t4s_doubles = 0;
+  // The setup images (Ã's dense image and the weight table Wx, sls_device.h: twisted4_image_doubles) of the same columns, from
+  // the same kernel; kept exactly when d_t4s is, and counted in the same budget.
+  double* d_t4i = nullptr;
+  int64_t t4i_doubles = 0;
   struct Launch : sls::LaunchSpec {    // what kernel selection decided + what the launch runs on
     explicit Launch(const sls::LaunchSpec& spec) : sls::LaunchSpec(spec) {}
     hipStream_t stream = nullptr;      // aux stream (launch 0 runs on the caller's stream)
     hipEvent_t done = nullptr;
     int64_t t4_off = 0;                // four-wave launch: its first record in d_t4
     int64_t t4s_off = 0, t4s_stride = 0;   // … its first double in d_t4s, doubles per column
+    int64_t t4i_off = 0, t4i_stride = 0;   // … and in d_t4i
   };
   std::vector<Launch> launches;
   hipEvent_t ev_fork = nullptr;

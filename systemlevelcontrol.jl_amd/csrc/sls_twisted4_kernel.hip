@@ -35,7 +35,9 @@
 // plan-owned pool; a launch copies the record into LDS with coalesced loads and builds its dense images from there.
 // The static parts S_k themselves (and δ) are plan constants too: the same kernel builds them into a second pool, in the helper's
 // register layout, and the helpers load them (h2_column_twisted4_kernel<…, PRE = true>); the instantiation with PRE = false
-// still rebuilds them per launch, for plans whose pool would be too large and for SLS_T4_PRESTATIC=0.
+// still rebuilds them per launch, for plans whose pool would be too large and for SLS_T4_PRESTATIC=0.  With the blocks go the two
+// setup images that depend on the plan alone — the dense image of Ã and the weight table Wx — in a third pool: the PRE
+// instantiation copies them, the other one builds them in a second setup stage.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <utility>
@@ -484,7 +486,8 @@ static inline __host__ __device__ bool twisted4_slot_read(int slot, int T, int c
 
 template <int NPL, int RPL, bool PRE>
 __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, const SubDesc& sd, const unsigned char* __restrict__ rec,
-                                                      const double* __restrict__ spool, double* __restrict__ fac, unsigned char* lds_raw) {
+                                                      const double* __restrict__ spool, const double* __restrict__ images,
+                                                      double* __restrict__ fac, unsigned char* lds_raw) {
   static_assert(NPL == 32, "written for the NPL = 32 classes (8×8 lane grid)");
   constexpr int HS = 64 / NPL, NP = HS * RPL;
   constexpr int TR = (NP + 7) / 8, NR = 8 * TR, TT = TR * TR;
@@ -547,6 +550,17 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
   auto lap = [&](int slot) { const unsigned long long now = __builtin_amdgcn_s_memtime(); tc[slot] += now - tlast; tlast = now; };
 
   __syncthreads();
+  // Plan-time blocks: each helper asks for the static block of its first step (upward: slot 0, downward: slot T) before anything
+  // else — step s = 1 has no elimination beside it to hide the load behind, and the chain wave waits for its hand-over.
+  constexpr int TQ0 = TR * (TR + 1) / 2;
+  double Sl0[TQ0];
+  if constexpr (PRE) {
+    if (helper) {
+      const double* src = spool + (int64_t)(dir == 0 ? 0 : T) * (TQ0 * 64) + lane;
+#pragma unroll
+      for (int q = 0; q < TQ0; ++q) Sl0[q] = src[q * 64];
+    }
+  }
   // ---- setup, split over the four waves ----
   // The row lists of Ã, Ãᵀ, B̃, B̃ᵀ, their lengths and the mask-repeat bits come from the column's prepared record
   // (twisted4_prepare_kernel, once per plan): one coalesced copy onto the list images, which lie in the record in LDS order.
@@ -555,6 +569,11 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
     const unsigned long long* src = reinterpret_cast<const unsigned long long*>(rec + kT4RecHeader);
     unsigned long long* dst = reinterpret_cast<unsigned long long*>(arow_v);
     for (int i = threadIdx.x; i < nw; i += 256) dst[i] = src[i];
+    // … and with plan-time blocks the two images of the setup, which lie in the column's pool as the launch would build them
+    if constexpr (PRE) {
+      for (int i = threadIdx.x; i < NR * LDT; i += 256) Ad[i] = images[i];
+      for (int i = threadIdx.x; i < (T + 1) * NPL; i += 256) wxt[i] = images[NR * LDT + i];
+    }
   }
   if (wv == 0) {
     if (lane < NPL) {
@@ -566,8 +585,10 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
   } else if (wv == 1) {
     for (int i = lane; i < T * nm; i += 64) mask[i] = p.mask_pool[sd.off_mask + i];
   } else if (wv == 2) {
-    for (int i = lane; i < NR * LDT; i += 64) Ad[i] = 0.0;
-    if constexpr (!PRE) { for (int i = lane; i < NPL * MC; i += 64) Bd[i] = 0.0; }
+    if constexpr (!PRE) {
+      for (int i = lane; i < NR * LDT; i += 64) Ad[i] = 0.0;
+      for (int i = lane; i < NPL * MC; i += 64) Bd[i] = 0.0;
+    }
   } else {
     if (lane < 4) nzs[lane] = reinterpret_cast<const int32_t*>(rec + 16)[lane];
     // δ depends on the weights and the row lists only: with the plan-time blocks it comes from the record, like them
@@ -581,10 +602,10 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
     flagA[lane] = 0;                                      // flagA[0..1], flagB[0..1] of this direction
   }
   __syncthreads();
-  // LDS only from here: no global chain, no search
-  if (PRE && wv < 2) {
-    // plan-time static blocks: no δ reduction and no dense B̃ in the launch (the regions stay in the carve, unused)
-  } else if (wv == 0) {
+  // LDS only from here: no global chain, no search.  With plan-time blocks this stage and its barrier do not exist: no δ
+  // reduction, no dense B̃ (the regions stay in the carve, unused), and the images of Ã and Wx were copied above.
+  if constexpr (!PRE) {
+  if (wv == 0) {
     const int a0 = nzs[0], a2 = nzs[2];
     double sc = 0.0;
     if (lane < n) {
@@ -618,14 +639,13 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
       const int k = i / NPL, jj = i % NPL;
       wxt[i] = (k < T && jj < n && mask[k * nm + jj]) ? hx[jj] : 0.0;
     }
-    if constexpr (!PRE) {
-      for (int i = lane; i < T * MC; i += 64) {
-        const int k = i / MC, q = i % MC;
-        wut[i] = (q < m && mask[k * nm + n + q]) ? hu[q] : 0.0;
-      }
+    for (int i = lane; i < T * MC; i += 64) {
+      const int k = i / MC, q = i % MC;
+      wut[i] = (q < m && mask[k * nm + n + q]) ? hu[q] : 0.0;
     }
   }
   __syncthreads();
+  }
   const int nzA = nzs[0], nzAc = nzs[1], nzB = nzs[2], nzBc = nzs[3];
   const double delta = red[4];
   lap(0);
@@ -665,6 +685,9 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
   constexpr int PN = TILE ? TT : RPL;                      // registers (and workspace rows) per block
   const int wi = TILE ? tb + 8 * twisted4_tile_slot(ta) : lane;
   const bool wr = TILE ? ((0x15u >> ta) & 1u) != 0 : (lane < NPL);        // a = 0, 2, 4 (a shift, not three compares: no branches)
+  auto wk_arg = [&](int k) -> double {                     // the sweeps' weight argument: only the column layout reads it
+    if constexpr (TILE) return 0.0; else return wx_of(k);
+  };
   auto matvec = [&](const double (&Pk)[PN]) -> double {
     if constexpr (TILE) {
       return matvec_tiles(Pk, tmp2[ta], tmp2[ta + 8], tmp2[ta + 16]);
@@ -797,7 +820,7 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
   auto elim_down = [&](int k, const double (&Pk)[PN], double wk) {
     if (lane < NPL) {
       double a = rq[k * NPL + lane];
-      if (k < T) a += wk * dotA_col(tmp);                    // tmp = q_{k+1}
+      if (k < T) a += (TILE ? wxt[k * NPL + lane] : wk) * dotA_col(tmp);      // tmp = q_{k+1}
       tmp2[lane] = (lane < n) ? a : 0.0;
     }
     WSYNC();
@@ -809,7 +832,7 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
     if (lane < NPL) {
       double a = rq[c * NPL + lane];
       if (c >= 1) a += dotA_row(tmp);
-      a += wx_of(c) * dotA_col(rq + (c + 1) * NPL);
+      a += (TILE ? wxt[c * NPL + lane] : wx_of(c)) * dotA_col(rq + (c + 1) * NPL);
       tmp2[lane] = (lane < n) ? a : 0.0;
     }
     WSYNC();
@@ -835,17 +858,34 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
     } else if (wv == 1) {
       for (int k = c + 1; k <= T; ++k) {
         load_P(k, Pk);
-        if (lane < NPL) tmp[lane] = wx_of(k - 1) * rq[(k - 1) * NPL + lane];     // Wx_{k−1} Δλ_{k−1}
-        WSYNC();
+        // tmp = Wx_{k−1} Δλ_{k−1}.  Three-tile classes: the step before wrote it together with rq[k − 1] (as elim_up does); only
+        // the first step, whose predecessor is wave 0's `middle`, forms it here.  Entries 24 … 31 are written by that first step
+        // alone (zeros: wxt is 0 beyond ñx) and no dot product reads them.
+        if (!TILE || k == c + 1) {
+          if (lane < NPL) tmp[lane] = (TILE ? wxt[(k - 1) * NPL + lane] : wx_of(k - 1)) * rq[(k - 1) * NPL + lane];
+          WSYNC();
+        }
         if (lane < NPL) tmp2[lane] = (lane < n) ? dotA_row(tmp) : 0.0;
         WSYNC();
         const double dl = matvec(Pk) + (wr ? rq[k * NPL + wi] : 0.0);
-        if (wr) { rq[k * NPL + wi] = dl; lam[k * NPL + wi] += dl; }
+        if (wr) {
+          rq[k * NPL + wi] = dl; lam[k * NPL + wi] += dl;
+          if constexpr (TILE) tmp[wi] = wxt[k * NPL + wi] * dl;
+        }
         WSYNC();
       }
     }
   };
 
+  // SLS_PHASE_TIMERS = 4 (-DSLS_T4_PHASES=1 builds only): what follows lap(1), per wave — 0 residual passes, 1 inward sweeps of the
+  // later passes, 2 middle (wave 1: waiting for it), 3 outward sweeps (stamped BEFORE the barrier: the slower wave shows),
+  // 4 output pass, 5 the barriers behind the factor half and behind the sweeps
+  unsigned long long p4[6] = {0, 0, 0, 0, 0, 0}, t4last = 0;
+  auto stamp4 = [&](int slot) {
+    if constexpr (SLS_T4_PHASES != 0) {
+      if (p.dbg_level == 4) { const unsigned long long now = __builtin_amdgcn_s_memtime(); p4[slot] += now - t4last; t4last = now; }
+    }
+  };
   unsigned long long ph[4] = {0, 0, 0, 0};      // diagnostics (SLS_PHASE_TIMERS ≥ 2): chain wave: hand-off waits / Gauss–Jordan / store + sweep; helper: static + border / elimination / of which waiting
   if (resid > p.tol) {
     double M[PN];
@@ -1075,7 +1115,12 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
         } else {
           if constexpr (PRE) {
             double Sl[TQ];
-            load_slot(s, Sl);
+            if (s == 1) {                                    // requested in the setup
+#pragma unroll
+              for (int q = 0; q < TQ; ++q) Sl[q] = Sl0[q];
+            } else {
+              load_slot(s, Sl);
+            }
             int q = 0;
 #pragma unroll
             for (int ri = 0; ri < TR; ++ri) {
@@ -1106,12 +1151,17 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
       }
     }
     lap(1);                        // own half of the factorisation
+    if constexpr (SLS_T4_PHASES != 0) t4last = tlast;
     __syncthreads();
     lap(2);                        // waiting for the other waves
+    stamp4(5);
     if (wv == 0) middle(M);        // M = P_c
     __syncthreads();
+    stamp4(2);
     outward();
+    stamp4(3);
     __syncthreads();
+    stamp4(5);
     lap(3);
 
     // ---------------- multiplier iteration ----------------
@@ -1122,17 +1172,23 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
       if (it > 1) {
         double Pk[PN];
         if (wv == 0) {
-          for (int k = 0; k < c; ++k) { load_P(k, Pk); elim_up(k, Pk, wx_of(k)); }
+          for (int k = 0; k < c; ++k) { load_P(k, Pk); elim_up(k, Pk, wk_arg(k)); }
         } else if (wv == 1) {
-          for (int k = T; k > c; --k) { load_P(k, Pk); elim_down(k, Pk, wx_of(k)); }
+          for (int k = T; k > c; --k) { load_P(k, Pk); elim_down(k, Pk, wk_arg(k)); }
         }
+        stamp4(1);
         __syncthreads();
+        stamp4(5);
         if (wv == 0) { load_P(c, Pk); middle(Pk); }
         __syncthreads();
+        stamp4(2);
         outward();
+        stamp4(3);
         __syncthreads();
+        stamp4(5);
       }
       resid = residual_pass();
+      stamp4(0);
       if (resid <= p.tol) break;
       if (it >= 2 && resid > p.stag * prev) {          // (still_contracting: sls_device.h)
         if (!(p.max_iters_slow > 0 && (resid > p.tol_ok || itmax > p.max_iters) && still_contracting(it >= 3 ? prev2 : prev, prev, resid))) { status = 1; break; }
@@ -1143,7 +1199,9 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
     if (resid <= p.tol_ok) status = 0;
     else if (status == 0) status = 2;
   }
+  if constexpr (SLS_T4_PHASES != 0) { if (t4last == 0) t4last = __builtin_amdgcn_s_memtime(); }      // (a column that needed no pass)
   output_pass();
+  stamp4(4);
   if (p.dbg && lane == 0) {
     const unsigned long long now = __builtin_amdgcn_s_memtime();
     if (p.dbg_level <= 1 && wv < 2) {
@@ -1156,6 +1214,9 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
         p.dbg[sd.out_index * 8 + dir * 4 + 2] = (ph[2] & 0xffffffffull) | (tc[0] << 32);
         p.dbg[sd.out_index * 8 + dir * 4 + 3] = (tc[1] & 0xffffffffull) | (ph[3] << 32);
       }
+    } else if (SLS_T4_PHASES != 0 && p.dbg_level == 4 && wv < 2) {       // 4: the chain waves' time after the factor half, two shares per slot
+      for (int q = 0; q < 3; ++q) p.dbg[sd.out_index * 8 + wv * 4 + q] = (p4[2 * q] & 0xffffffffull) | (p4[2 * q + 1] << 32);
+      p.dbg[sd.out_index * 8 + wv * 4 + 3] = tc[1];
     }
   }
   if (sd.pos < 0 && status == 0) status = 3;
@@ -1176,7 +1237,8 @@ __global__ __launch_bounds__(256, 1) void h2_column_twisted4_kernel(const Kernel
     const SubDesc sd = p.subs[p.order[p.order_off + s]];
     const int rs = p.t4_pos ? p.t4_pos[s] : s;      // a selected run: the record (and the pool) of the column's place in the full launch
     const double* spool = PRE ? p.t4_static + (int64_t)rs * p.t4_static_stride : nullptr;
-    twisted4_solve_column<NPL, RPL, PRE>(p, sd, p.t4_rec + (int64_t)rs * p.t4_stride, spool, fac, lds_raw);
+    const double* images = PRE ? p.t4_images + (int64_t)rs * p.t4_images_stride : nullptr;
+    twisted4_solve_column<NPL, RPL, PRE>(p, sd, p.t4_rec + (int64_t)rs * p.t4_stride, spool, images, fac, lds_raw);
   }
 }
 
@@ -1342,6 +1404,13 @@ __global__ __launch_bounds__(256) void twisted4_prepare_kernel(const KernelParam
       }
     }
     __syncthreads();
+    // the two images a launch would build the same way (Ã: zero fill, then `+=` in list order; Wx: mask ⊙ H⁻¹), as they stand here
+    if (p.t4_images) {
+      double* img = p.t4_images + (int64_t)blockIdx.x * p.t4_images_stride;
+      constexpr int NAD = NR * LDT;
+      for (int i = threadIdx.x; i < NAD; i += 256) img[i] = Ad[i];
+      for (int i = threadIdx.x; i < (T + 1) * NPL; i += 256) img[NAD + i] = wxt[i];
+    }
     const double delta = sdelta;
     const int c = twisted4_middle(T);
     const unsigned long long up = (SLS_T4_SAME != 0) ? sbits[0] : 0ull, down = (SLS_T4_SAME != 0) ? sbits[1] : 0ull;

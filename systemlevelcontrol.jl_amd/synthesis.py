@@ -376,6 +376,22 @@ class Plan:
         return {"delta": delta, "valid": valid,
                 "blocks": [blocks[off[i]:off[i + 1]].reshape(ns, -1, 64).copy() for i in range(n)]}
 
+    def twisted4_images(self):
+        """sls_plan_debug_twisted4_images: the plan-time setup images of the plan's four-wave columns, in col_status order, as a
+        dict — `Ad`, a list of n arrays [8·TR, 40] (the dense image of Ã the launch holds in LDS), and `wxt`, a list of n arrays
+        [T + 1, 32] (the weight table Wx).  Raises SLSError when the plan has no four-wave launch or keeps no pool."""
+        f = self._lib.sls_plan_debug_twisted4_images
+        i32p, i64p, dp = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+        n = C.c_int64()
+        _capi.check(f(self.handle, C.byref(n), None, None, None), self.ctx.handle)
+        n = n.value
+        off = np.zeros(n + 1, dtype=np.int64); ad = np.zeros(n, dtype=np.int32)
+        _capi.check(f(self.handle, C.byref(C.c_int64()), off.ctypes.data_as(i64p), ad.ctypes.data_as(i32p), None), self.ctx.handle)
+        img = np.zeros(max(int(off[-1]), 1), dtype=np.float64)
+        _capi.check(f(self.handle, C.byref(C.c_int64()), None, None, img.ctypes.data_as(dp)), self.ctx.handle)
+        return {"Ad": [img[off[i]:off[i] + ad[i]].reshape(-1, 40).copy() for i in range(n)],
+                "wxt": [img[off[i] + ad[i]:off[i + 1]].reshape(-1, 32).copy() for i in range(n)]}
+
     def kernel_time_ms(self):
         avg = C.c_double(); n = C.c_int64()
         _capi.check(self._lib.sls_plan_kernel_time_ms(self.handle, C.byref(avg), C.byref(n)), self.ctx.handle)

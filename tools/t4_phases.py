@@ -1,5 +1,7 @@
-"""Phase shares inside the four-wave twisted kernel's factor half (SLS_PHASE_TIMERS=1: laps; 2: chain waves; 3: helper waves).
-Levels 2 and 3 need the per-pivot stamps compiled in: make -C systemlevelcontrol.jl_amd/csrc -B EXTRA=-DSLS_T4_PHASES=1.
+"""Phase shares inside the four-wave twisted kernel (SLS_PHASE_TIMERS=1: laps; 2: chain waves' factor half; 3: helper waves;
+4: the chain waves' time AFTER the factor half — residual passes, inward sweeps of the later passes, middle, outward sweeps,
+output pass, barriers — for the column with the longest factor half).
+Levels 2 to 4 need the stamps compiled in: make -C systemlevelcontrol.jl_amd/csrc -B EXTRA=-DSLS_T4_PHASES=1.
 Level 3 also prints, per helper wave, the setup lap (launch → end of the setup stage) and the pre-loop stamp (end of setup →
 entry of the helper's block loop), which that build packs into the high halves of two slots."""
 import ctypes as C, os, sys
@@ -25,6 +27,12 @@ if lvl == "1":
     for w in (0, 1):
         hi = int(b[k, w, 3]) >> 32; lo = int(b[k, w, 3]) & 0xffffffff
         print(f"chain wave {w} (column {k}): setup {b[k,w,0]}, own factor half {b[k,w,1]}, wait {b[k,w,2]}, middle+outward {hi}, later passes+residual+output {lo}; total {b[k,w,0]+b[k,w,1]+b[k,w,2]+hi+lo}")
+elif lvl == "4":
+    k = int(np.argmax(b[:, 0, 3]))
+    names = ("residual passes", "inward sweeps (later passes)", "middle", "outward sweeps", "output pass", "barriers")
+    for w in (0, 1):
+        v = [(int(b[k, w, q // 2]) >> (32 * (q % 2))) & 0xffffffff for q in range(6)]
+        print(f"chain wave {w} (column {k}): " + ", ".join(f"{nm} {x}" for nm, x in zip(names, v)) + f"; sum {sum(v)}; factor half {b[k,w,3]}")
 else:
     names = ("hand-off waits", "Gauss-Jordan", "convert+store+sweep") if lvl == "2" else ("static part + border", "elimination (incl. waits)", "of which waiting for pivots")
     lo32 = lambda v: int(v) & 0xffffffff
