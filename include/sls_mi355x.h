@@ -565,7 +565,28 @@ void sls_controller_destroy(sls_controller* ctl);
  * upload that still reads the pinned buffer.  The caller issues the calls of one object on one stream or orders them with events.
  * sls_norms_fetch_l1 / sls_norms_fetch_hinf: the same passes into the plan-owned buffer on `hip_stream`, waited for and copied
  *   to HOST arrays (each nullable), like sls_plan_fetch_objective.
- * sls_norms_info (each output nullable): stored-true entries (a pass reads 12 B each), device bytes held, max_freq. */
+ * sls_norms_info (each output nullable): stored-true entries (a pass reads 12 B each), device bytes held, max_freq.
+ *
+ * 𝓗₂ shares and covariance.  Under unit white w the steady-state covariance of z is Σ = Σ_{t<T} G[t]·G[t]ᵀ — exact for the FIR
+ * closed loop from step T on.
+ * sls_norms_h2: outputs on the DEVICE, each may be NULL.  row_h2[i] = Σ_t Σ_j G[t][i,j]² (N) is the variance of z_i, its square
+ *   root the RMS of that state or actuator; col_h2[j] = Σ_t Σ_i G[t][i,j]² (Nx) is the share of disturbance j — with cz / b from
+ *   the plant and D11 = 0 the number sls_plan_objective reports for column j; totals[0] = Σ_i row_h2[i], the squared 𝓗₂ norm,
+ *   totals[1] = max_i row_h2[i].  The 𝓛₁ pass with fma(v, v, ·) per entry: a fixed order, no floating-point atomics, bit-identical
+ *   from call to call; a sum that comes out NaN is reported as +inf.  Asynchronous on `hip_stream`, allocates nothing.  The
+ *   plan-owned copy of the result takes the place of the 𝓛₁ one (a fetch call always makes its own pass first).
+ * sls_norms_cov_pattern: the entries of Σ the caller wants, pair_i[p], pair_j[p] in HOST memory (index_base of the plan's dims
+ *   applies): any order, duplicates and i == j allowed.  SLS_EINVAL for an index outside the N rows (the message names p) or
+ *   npairs < 0, SLS_EUNSUPPORTED for npairs > 2³¹ − 1; the pattern in place is kept then.  Uploads the list and allocates it and
+ *   a result buffer (16 B per pair, counted in sls_norms_info's device_bytes from then on); a second call replaces the first
+ *   after the device is idle; npairs = 0 clears the pattern.  Waits; may be called before or after sls_norms_load.
+ * sls_norms_cov: d_cov [npairs] on the DEVICE: cov[p] = Σ_t Σ_k G[t][i_p,k]·G[t][j_p,k], the sum over the keys the two row lists
+ *   share, one wave per pair.  Bit-identical from call to call; (i,j) and (j,i) give the same bits; the value of a pair does not
+ *   depend on the other pairs of the list or on its place in it; a pair without a shared key gives exactly 0.0; a NaN in a
+ *   shared entry reaches that pair and no other.  SLS_EINVAL before the first load, without a pattern, for a NULL output (all
+ *   refused before anything is enqueued).  Asynchronous, allocates nothing.
+ * sls_norms_fetch_h2 / sls_norms_fetch_cov: the same passes into object-owned buffers, waited for and copied to HOST arrays
+ *   (each nullable). */
 typedef struct sls_norms sls_norms;
 int  sls_norms_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su,
                     const double* cz, const double* b, int64_t max_freq, sls_norms** out);
@@ -576,6 +597,11 @@ int  sls_norms_hinf(sls_norms* norms, void* hip_stream, const double* omega, int
 int  sls_norms_fetch_l1(sls_norms* norms, void* hip_stream, double* row_l1, double* col_l1, double* totals);
 int  sls_norms_fetch_hinf(sls_norms* norms, void* hip_stream, const double* omega, int64_t nfreq, int64_t iters, double* sigma,
                           double* peak);
+int  sls_norms_h2(sls_norms* norms, void* hip_stream, double* d_row_h2, double* d_col_h2, double* d_totals);
+int  sls_norms_fetch_h2(sls_norms* norms, void* hip_stream, double* row_h2, double* col_h2, double* totals);
+int  sls_norms_cov_pattern(sls_norms* norms, int64_t npairs, const int64_t* pair_i, const int64_t* pair_j);
+int  sls_norms_cov(sls_norms* norms, void* hip_stream, double* d_cov);
+int  sls_norms_fetch_cov(sls_norms* norms, void* hip_stream, double* cov);
 int  sls_norms_info(const sls_norms* norms, int64_t* n_entries, int64_t* device_bytes, int64_t* max_freq);
 void sls_norms_destroy(sls_norms* norms);
 

@@ -150,6 +150,17 @@ int sls_debug_norms_host(const sls_dims* dims, const sls_csc_bool* Sx, const sls
                          const double* b, const double* omega, int64_t nfreq, int64_t iters, double* row_l1, double* col_l1,
                          double* totals, double* sigma, double* peak);
 
+/* Host twin of sls_norms_load + sls_norms_h2 (csrc/sls_norms.cpp): fma(v, v, ·) per entry over the same tables, rows and entries
+ * ascending, in double.  Outputs, each nullable: row_h2 [N], col_h2 [Nx], totals [2] (Σ row_h2, max row_h2).  Needs no device. */
+int sls_debug_norms_h2_host(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, const double* values, const double* cz,
+                            const double* b, double* row_h2, double* col_h2, double* totals);
+
+/* Host twin of sls_norms_load + sls_norms_cov_pattern + sls_norms_cov (csrc/sls_norms.cpp): cov[p] = Σ over the keys rows
+ * pair_i[p] and pair_j[p] share (index_base of dims applies) of fma(v_i, v_j, ·), by a two-pointer merge of the two row lists.
+ * SLS_EINVAL for an index out of range (the message names p) or npairs < 0.  Needs no device. */
+int sls_debug_norms_cov_host(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, const double* values, const double* cz,
+                             const double* b, int64_t npairs, const int64_t* pair_i, const int64_t* pair_j, double* cov);
+
 #ifdef __cplusplus
 }
 #endif

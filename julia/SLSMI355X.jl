@@ -11,7 +11,7 @@
 module SLSMI355X
 
 using SparseArrays
-export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!, Norms, l1, hinf
+export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!, Norms, l1, hinf, h2, covariance_pattern!, covariance
 
 const LIB = get(ENV, "SLS_MI355X_LIB", "libsls_mi355x.so")
 
@@ -216,6 +216,7 @@ EXECUTED in the build container, like the rest of this file.
 mutable struct Norms
     handle::Ptr{Cvoid}
     Nx::Int; Nu::Int; max_freq::Int
+    npairs::Int                                                          # of the covariance pattern in place (0 = none)
 end
 function Norms(ctx::Ptr{Cvoid}, Nx::Integer, Nu::Integer, 𝓢::AbstractVector; cz::Union{Nothing,Vector{Float64}}=nothing,
                b::Union{Nothing,Vector{Float64}}=nothing, max_freq::Integer=64, dev_slot::Integer=0)
@@ -232,7 +233,7 @@ function Norms(ctx::Ptr{Cvoid}, Nx::Integer, Nu::Integer, 𝓢::AbstractVector; 
                    ctx, dev_slot, dims, sx, su, cz === nothing ? C_NULL : pointer(cz), b === nothing ? C_NULL : pointer(b), max_freq, h)
     end
     rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx)))
-    return Norms(h[], Nx, Nu, max_freq)
+    return Norms(h[], Nx, Nu, max_freq, 0)
 end
 load!(n::Norms, d_values::Ptr{Cvoid}; stream::Ptr{Cvoid}=C_NULL) =
     _ctl_check(ccall((:sls_norms_load, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), n.handle, stream, d_values))
@@ -247,6 +248,34 @@ function hinf(n::Norms, ω::AbstractVector{<:Real}; iters::Integer=32, stream::P
     _ctl_check(ccall((:sls_norms_fetch_hinf, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
                      n.handle, stream, om, length(om), iters, sigma, peak))
     return sigma, peak[1], Int(peak[2]) + 1
+end
+"""
+    row_h2, col_h2, totals = h2(n);   covariance_pattern!(n, pairs_i, pairs_j);   cov = covariance(n)
+
+`sls_norms_fetch_h2`, `sls_norms_cov_pattern`, `sls_norms_fetch_cov`.  `row_h2[i] = Σₜ Σⱼ G[t][i,j]²` is the variance of `zᵢ` under
+unit white `w` (its square root the RMS of that state or actuator), `col_h2[j]` the share of disturbance `j`, `totals = (Σ row_h2,
+max row_h2)`.  `covariance_pattern!` sets the entries `(pairs_i[p], pairs_j[p])` (1-based rows: states, then inputs) of
+`Σ = Σₜ G[t]·G[t]ᵀ` that `covariance` evaluates — any order, duplicates and `i == j` allowed, empty lists clear the pattern; it
+uploads and allocates, so call it once per pattern.  `h2` and `covariance` wait for `stream`.  NOT EXECUTED in the build
+container, like the rest of this file.
+"""
+function h2(n::Norms; stream::Ptr{Cvoid}=C_NULL)
+    row = zeros(Float64, n.Nx + n.Nu);  col = zeros(Float64, n.Nx);  totals = zeros(Float64, 2)
+    _ctl_check(ccall((:sls_norms_fetch_h2, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                     n.handle, stream, row, col, totals))
+    return row, col, totals
+end
+function covariance_pattern!(n::Norms, pairs_i::AbstractVector{<:Integer}, pairs_j::AbstractVector{<:Integer})
+    length(pairs_i) == length(pairs_j) || error("pairs_i and pairs_j must have one length")
+    ip = Vector{Int64}(pairs_i);  jp = Vector{Int64}(pairs_j)
+    _ctl_check(ccall((:sls_norms_cov_pattern, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}), n.handle, length(ip), ip, jp))
+    n.npairs = length(ip)
+    return n
+end
+function covariance(n::Norms; stream::Ptr{Cvoid}=C_NULL)
+    cov = zeros(Float64, n.npairs)
+    _ctl_check(ccall((:sls_norms_fetch_cov, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}), n.handle, stream, cov))
+    return cov
 end
 function Base.close(n::Norms)
     n.handle != C_NULL && (ccall((:sls_norms_destroy, LIB), Cvoid, (Ptr{Cvoid},), n.handle); n.handle = C_NULL)

@@ -93,7 +93,7 @@ EXPORTS = [
     "sls_controller_plan", "sls_controller_load", "sls_controller_reset", "sls_controller_step", "sls_controller_info",
     "sls_controller_destroy",
     "sls_norms_plan", "sls_norms_load", "sls_norms_l1", "sls_norms_hinf", "sls_norms_fetch_l1", "sls_norms_fetch_hinf", "sls_norms_info",
-    "sls_norms_destroy",
+    "sls_norms_destroy", "sls_norms_h2", "sls_norms_fetch_h2", "sls_norms_cov_pattern", "sls_norms_cov", "sls_norms_fetch_cov",
 ]
 
 _lib = None
@@ -212,7 +212,16 @@ def load_library(path: str | None = None):
     lib.sls_norms_fetch_hinf.restype = C.c_int; lib.sls_norms_fetch_hinf.argtypes = [vp, vp, dp, C.c_int64, C.c_int64, dp, dp]
     lib.sls_norms_info.restype = C.c_int; lib.sls_norms_info.argtypes = [vp, i64p, i64p, i64p]
     lib.sls_norms_destroy.restype = None; lib.sls_norms_destroy.argtypes = [vp]
+    lib.sls_norms_h2.restype = C.c_int; lib.sls_norms_h2.argtypes = [vp, vp, vp, vp, vp]
+    lib.sls_norms_fetch_h2.restype = C.c_int; lib.sls_norms_fetch_h2.argtypes = [vp, vp, dp, dp, dp]
+    lib.sls_norms_cov_pattern.restype = C.c_int; lib.sls_norms_cov_pattern.argtypes = [vp, C.c_int64, i64p, i64p]
+    lib.sls_norms_cov.restype = C.c_int; lib.sls_norms_cov.argtypes = [vp, vp, vp]
+    lib.sls_norms_fetch_cov.restype = C.c_int; lib.sls_norms_fetch_cov.argtypes = [vp, vp, dp]
     # diagnostics outside the public header
+    lib.sls_debug_norms_h2_host.restype = C.c_int
+    lib.sls_debug_norms_h2_host.argtypes = masks + [dp, dp, dp, dp, dp, dp]
+    lib.sls_debug_norms_cov_host.restype = C.c_int
+    lib.sls_debug_norms_cov_host.argtypes = masks + [dp, dp, dp, C.c_int64, i64p, i64p, dp]
     lib.sls_debug_norms_tables.restype = C.c_int
     lib.sls_debug_norms_tables.argtypes = masks + [i64p, i32p, i32p, i32p, i32p, i32p, i32p]
     lib.sls_debug_norms_host.restype = C.c_int

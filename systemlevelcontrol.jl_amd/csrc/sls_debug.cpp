@@ -1,5 +1,6 @@
 // sls_debug.cpp — the exports of include/sls_mi355x_debug.h that look into a plan or run a host twin: diagnostics for the tests
-// and the tools, not part of the drop-in ABI.  (sls_debug_controller_* live with the controller, sls_controller.hip.)
+// and the tools, not part of the drop-in ABI.  (sls_debug_controller_* live with the controller, sls_controller.hip; the
+// tables and the 𝓛₁ / 𝓗∞ twin of the norms with sls_norms.hip.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,6 +12,7 @@
 
 #include "../../include/sls_mi355x.h"
 #include "../../include/sls_mi355x_debug.h"
+#include "sls_norms.h"
 #include "sls_objective.h"
 #include "sls_plan.h"
 #include "sls_residual.h"
@@ -357,6 +359,28 @@ int sls_plan_debug_twisted4_images(sls_plan* plan, int64_t* n_columns, int64_t* 
     std::memcpy(images + o, host.data() + by_col[i].first, (size_t)by_col[i].doubles * sizeof(double));
     o += by_col[i].doubles;
   }
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): host twin of load + h2 (csrc/sls_norms.cpp).  Needs no device. */
+int sls_debug_norms_h2_host(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, const double* values, const double* cz,
+                            const double* b, double* row_h2, double* col_h2, double* totals) {
+  NormsOperator Op;
+  std::string msg;
+  int rc = build_norms_operator(dims, Sx, Su, Op, msg);
+  if (!rc) rc = norms_h2_host(Op, values, cz, b, row_h2, col_h2, totals, msg);
+  if (rc) return fail(nullptr, rc, "sls_debug_norms_h2_host: " + msg);
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): host twin of load + cov_pattern + cov (csrc/sls_norms.cpp).  Needs no device. */
+int sls_debug_norms_cov_host(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, const double* values, const double* cz,
+                             const double* b, int64_t npairs, const int64_t* pair_i, const int64_t* pair_j, double* cov) {
+  NormsOperator Op;
+  std::string msg;
+  int rc = build_norms_operator(dims, Sx, Su, Op, msg);
+  if (!rc) rc = norms_cov_host(Op, values, cz, b, dims->index_base, npairs, pair_i, pair_j, cov, msg);
+  if (rc) return fail(nullptr, rc, "sls_debug_norms_cov_host: " + msg);
   return 0;
 }
 

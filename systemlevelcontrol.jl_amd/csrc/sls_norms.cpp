@@ -111,4 +111,69 @@ int norms_host(const NormsOperator& Op, const double* values, const double* cz, 
   return 0;
 }
 
+int norms_h2_host(const NormsOperator& Op, const double* values, const double* cz, const double* b, double* row_h2, double* col_h2,
+                  double* totals, std::string& msg) {
+  const int64_t Nx = Op.Nx, N = Op.Nx + Op.Nu;
+  std::vector<double> w_row, w_col;
+  if (int rc = norms_entry_weights(Op, cz, b, w_row, w_col, msg)) return rc;
+  const int64_t n = Op.row_ptr[N];
+  if (n > 0 && !values) { msg = "null values"; return SLS_EINVAL; }
+  auto h2 = [&](const std::vector<int32_t>& ptr, const std::vector<int32_t>& perm, const std::vector<double>& w, int64_t nlines,
+                double* out, double* tot) {
+    double sum = 0.0, mx = 0.0;
+    for (int64_t i = 0; i < nlines; ++i) {
+      double s = 0.0;
+      for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) { const double v = values[perm[e]] * w[(size_t)e]; s = std::fma(v, v, s); }
+      s = norms_l1_report(s);
+      if (out) out[i] = s;
+      sum += s; mx = std::max(mx, s);
+    }
+    if (tot) { tot[0] = sum; tot[1] = mx; }
+  };
+  if (row_h2 || totals) h2(Op.row_ptr, Op.row_perm, w_row, N, row_h2, totals);
+  if (col_h2) h2(Op.col_ptr, Op.col_perm, w_col, Nx, col_h2, nullptr);
+  return 0;
+}
+
+int norms_cov_check(int64_t N, int64_t index_base, int64_t npairs, const int64_t* pair_i, const int64_t* pair_j, std::string& msg) {
+  if (npairs < 0) { msg = "npairs must be >= 0"; return SLS_EINVAL; }
+  if (npairs > 0 && (!pair_i || !pair_j)) { msg = "null pair list"; return SLS_EINVAL; }
+  for (int64_t p = 0; p < npairs; ++p) {
+    const int64_t i = pair_i[p] - index_base, j = pair_j[p] - index_base;
+    if (i < 0 || i >= N || j < 0 || j >= N) {
+      msg = "pair " + std::to_string(p) + " (" + std::to_string(pair_i[p]) + ", " + std::to_string(pair_j[p]) + ") is outside the " +
+            std::to_string(N) + " rows";
+      return SLS_EINVAL;
+    }
+  }
+  return 0;
+}
+
+int norms_cov_host(const NormsOperator& Op, const double* values, const double* cz, const double* b, int64_t index_base, int64_t npairs,
+                   const int64_t* pair_i, const int64_t* pair_j, double* cov, std::string& msg) {
+  const int64_t N = Op.Nx + Op.Nu;
+  std::vector<double> w_row, w_col;
+  if (int rc = norms_entry_weights(Op, cz, b, w_row, w_col, msg)) return rc;
+  if (int rc = norms_cov_check(N, index_base, npairs, pair_i, pair_j, msg)) return rc;
+  const int64_t n = Op.row_ptr[N];
+  if (n > 0 && !values) { msg = "null values"; return SLS_EINVAL; }
+  if (npairs > 0 && !cov) { msg = "null output"; return SLS_EINVAL; }
+  std::vector<double> rv((size_t)n);                                   // the gather of sls_norms_load, row order
+  for (int64_t e = 0; e < n; ++e) rv[(size_t)e] = values[Op.row_perm[e]] * w_row[(size_t)e];
+  for (int64_t p = 0; p < npairs; ++p) {
+    int32_t i = (int32_t)(pair_i[p] - index_base), j = (int32_t)(pair_j[p] - index_base);
+    if (norms_cov_swap(i, Op.row_ptr[i + 1] - Op.row_ptr[i], j, Op.row_ptr[j + 1] - Op.row_ptr[j])) std::swap(i, j);
+    int32_t ea = Op.row_ptr[i], eb = Op.row_ptr[j];
+    const int32_t a_end = Op.row_ptr[i + 1], b_end = Op.row_ptr[j + 1];
+    double s = 0.0;
+    while (ea < a_end && eb < b_end) {
+      const int32_t ka = Op.row_key[ea], kb = Op.row_key[eb];
+      if (ka == kb) s = std::fma(rv[(size_t)ea], rv[(size_t)eb], s);
+      ea += ka <= kb; eb += kb <= ka;
+    }
+    cov[p] = s;
+  }
+  return 0;
+}
+
 }  // namespace sls

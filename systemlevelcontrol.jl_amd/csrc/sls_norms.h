@@ -23,6 +23,15 @@
 // e^{−iωt}, plus in the adjoint — then four FMAs, re: fma(w.re, x.re, ·), fma(−w.im, x.im, ·); im: fma(w.re, x.im, ·),
 // fma(w.im, x.re, ·).  ‖·‖² is Σ fma(re, re, im·im) over the rows.
 //
+//
+// 𝓗₂ shares and covariance.  Under unit white w the steady-state covariance of z is Σ = Σ_{t<T} G[t]·G[t]ᵀ (exact for the FIR
+// closed loop from step T on: z[k] = Σ_{t<T} G[t]·w[k−t] is a finite sum of independent terms).  row_h2[i] = Σ_t Σ_j G[t][i,j]²
+// is its diagonal — the variance of z_i — and col_h2[j] = Σ_t Σ_i G[t][i,j]² the share of disturbance j; totals[0] = Σ_i row_h2
+// (the squared 𝓗₂ norm, rows ascending), totals[1] = max_i row_h2.  One entry is fma(v, v, acc); a sum that comes out NaN is
+// reported as +inf.  Σ[i,j] = Σ over the keys the row lists of i and j share of fma(v_i, v_j, acc): the lists are ascending in
+// key = t·Nx + col, so the sum is a sparse dot product of two sorted lists.  The pair is canonicalised first (norms_cov_swap:
+// the shorter list leads, the smaller row on equal lengths), so (i,j) and (j,i) run the same operations.
+//
 // The device passes are csrc/sls_norms.hip; this header holds what they share with the host twin (csrc/sls_norms.cpp).
 #pragma once
 #include <cmath>
@@ -61,6 +70,11 @@ SLS_NRM_HD static inline double norms_scale(double n2) { return n2 > 0.0 ? 1.0 /
 // what a sum of absolute values reports: +inf when a NaN went in
 SLS_NRM_HD static inline double norms_l1_report(double s) { return s != s ? (double)INFINITY : s; }
 
+// a covariance pair in the order the passes walk it: true when row j leads (its list is the shorter one, or as long and j < i)
+SLS_NRM_HD static inline bool norms_cov_swap(int32_t i, int32_t len_i, int32_t j, int32_t len_j) {
+  return len_j < len_i || (len_j == len_i && j < i);
+}
+
 // per-entry weights cz[row]·b[col] in row order and in column order (either vector NULL = ones); non-finite weights refused
 int norms_entry_weights(const NormsOperator& Op, const double* cz, const double* b, std::vector<double>& w_row,
                         std::vector<double>& w_col, std::string& msg);
@@ -71,5 +85,18 @@ int norms_entry_weights(const NormsOperator& Op, const double* cz, const double*
 // iters ≥ 1 when either is asked for).
 int norms_host(const NormsOperator& Op, const double* values, const double* cz, const double* b, const double* omega, int64_t nfreq,
                int64_t iters, double* row_l1, double* col_l1, double* totals, double* sigma, double* peak, std::string& msg);
+
+// Host twin of sls_norms_load + sls_norms_h2.  Outputs, each nullable: row_h2 [N], col_h2 [Nx], totals [2].
+int norms_h2_host(const NormsOperator& Op, const double* values, const double* cz, const double* b, double* row_h2, double* col_h2,
+                  double* totals, std::string& msg);
+
+// Range check of a covariance pattern (shared with sls_norms_cov_pattern): pair_i[p], pair_j[p] − index_base in 0 … N−1.
+// SLS_EINVAL names the first bad position p.
+int norms_cov_check(int64_t N, int64_t index_base, int64_t npairs, const int64_t* pair_i, const int64_t* pair_j, std::string& msg);
+
+// Host twin of sls_norms_load + sls_norms_cov: cov[p] over the pairs (pair_i[p], pair_j[p]) (index_base applied), a two-pointer
+// merge of the two row lists in ascending key order.
+int norms_cov_host(const NormsOperator& Op, const double* values, const double* cz, const double* b, int64_t index_base, int64_t npairs,
+                   const int64_t* pair_i, const int64_t* pair_j, double* cov, std::string& msg);
 
 }  // namespace sls

@@ -16,6 +16,10 @@
 // ‖·‖² per frequency: each wave leaves |out|² of its line, norms_norm2_kernel adds them over the lines in a fixed order (one
 // block per frequency) and leaves 1/‖·‖ for the next forward pass to read, or sigma.  No floating-point atomics; no launch
 // argument depends on device data; load, l1 and hinf allocate nothing, and only the fetch calls wait.
+//
+// 𝓗₂ shares and covariance (sls_norms.h): norms_h2_kernel is the 𝓛₁ traversal with fma(v, v, ·); norms_cov_kernel intersects the
+// sorted row lists of a pair, one wave per pair, over a pattern the caller sets once (sls_norms_cov_pattern — the only call
+// here besides the plan that allocates and waits).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -102,6 +106,105 @@ __global__ void __launch_bounds__(kBlock) norms_l1_totals_kernel(const double* _
   if (threadIdx.x != 0) return;
   res_totals[0] = m0; res_totals[1] = m1;
   if (out) { out[0] = m0; out[1] = m1; }
+}
+
+// the 𝓛₁ pass with fma(v, v, ·) per entry: row_h2 [N], col_h2 [Nx] (sls_norms.h).  The lines, the slots and the order are
+// those of norms_l1_kernel; the results take the 𝓛₁ slots of the plan-owned buffer (a fetch runs its own pass first).
+__global__ void __launch_bounds__(kBlock) norms_h2_kernel(L1Params p) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int line = blockIdx.x * kWavesPerBlock + wave;
+  if (line >= p.N + p.Nx) return;
+  const bool col = line >= p.N;
+  const int i = col ? line - p.N : line;
+  const int32_t* ptr = col ? p.col_ptr : p.row_ptr;
+  const double* vals = col ? p.vals + p.n : p.vals;
+  const int beg = ptr[i], end = ptr[i + 1];
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  int e = beg + lane;
+  for (; e + 192 < end; e += 256) {
+    const double v0 = vals[e], v1 = vals[e + 64], v2 = vals[e + 128], v3 = vals[e + 192];
+    a0 = fma(v0, v0, a0); a1 = fma(v1, v1, a1); a2 = fma(v2, v2, a2); a3 = fma(v3, v3, a3);
+  }
+  for (; e < end; e += 64) { const double v = vals[e]; a0 = fma(v, v, a0); }
+  const double s = sls::norms_l1_report(wave_sum((a0 + a1) + (a2 + a3)));
+  if (lane != 0) return;
+  p.res[line] = s;
+  double* out = col ? p.col_out : p.row_out;
+  if (out) out[i] = s;
+}
+
+// totals[0] = Σ_i row_h2[i] — thread k adds the rows k, k + 256, … in turn, then the butterfly, then the four waves as
+// (w0 + w1) + (w2 + w3) — and totals[1] = max_i row_h2 (the entries are ≥ 0 or +inf, never NaN)
+__global__ void __launch_bounds__(kBlock) norms_h2_totals_kernel(const double* __restrict__ res, int N, double* res_totals, double* out) {
+  __shared__ double lds[2 * kWavesPerBlock];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < N; i += kBlock) s += res[i];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) lds[kWavesPerBlock + (threadIdx.x >> 6)] = s;
+  const double m = block_max(res, N, lds);                      // its barriers publish the sums as well
+  if (threadIdx.x != 0) return;
+  const double t = (lds[4] + lds[5]) + (lds[6] + lds[7]);
+  res_totals[0] = t; res_totals[1] = m;
+  if (out) { out[0] = t; out[1] = m; }
+}
+
+struct CovParams {
+  const int32_t* row_ptr; const int32_t* row_key; const double* vals;   // the row table, values in row order
+  const int32_t* pair;         // [npairs][2]: (i, j), 0-based
+  int npairs;
+  double* res;                 // [npairs], owned by the pattern
+  double* out;                 // the caller's, or NULL
+};
+
+// first index of key[lo, lo + n) whose key is ≥ k, lo + n when there is none.  The trip count depends on n alone: lanes that
+// search the same window for different keys stay together.  Reads inside [lo, lo + n) only.
+__device__ __forceinline__ int cov_lower_bound(const int32_t* __restrict__ key, int lo, int n, int32_t k) {
+  while (n > 1) {
+    const int half = n >> 1;
+    lo = key[lo + half - 1] < k ? lo + half : lo;
+    n -= half;
+  }
+  return (n == 1 && key[lo] < k) ? lo + 1 : lo;
+}
+
+// One wave per pair: cov = Σ over the keys rows i and j share of v_i·v_j.  a = the shorter list (norms_cov_swap), walked in
+// chunks of 64, one entry per lane; the chunk's first and last key (read by every lane from the same address — a partly filled
+// chunk has no lane 63 to broadcast from) cut b down to the window [lo, hi) that can hold a partner, and lo only moves up
+// from chunk to chunk.  A lane looks its key up in the window and adds fma(va, vb, acc) on a hit: per lane the chunks
+// ascend, then the xor butterfly — an order that depends on the two rows alone, not on the pair's place in the list or on the
+// grid (the pairs of a wave are q, q + waves of the grid, …).  No LDS, no atomics; every cross-lane operation sits in
+// wave-uniform control flow.
+__global__ void __launch_bounds__(kBlock) norms_cov_kernel(CovParams p) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int32_t* __restrict__ key = p.row_key;
+  const double* __restrict__ vals = p.vals;
+  for (long long q = (long long)blockIdx.x * kWavesPerBlock + wave; q < p.npairs; q += (long long)gridDim.x * kWavesPerBlock) {
+    const int i = __builtin_amdgcn_readfirstlane(p.pair[2 * q]), j = __builtin_amdgcn_readfirstlane(p.pair[2 * q + 1]);
+    const int ib = p.row_ptr[i], ie = p.row_ptr[i + 1], jb = p.row_ptr[j], je = p.row_ptr[j + 1];
+    const bool swap = sls::norms_cov_swap(i, ie - ib, j, je - jb);
+    const int a_end = swap ? je : ie, b_end = swap ? ie : je;
+    int lo = swap ? ib : jb;                                      // b below lo lies below every key of the chunks still to come
+    double acc = 0.0;
+    for (int c = swap ? jb : ib; c < a_end && lo < b_end; c += 64) {
+      const int32_t k_first = key[c], k_last = key[min(c + 63, a_end - 1)];
+      lo = cov_lower_bound(key, lo, b_end - lo, k_first);
+      int hi = cov_lower_bound(key, lo, b_end - lo, k_last);
+      if (hi < b_end && key[hi] == k_last) ++hi;                  // keys ascend strictly: at most one equal
+      const int e = c + lane;
+      if (e < a_end && lo < hi) {
+        const int32_t k = key[e];
+        const int at = cov_lower_bound(key, lo, hi - lo, k);
+        if (at < hi && key[at] == k) acc = fma(vals[e], vals[at], acc);
+      }
+      lo = hi;
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) {
+      p.res[q] = acc;
+      if (p.out) p.out[q] = acc;
+    }
+  }
 }
 
 // v[j][f] = norms_v0(j) and its square for the norm kernel
@@ -263,8 +366,14 @@ struct sls_norms {
   double* d_vals = nullptr;            // [2·n]
   double2 *d_v = nullptr, *d_y = nullptr, *d_tw = nullptr;   // [Nx][max_freq], [N][max_freq], [T][max_freq]
   double *d_part = nullptr, *d_scale = nullptr;             // [N][max_freq], [max_freq]
-  double* d_res = nullptr;             // row_l1 [N], col_l1 [Nx], totals [2], sigma [max_freq], peak [2]
+  double* d_res = nullptr;             // row_l1 [N], col_l1 [Nx], totals [2], sigma [max_freq], peak [2]; h2 takes the l1 slots
   bool loaded = false;
+  // the covariance pattern (sls_norms_cov_pattern): its own allocation, absent until the first pattern is set
+  int64_t index_base = 0, npairs = 0;
+  void* cov_arena = nullptr;           // pairs [npairs][2] int32, then the result buffer [npairs]
+  size_t cov_bytes = 0;
+  const int32_t* d_pair = nullptr;
+  double* d_cov = nullptr;
 };
 
 using namespace sls;
@@ -278,6 +387,35 @@ int enqueue_l1(sls_norms* L, hipStream_t st, double* d_row, double* d_col, doubl
   HIPCHK(L->ctx, hipGetLastError());
   hipLaunchKernelGGL(norms_l1_totals_kernel, dim3(1), dim3(kBlock), 0, st, L->d_res, N, Nx, L->d_res + N + Nx, d_totals);
   HIPCHK(L->ctx, hipGetLastError());
+  return 0;
+}
+
+int enqueue_h2(sls_norms* L, hipStream_t st, double* d_row, double* d_col, double* d_totals) {
+  const int N = (int)(L->Nx + L->Nu), Nx = (int)L->Nx;
+  L1Params p{L->d_row_ptr, L->d_col_ptr, L->d_vals, (long long)L->n_entries, N, Nx, L->d_res, d_row, d_col};
+  hipLaunchKernelGGL(norms_h2_kernel, dim3((N + Nx + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, st, p);
+  HIPCHK(L->ctx, hipGetLastError());
+  hipLaunchKernelGGL(norms_h2_totals_kernel, dim3(1), dim3(kBlock), 0, st, L->d_res, N, L->d_res + N + Nx, d_totals);
+  HIPCHK(L->ctx, hipGetLastError());
+  return 0;
+}
+
+// one wave per pair up to kCovMaxBlocks blocks; past that a wave takes several pairs (a launch stays below 2³² threads)
+constexpr long long kCovMaxBlocks = 1LL << 22;
+
+int enqueue_cov(sls_norms* L, hipStream_t st, double* d_out) {
+  const long long blocks = std::min<long long>((L->npairs + kWavesPerBlock - 1) / kWavesPerBlock, kCovMaxBlocks);
+  CovParams p{L->d_row_ptr, L->d_row_key, L->d_vals, L->d_pair, (int)L->npairs, L->d_cov, d_out};
+  hipLaunchKernelGGL(norms_cov_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, p);
+  HIPCHK(L->ctx, hipGetLastError());
+  return 0;
+}
+
+// what every covariance pass needs: a Φ and a pattern
+int cov_ready(sls_norms* L, const char* who) {
+  if (!L) return fail(nullptr, SLS_EINVAL, std::string(who) + ": null object");
+  if (!L->loaded) return fail(L->ctx, SLS_EINVAL, std::string(who) + ": no Φ loaded (sls_norms_load first)");
+  if (L->npairs == 0) return fail(L->ctx, SLS_EINVAL, std::string(who) + ": no pattern set (sls_norms_cov_pattern first)");
   return 0;
 }
 
@@ -333,15 +471,18 @@ int enqueue_hinf(sls_norms* L, hipStream_t st, const double* omega, int64_t nfre
   return 0;
 }
 
-// the plan-owned result buffer [off, off + n) to the host, after waiting for `st`
-int fetch(sls_norms* L, hipStream_t st, size_t off, size_t n, double* stage_out) {
+// n doubles of an object-owned device buffer to the host, after waiting for `st`
+int fetch_from(sls_norms* L, hipStream_t st, const double* d_src, size_t n, double* stage_out) {
   const size_t bytes = n * sizeof(double);
   double* pin = reinterpret_cast<double*>(slot_pinned(L->ctx, L->slot, bytes));
-  HIPCHK(L->ctx, hipMemcpyAsync(pin ? pin : stage_out, L->d_res + off, bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(L->ctx, hipMemcpyAsync(pin ? pin : stage_out, d_src, bytes, hipMemcpyDeviceToHost, st));
   HIPCHK(L->ctx, hipStreamSynchronize(st));
   if (pin) std::memcpy(stage_out, pin, bytes);
   return 0;
 }
+
+// the plan-owned result buffer [off, off + n) to the host, after waiting for `st`
+int fetch(sls_norms* L, hipStream_t st, size_t off, size_t n, double* stage_out) { return fetch_from(L, st, L->d_res + off, n, stage_out); }
 
 }  // namespace
 
@@ -367,7 +508,7 @@ int sls_norms_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_c
   sls_norms* L = new (std::nothrow) sls_norms();
   if (!L) return fail(ctx, SLS_ENOMEM, "sls_norms_plan: out of memory");
   L->ctx = ctx; L->dev = ctx->devs[dev_slot]; L->slot = dev_slot;
-  L->n_entries = n; L->max_freq = max_freq; L->Nx = Nx; L->Nu = Op.Nu; L->T = T;
+  L->n_entries = n; L->max_freq = max_freq; L->Nx = Nx; L->Nu = Op.Nu; L->T = T; L->index_base = dims->index_base;
   hipError_t e = hipSetDevice(L->dev);
   if (e != hipSuccess) { delete L; return hipfail(ctx, e, "hipSetDevice"); }
   auto al = [](size_t b_) { return (std::max<size_t>(b_, 16) + 255) / 256 * 256; };
@@ -452,10 +593,76 @@ int sls_norms_fetch_hinf(sls_norms* L, void* hip_stream, const double* omega, in
   return 0;
 }
 
+int sls_norms_h2(sls_norms* L, void* hip_stream, double* d_row_h2, double* d_col_h2, double* d_totals) {
+  if (!L) return fail(nullptr, SLS_EINVAL, "sls_norms_h2: null object");
+  if (!L->loaded) return fail(L->ctx, SLS_EINVAL, "sls_norms_h2: no Φ loaded (sls_norms_load first)");
+  HIPCHK(L->ctx, hipSetDevice(L->dev));
+  return enqueue_h2(L, static_cast<hipStream_t>(hip_stream), d_row_h2, d_col_h2, d_totals);
+}
+
+int sls_norms_fetch_h2(sls_norms* L, void* hip_stream, double* row_h2, double* col_h2, double* totals) {
+  if (int rc = sls_norms_h2(L, hip_stream, nullptr, nullptr, nullptr)) return rc;
+  const size_t N = (size_t)(L->Nx + L->Nu), Nx = (size_t)L->Nx;
+  std::vector<double> h(N + Nx + 2);
+  if (int rc = fetch(L, static_cast<hipStream_t>(hip_stream), 0, h.size(), h.data())) return rc;
+  if (row_h2) std::memcpy(row_h2, h.data(), N * sizeof(double));
+  if (col_h2) std::memcpy(col_h2, h.data() + N, Nx * sizeof(double));
+  if (totals) std::memcpy(totals, h.data() + N + Nx, 2 * sizeof(double));
+  return 0;
+}
+
+int sls_norms_cov_pattern(sls_norms* L, int64_t npairs, const int64_t* pair_i, const int64_t* pair_j) {
+  if (!L) return fail(nullptr, SLS_EINVAL, "sls_norms_cov_pattern: null object");
+  if (npairs > 0x7fffffffLL) return fail(L->ctx, SLS_EUNSUPPORTED, "sls_norms_cov_pattern: npairs exceeds int32");
+  std::string msg;
+  if (int rc = norms_cov_check(L->Nx + L->Nu, L->index_base, npairs, pair_i, pair_j, msg)) return fail(L->ctx, rc, "sls_norms_cov_pattern: " + msg);
+  HIPCHK(L->ctx, hipSetDevice(L->dev));
+  void* arena = nullptr;
+  size_t bytes = 0, b_pair = 0;
+  if (npairs > 0) {
+    std::vector<int32_t> pr;
+    try { pr.resize(2 * (size_t)npairs); } catch (const std::bad_alloc&) { return fail(L->ctx, SLS_ENOMEM, "sls_norms_cov_pattern: out of memory"); }
+    for (int64_t p = 0; p < npairs; ++p) {
+      pr[2 * (size_t)p] = (int32_t)(pair_i[p] - L->index_base);
+      pr[2 * (size_t)p + 1] = (int32_t)(pair_j[p] - L->index_base);
+    }
+    b_pair = ((size_t)npairs * 8 + 255) / 256 * 256;
+    bytes = b_pair + ((size_t)npairs * 8 + 255) / 256 * 256;
+    hipError_t e = hipMalloc(&arena, bytes);
+    if (e != hipSuccess) return hipfail(L->ctx, e, "hipMalloc (covariance pattern)");
+    e = hipMemcpy(arena, pr.data(), (size_t)npairs * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(static_cast<unsigned char*>(arena) + b_pair, 0, bytes - b_pair);
+    if (e != hipSuccess) { (void)hipFree(arena); return hipfail(L->ctx, e, "sls_norms_cov_pattern: upload"); }
+  }
+  const hipError_t idle = hipDeviceSynchronize();                 // the new list is up, and no pass reads the old buffers any more
+  if (idle != hipSuccess) { if (arena) (void)hipFree(arena); return hipfail(L->ctx, idle, "sls_norms_cov_pattern: hipDeviceSynchronize"); }
+  if (L->cov_arena) (void)hipFree(L->cov_arena);
+  L->cov_arena = arena; L->cov_bytes = bytes; L->npairs = npairs;
+  L->d_pair = static_cast<const int32_t*>(arena);
+  L->d_cov = arena ? reinterpret_cast<double*>(static_cast<unsigned char*>(arena) + b_pair) : nullptr;
+  return 0;
+}
+
+int sls_norms_cov(sls_norms* L, void* hip_stream, double* d_cov) {
+  if (int rc = cov_ready(L, "sls_norms_cov")) return rc;
+  if (!d_cov) return fail(L->ctx, SLS_EINVAL, "sls_norms_cov: null output");
+  HIPCHK(L->ctx, hipSetDevice(L->dev));
+  return enqueue_cov(L, static_cast<hipStream_t>(hip_stream), d_cov);
+}
+
+int sls_norms_fetch_cov(sls_norms* L, void* hip_stream, double* cov) {
+  if (int rc = cov_ready(L, "sls_norms_fetch_cov")) return rc;
+  HIPCHK(L->ctx, hipSetDevice(L->dev));
+  if (int rc = enqueue_cov(L, static_cast<hipStream_t>(hip_stream), nullptr)) return rc;
+  if (cov) return fetch_from(L, static_cast<hipStream_t>(hip_stream), L->d_cov, (size_t)L->npairs, cov);
+  HIPCHK(L->ctx, hipStreamSynchronize(static_cast<hipStream_t>(hip_stream)));
+  return 0;
+}
+
 int sls_norms_info(const sls_norms* L, int64_t* n_entries, int64_t* device_bytes, int64_t* max_freq) {
   if (!L) return fail(nullptr, SLS_EINVAL, "sls_norms_info: null object");
   if (n_entries) *n_entries = L->n_entries;
-  if (device_bytes) *device_bytes = (int64_t)L->arena_bytes;
+  if (device_bytes) *device_bytes = (int64_t)(L->arena_bytes + L->cov_bytes);
   if (max_freq) *max_freq = L->max_freq;
   return 0;
 }
@@ -464,6 +671,7 @@ void sls_norms_destroy(sls_norms* L) {
   if (!L) return;
   (void)hipSetDevice(L->dev);
   if (L->arena) (void)hipFree(L->arena);
+  if (L->cov_arena) (void)hipFree(L->cov_arena);
   delete L;
 }
 

@@ -6,7 +6,9 @@ Rows are the Nx state rows followed by the Nu input rows, N = Nx + Nu; for t = 0
 
 `l1()` gives the row and column absolute sums of G and their maxima — the 𝓛₁ norm (induced ℓ∞ → ℓ∞) and the 𝓔₁ norm; `hinf()`
 gives, per frequency of the caller's grid, a power-iteration lower bound of σ_max(G(ω)) and the peak over the grid.  The peak is
-a lower bound of the 𝓗∞ norm ON THAT GRID: refining the grid is the caller's business.  The passes run in libsls_mi355x.so
+a lower bound of the 𝓗∞ norm ON THAT GRID: refining the grid is the caller's business.  `h2()` splits the squared 𝓗₂ norm by
+output row — the variance of every state and actuator under unit white w — and by disturbance column; `covariance()` gives
+chosen entries of Σ = Σ_t G[t]·G[t]ᵀ, the steady-state covariance of z (exact for the FIR loop).  The passes run in libsls_mi355x.so
 (sls_norms_*: HIP kernels); this module only marshals.  No CPU fallback: `norms_host` / `norms_tables` are the diagnostic host
 twin the tests compare against, not a second backend.
 """
@@ -57,6 +59,18 @@ def plant_weights(P):
     return cz, _diagonal(P.B1, "B1")
 
 
+def covariance_pattern_of(P, index_base=0):
+    """(pairs_i, pairs_j), int64: the "neighbour" pattern of a plant — the upper triangle (i ≤ j) of (A ≠ 0) ∪ I on the state
+    rows, an entry of A below the diagonal counted at its mirror place, plus the diagonal of the input rows Nx … Nx+Nu−1.
+    Sorted by (i, j), no duplicates."""
+    A = sp.coo_matrix(P.A)
+    nz = A.data != 0
+    i, j = np.minimum(A.row[nz], A.col[nz]).astype(np.int64), np.maximum(A.row[nz], A.col[nz]).astype(np.int64)
+    d = np.arange(P.Nx + P.Nu, dtype=np.int64)
+    flat = np.unique(np.concatenate([i * (P.Nx + P.Nu) + j, d * (P.Nx + P.Nu) + d]))
+    return flat // (P.Nx + P.Nu) + index_base, flat % (P.Nx + P.Nu) + index_base
+
+
 class ClosedLoopNorms:
     """Row- and column-ordered tables of G built from the masks alone (sls_norms_plan) on one device of `ctx`, with the work
     vectors of `max_freq` frequencies.  P_or_dims: a Plant (only Nx, Nu are read) or (Nx, Nu); cz [Nx+Nu], b [Nx]: host weight
@@ -78,6 +92,9 @@ class ClosedLoopNorms:
         _capi.check(self._lib.sls_norms_plan(ctx.handle, dev_slot, C.byref(self.m.dims), self.m.Sx, self.m.Su, pcz, pb, int(max_freq),
                                              C.byref(h)), ctx.handle)
         self.handle = h
+        self.index_base, self.npairs = int(index_base), 0
+
+    covariance_pattern_of = staticmethod(covariance_pattern_of)
 
     @classmethod
     def from_plant(cls, P, Sx, Su, **kw):
@@ -129,6 +146,42 @@ class ClosedLoopNorms:
         _capi.check(self._lib.sls_norms_hinf(self.handle, stream, om.ctypes.data_as(_DP), om.size, int(iters),
                                              _ptr(sigma, om.size, "sigma"), _ptr(peak, 2, "peak")), self.ctx.handle)
 
+    def h2(self, stream=None):
+        """(row_h2 [N], col_h2 [Nx], totals [2]) on the host: row_h2[i] = Σ_t Σ_j G[t][i,j]², the variance of z_i under unit white
+        w (its square root is the RMS of that state or actuator); col_h2[j] the share of disturbance j; totals[0] = Σ row_h2,
+        the squared 𝓗₂ norm, totals[1] = max row_h2.  Waits."""
+        row, col, tot = np.zeros(self.N), np.zeros(self.Nx), np.zeros(2)
+        _capi.check(self._lib.sls_norms_fetch_h2(self.handle, stream, row.ctypes.data_as(_DP), col.ctypes.data_as(_DP),
+                                                 tot.ctypes.data_as(_DP)), self.ctx.handle)
+        return row, col, tot
+
+    def h2_async(self, row_h2=None, col_h2=None, totals=None, stream=None):
+        """the same pass into device tensors / pointers (each may be None); nothing waits"""
+        _capi.check(self._lib.sls_norms_h2(self.handle, stream, _ptr(row_h2, self.N, "row_h2"), _ptr(col_h2, self.Nx, "col_h2"),
+                                           _ptr(totals, 2, "totals")), self.ctx.handle)
+
+    def set_covariance_pattern(self, pairs_i, pairs_j):
+        """The entries (pairs_i[p], pairs_j[p]) of Σ = Σ_t G[t]·G[t]ᵀ that `covariance` evaluates, in the index base of the
+        object: any order, duplicates and i == j allowed.  Uploads the list and allocates it and a result buffer; a second call
+        replaces the first, empty lists clear the pattern.  Waits.  Returns self."""
+        pi, pj = (np.ascontiguousarray(np.atleast_1d(a), dtype=np.int64) for a in (pairs_i, pairs_j))
+        if pi.ndim != 1 or pi.shape != pj.shape:
+            raise ValueError(f"pairs_i and pairs_j must be two lists of one length, got shapes {pi.shape} and {pj.shape}")
+        ip = C.POINTER(C.c_int64)
+        _capi.check(self._lib.sls_norms_cov_pattern(self.handle, pi.size, pi.ctypes.data_as(ip), pj.ctypes.data_as(ip)), self.ctx.handle)
+        self.npairs = int(pi.size)
+        return self
+
+    def covariance(self, stream=None):
+        """cov [npairs] on the host: cov[p] = Σ_t Σ_k G[t][i_p,k]·G[t][j_p,k] for the pairs of `set_covariance_pattern`.  Waits."""
+        cov = np.zeros(max(self.npairs, 1))
+        _capi.check(self._lib.sls_norms_fetch_cov(self.handle, stream, cov.ctypes.data_as(_DP)), self.ctx.handle)
+        return cov[: self.npairs]
+
+    def covariance_async(self, out, stream=None):
+        """the same pass into a device tensor / pointer of npairs doubles; nothing waits"""
+        _capi.check(self._lib.sls_norms_cov(self.handle, stream, _ptr(out, self.npairs, "out")), self.ctx.handle)
+
     def close(self):
         if getattr(self, "handle", None):
             self._lib.sls_norms_destroy(self.handle)
@@ -178,3 +231,33 @@ def norms_host(P_or_dims, S, values, cz=None, b=None, omega=None, iters=32, inde
     if nf:
         out.update(sigma=sigma[:nf], peak=float(peak[0]), argpeak=int(peak[1]))
     return out
+
+
+def norms_h2_host(P_or_dims, S, values, cz=None, b=None, index_base=0):
+    """sls_debug_norms_h2_host (needs no device): the host twin of `h2`.  Returns (row_h2 [N], col_h2 [Nx], totals [2])."""
+    Nx, Nu = _dims_of(P_or_dims)
+    m = _capi.Marshalled.masks_only(Nx, Nu, S[0], S[1], index_base)
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    _, pcz = _vec(cz, Nx + Nu, "cz")
+    _, pb = _vec(b, Nx, "b")
+    row, col, tot = np.zeros(Nx + Nu), np.zeros(Nx), np.zeros(2)
+    _capi.check(_capi.load_library().sls_debug_norms_h2_host(C.byref(m.dims), m.Sx, m.Su, values.ctypes.data_as(_DP), pcz, pb,
+                                                             row.ctypes.data_as(_DP), col.ctypes.data_as(_DP), tot.ctypes.data_as(_DP)))
+    return row, col, tot
+
+
+def norms_cov_host(P_or_dims, S, values, pairs_i, pairs_j, cz=None, b=None, index_base=0):
+    """sls_debug_norms_cov_host (needs no device): the host twin of `set_covariance_pattern` + `covariance`.  Returns cov [npairs]."""
+    Nx, Nu = _dims_of(P_or_dims)
+    m = _capi.Marshalled.masks_only(Nx, Nu, S[0], S[1], index_base)
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    _, pcz = _vec(cz, Nx + Nu, "cz")
+    _, pb = _vec(b, Nx, "b")
+    pi, pj = (np.ascontiguousarray(np.atleast_1d(a), dtype=np.int64) for a in (pairs_i, pairs_j))
+    if pi.ndim != 1 or pi.shape != pj.shape:
+        raise ValueError(f"pairs_i and pairs_j must be two lists of one length, got shapes {pi.shape} and {pj.shape}")
+    cov = np.zeros(max(pi.size, 1))
+    ip = C.POINTER(C.c_int64)
+    _capi.check(_capi.load_library().sls_debug_norms_cov_host(C.byref(m.dims), m.Sx, m.Su, values.ctypes.data_as(_DP), pcz, pb, pi.size,
+                                                              pi.ctypes.data_as(ip), pj.ctypes.data_as(ip), cov.ctypes.data_as(_DP)))
+    return cov[: pi.size]
