@@ -71,6 +71,12 @@ extern "C" {
                                     reference (it has no 𝓗∞ synthesis; BASELINE configs[3] names one).  Needs a diagonal
                                     [C1 D12]ᵀ[C1 D12] and D11 = 0, else SLS_EUNSUPPORTED.  ADMM whose projection step is the 𝓗₂ machinery (one-wave
                                     kernel for ñx ≤ 32, tile kernel beyond); status SLS_COL_NOTCONV when the step cap is hit. */
+#define SLS_PLAN_WEIGHTS_UPDATABLE 2u /* sls_h2_sf_plan / sls_h2_sf_plan_localized: the plan can take new LQR weights later
+                                    (sls_plan_update_weights below, which states the shape the plant must have; SLS_EUNSUPPORTED
+                                    otherwise).  Every column with B1[c,c] ≠ 0 then gets a weight record, uniform weights
+                                    included; without the flag a plan is built exactly as before.  The one-shot and batch calls
+                                    (sls_h2_sf_solve, _solve_batch, _solve_localized) ACCEPT the flag and apply the same shape
+                                    rule and the same records — they keep no plan, so there is nothing to update afterwards. */
 
 /* Julia SparseMatrixCSC{Float64,Int}  (reference src/types/GeneralizedPlant.jl:47-52) */
 typedef struct sls_csc_f64 {
@@ -305,6 +311,35 @@ int  sls_plan_update_result(sls_plan* plan, int64_t* n_rejected);
  * pass it to sls_plan_refine — reads it here instead of keeping its own copies.  Like every call on a context, the update
  * entry points are for one thread at a time per context (they share the context's pinned staging buffer).                    */
 int  sls_plan_fetch_plant(sls_plan* plan, double* A_nzval, double* B2_nzval);
+/* ---- new LQR weights for a live plan (no rebuild) ----------------------------------------------------------------------------
+ * For a plan built with SLS_PLAN_WEIGHTS_UPDATABLE in sls_dims.flags.  The flag requires the LQR shape: C1 and D12 are each NULL
+ * (identity) or hold exactly one stored entry per column on that column's own z-row — C1 = [diag(q); 0], D12 = [0; diag(r)];
+ * D11 is NULL or has no non-zero on a z-row a column selects (sls_h2_sf_plan_localized: no non-zero at all); no coupled column
+ * group (non-diagonal B1[c_j, c_j]); either objective.  SLS_EUNSUPPORTED with the reason otherwise.  Masks, index sets,
+ * destinations, launch list and workspaces do not depend on a weight value; what does is the per-column record
+ * 1 / (B1[c,c]²·v² + ridge) and the four-wave kernel's plan-time tables, and sls_plan_update_weights rewrites those on
+ * `hip_stream`; the next sls_plan_execute solves the re-weighted problem, sls_plan_objective values it.
+ *   c1_diag [Nx]: c1_diag[i] is the stored value C1[i, i]; d12_diag [Nu]: d12_diag[j] is D12[Nx + j, j].  NULL: that half keeps its
+ *     values; both NULL is SLS_EINVAL, and so is a plan built without the flag.
+ *   on_device, ordering, staging and the one-thread-per-context rule: as sls_plan_update_plant.  Nothing is allocated and the
+ *     device is never waited for.
+ * The value rule: a value is accepted when it is finite and B1[c,c]²·v² + ridge > 0 in every column that holds the variable
+ * (the plan-time rule: a singular Hessian is refused; the sign of v does not matter, 0.0 needs a positive ridge).
+ *   host path:   checked before anything is enqueued — SLS_EINVAL, the message names the matrix and the position, the plan is
+ *                untouched.
+ *   device path: the kernel skips an offending value — every record keeps its old value for that variable — and counts it.
+ *                sls_plan_update_weights_result waits for the plan's last update and returns the count of the last weights
+ *                update (0 = applied in full).
+ * A value whose variable lies in no solved column's index sets is only kept (sls_plan_fetch_weights returns it).
+ * Equivalence: the records are rewritten to the bits a plan built from the re-weighted plant with the flag holds, so the next
+ * execute gives that plan's Φ.  An attached refinement is detached and freed as by sls_plan_update_plant; with
+ * sls_plan_track_changes on, the subproblems in which at least one record value changed bits are marked dirty.  B1, the ridge
+ * term, D11 and the shape stay plan constants.
+ * sls_plan_fetch_weights: the diagonals the plan holds now (HOST outputs, either may be NULL): the plan-time values, then what the
+ * updates left, refused values of the device path at their old values.  Waits like sls_plan_fetch_plant.                      */
+int  sls_plan_update_weights(sls_plan* plan, void* hip_stream, const double* c1_diag, const double* d12_diag, int on_device);
+int  sls_plan_update_weights_result(sls_plan* plan, int64_t* n_rejected);
+int  sls_plan_fetch_weights(sls_plan* plan, double* c1_diag, double* d12_diag);
 /* ---- re-solve only some columns of a resident plan ---------------------------------------------------------------------------
  * Subproblem q reads the plant only through A[s_x(q), s_x(q)] and B2[s_x(q), s_u(q)], so a change of A[i,j] can move it only if
  * i and j lie in s_x(q), and a change of B2[i,k] only if i lies in s_x(q) and k in s_u(q); every other column would be solved

@@ -119,6 +119,26 @@ int sls_debug_affected_host(const sls_dims* dims, const sls_plant* P, const sls_
                             const int64_t* group_ptr, const int64_t* group_cols, const uint8_t* changed_A, const uint8_t* changed_B2,
                             uint8_t* dirty);
 
+/* The shape rule of SLS_PLAN_WEIGHTS_UPDATABLE that needs no index set (csrc/sls_weights.h: weights_shape_check): 0 and the
+ * Nx + Nu diagonal values (C1's, then D12's; nullable) when C1 and D12 are each NULL or hold one stored entry per column on the
+ * column's own z-row, SLS_EUNSUPPORTED with the reason otherwise.  dims and P are validated first.  Needs no device. */
+int sls_debug_weights_shape_check(const sls_dims* dims, const sls_plant* P, double* diag);
+
+/* The weight records of the host symbolic pass over all groups, and the host twin of sls_plan_update_weights
+ * (csrc/sls_weights.cpp: weight_records_host).  dims->flags decides whether the pass is an updatable one
+ * (SLS_PLAN_WEIGHTS_UPDATABLE); ridge_x / ridge_u: the weights of sls_set_ridge (NULL = none).  With c1_diag [Nx] and / or
+ * d12_diag [Nu] given (updatable pass only, SLS_EINVAL otherwise) the update is then applied to the pass's records: strict = 1 as
+ * the host path does (every value checked first; SLS_EINVAL and nothing written on a refusal), strict = 0 as the device kernel does
+ * (refused values skipped and counted in *n_rejected).  Outputs, each nullable, [n_subproblems] in col_status order unless
+ * noted: *n_w (doubles in the weight pool), has_w, off_w, n_x / n_u (ñx, ñu), w_pool [*n_w], obj_pool [2·n_subproblems],
+ * b2 (B1[c,c]² of an updatable pass, else zeros), diag [Nx + Nu] (the diagonals after the update; updatable pass only),
+ * dirty (1 where the update changed the bits of a record value).  Call with w_pool = NULL first for *n_w.  Needs no device. */
+int sls_debug_weights_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su, int64_t ngroups,
+                           const int64_t* group_ptr, const int64_t* group_cols, const double* ridge_x, const double* ridge_u,
+                           const double* c1_diag, const double* d12_diag, int strict, int64_t* n_w, int32_t* has_w, int64_t* off_w,
+                           int32_t* n_x, int32_t* n_u, double* w_pool, double* obj_pool, double* b2, double* diag, uint8_t* dirty,
+                           int64_t* n_rejected);
+
 /* The tables of the stand-alone controller (sls_controller_plan) from the masks (dims: Nx, Nu, T, index_base are read), built
  * on the host by the routine the plan uses (csrc/sls_symbolic.cpp: build_controller_operator).  *n_entries: stored-true entries of
  * Sx[1..T−1] and Su[0..T−1]; row_ptr[Nx + Nu + 1]: the Nx β rows, then the Nu u rows; per entry, ascending in (lag, col) inside a

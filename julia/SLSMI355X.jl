@@ -11,7 +11,7 @@
 module SLSMI355X
 
 using SparseArrays
-export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!, Norms, l1, hinf, h2, covariance_pattern!, covariance
+export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, update_weights!, weights, SLS_PLAN_WEIGHTS_UPDATABLE, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!, Norms, l1, hinf, h2, covariance_pattern!, covariance
 
 const LIB = get(ENV, "SLS_MI355X_LIB", "libsls_mi355x.so")
 
@@ -114,6 +114,55 @@ function update_plant!(plan::Ptr{Cvoid}, A, B2; stream::Ptr{Cvoid}=C_NULL, wait:
     rc = ccall((:sls_plan_update_result, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), plan, n)
     rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
     return n[]
+end
+
+"`sls_dims.flags` bit: build the plan so that `update_weights!` can give it new LQR weights (or it with the objective's flag)."
+const SLS_PLAN_WEIGHTS_UPDATABLE = UInt32(2)
+
+"""
+    n_rejected = update_weights!(plan, c1, d12; Nx, Nu, stream=C_NULL, wait=true)
+
+`sls_plan_update_weights` on a resident plan built with `SLS_PLAN_WEIGHTS_UPDATABLE` in `dims.flags` (a `Ptr{Cvoid}` from
+`sls_h2_sf_plan`): new diagonals of `C1 = [diag(c1); 0]` and / or `D12 = [0; diag(d12)]` — a `Vector{Float64}` of the `Nx` / `Nu`
+diagonal values, a `SparseMatrixCSC{Float64}` of that LQR shape (one stored entry per column, checked here; its `nzval` is the
+diagonal) or `nothing` = unchanged — host path; the next `sls_plan_execute` solves the re-weighted problem without a rebuild.  A
+raw plan pointer carries no sizes: pass the plant's `Nx` and `Nu`, the lengths are checked against them.  Every value must be
+finite and keep the Hessian positive (0.0 needs a ridge term), else the call errors (`SLS_EINVAL`) and the plan is untouched.  An
+attached refinement is dropped.  With `wait = true` returns `sls_plan_update_weights_result` (0 after a host-path update).
+"""
+function update_weights!(plan::Ptr{Cvoid}, c1, d12; Nx::Integer, Nu::Integer, stream::Ptr{Cvoid}=C_NULL, wait::Bool=true)
+    function dg(M::SparseMatrixCSC, n, shift, name)
+        (size(M) == (Nx + Nu, n) && nnz(M) == n && M.colptr == collect(1:n+1) && rowvals(M) == collect(1:n) .+ shift) ||
+            error("update_weights!: $name must be $(Nx + Nu)×$n with one stored entry per column, column j on row $shift + j")
+        return convert(Vector{Float64}, nonzeros(M))
+    end
+    dg(v::AbstractVector, n, shift, name) = length(v) == n ? convert(Vector{Float64}, v) :
+        error("update_weights!: $name needs the $n diagonal values, got $(length(v))")
+    dg(::Nothing, n, shift, name) = nothing
+    c, d = dg(c1, Nx, 0, "C1"), dg(d12, Nu, Nx, "D12")
+    (c === nothing && d === nothing) && error("update_weights!: give c1, d12 or both")
+    GC.@preserve c d begin
+        rc = ccall((:sls_plan_update_weights, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint), plan, stream,
+                   c === nothing ? Ptr{Float64}(C_NULL) : pointer(c), d === nothing ? Ptr{Float64}(C_NULL) : pointer(d), 0)
+    end
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    wait || return 0
+    n = Ref{Int64}(0)
+    rc = ccall((:sls_plan_update_weights_result, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), plan, n)
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    return n[]
+end
+
+"""
+    c1, d12 = weights(plan; Nx, Nu)
+
+`sls_plan_fetch_weights`: the diagonals of `C1` and `D12` the plan holds on the device now (waits for the plan's last update).
+"""
+function weights(plan::Ptr{Cvoid}; Nx::Integer, Nu::Integer)
+    c, d = zeros(Float64, max(Nx, 1)), zeros(Float64, max(Nu, 1))
+    rc = ccall((:sls_plan_fetch_weights, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), plan, c, d)
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    return c[1:Nx], d[1:Nu]
 end
 
 """

@@ -23,6 +23,7 @@ LIB_PATH = os.path.join(_HERE, "libsls_mi355x.so")
 SLS_ABI_VERSION = 2
 SLS_EINVAL, SLS_ENOTSF, SLS_EUNSUPPORTED, SLS_EHIP, SLS_ENOMEM, SLS_ENODEVICE = -1, -2, -3, -4, -5, -6
 SLS_SOLVE_DEFAULT, SLS_SOLVE_SUM_OF_NORMS = 0, 1
+SLS_PLAN_WEIGHTS_UPDATABLE = 2
 SLS_COL_OK, SLS_COL_INFEASIBLE, SLS_COL_NOTCONV, SLS_COL_TRIVIAL, SLS_COL_SKIPPED, SLS_COL_UNSUPPORTED = 0, 1, 2, 3, 4, 5
 
 ERROR_NAMES = {SLS_EINVAL: "SLS_EINVAL", SLS_ENOTSF: "SLS_ENOTSF", SLS_EUNSUPPORTED: "SLS_EUNSUPPORTED",
@@ -88,6 +89,7 @@ EXPORTS = [
     "sls_closed_loop_entries", "sls_closed_loop_destroy",
     "sls_plan_objective", "sls_plan_fetch_objective", "sls_ctx_want_objective", "sls_ctx_last_objective",
     "sls_plan_update_plant", "sls_plan_update_result", "sls_plan_fetch_plant",
+    "sls_plan_update_weights", "sls_plan_update_weights_result", "sls_plan_fetch_weights",
     "sls_plan_execute_columns", "sls_plan_track_changes", "sls_plan_execute_dirty", "sls_plan_fetch_dirty", "sls_plan_clear_dirty",
     "sls_plan_residual", "sls_plan_fetch_residual",
     "sls_controller_plan", "sls_controller_load", "sls_controller_reset", "sls_controller_step", "sls_controller_info",
@@ -189,6 +191,9 @@ def load_library(path: str | None = None):
     lib.sls_plan_update_plant.restype = C.c_int; lib.sls_plan_update_plant.argtypes = [vp, vp, vp, vp, C.c_int]
     lib.sls_plan_update_result.restype = C.c_int; lib.sls_plan_update_result.argtypes = [vp, i64p]
     lib.sls_plan_fetch_plant.restype = C.c_int; lib.sls_plan_fetch_plant.argtypes = [vp, dp, dp]
+    lib.sls_plan_update_weights.restype = C.c_int; lib.sls_plan_update_weights.argtypes = [vp, vp, vp, vp, C.c_int]
+    lib.sls_plan_update_weights_result.restype = C.c_int; lib.sls_plan_update_weights_result.argtypes = [vp, i64p]
+    lib.sls_plan_fetch_weights.restype = C.c_int; lib.sls_plan_fetch_weights.argtypes = [vp, dp, dp]
     u8p = C.POINTER(C.c_uint8)
     lib.sls_plan_execute_columns.restype = C.c_int; lib.sls_plan_execute_columns.argtypes = [vp, vp, vp, C.c_int, i64p, C.c_int64, i64p]
     lib.sls_plan_track_changes.restype = C.c_int; lib.sls_plan_track_changes.argtypes = [vp, C.c_int]
@@ -239,6 +244,10 @@ def load_library(path: str | None = None):
                                                    i32p, C.POINTER(C.c_uint8)]
     lib.sls_debug_affected_host.restype = C.c_int
     lib.sls_debug_affected_host.argtypes = common + [u8p, u8p, u8p]
+    lib.sls_debug_weights_shape_check.restype = C.c_int
+    lib.sls_debug_weights_shape_check.argtypes = [C.POINTER(sls_dims), C.POINTER(sls_plant), dp]
+    lib.sls_debug_weights_host.restype = C.c_int
+    lib.sls_debug_weights_host.argtypes = common + [dp, dp, dp, dp, C.c_int, i64p, i32p, i64p, i32p, i32p, dp, dp, dp, dp, u8p, i64p]
     lib.sls_debug_tile_invert.restype = C.c_int; lib.sls_debug_tile_invert.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_int]
     lib.sls_plan_debug_read_workspace.restype = C.c_int; lib.sls_plan_debug_read_workspace.argtypes = [vp, C.c_int64, C.c_int64, dp]
     lib.sls_plan_debug_twisted4_tables.restype = C.c_int
@@ -286,8 +295,8 @@ class Marshalled:
         exercise the path the `ccall` binding takes); groups are always given 0-based on the Python side."""
         self.keep = []
         self.base = int(index_base)
-        # A and B2 as handed to the library (references only: struct, colptr, rowval, nzval, nrows), and — once
-        # Plan.update_plant has called own_plant_values — the nzval arrays this object owns and the structs point at
+        # A, B2, C1 and D12 as handed to the library (references only: struct, colptr, rowval, nzval, nrows), and — once
+        # Plan.update_plant or Plan.refine has called own_plant_values — the nzval arrays this object owns and the structs point at
         self.csc, self.nzval = {}, None
         T = len(Sx)
         if len(Su) != T:
@@ -296,7 +305,7 @@ class Marshalled:
         self.plant = sls_plant()
         for name, attr in (("A", "A"), ("B1", "B1"), ("B2", "B2"), ("C1", "C1"), ("D11", "D11"), ("D12", "D12")):
             M = getattr(P, attr)
-            setattr(self.plant, name, C.pointer(self._f64(M, name if name in ("A", "B2") else None)) if M is not None else None)
+            setattr(self.plant, name, C.pointer(self._f64(M, name if name in ("A", "B2", "C1", "D12") else None)) if M is not None else None)
         self.Sx = (sls_csc_bool * T)(*[self._bool(m) for m in Sx])
         self.Su = (sls_csc_bool * T)(*[self._bool(m) for m in Su])
         if groups is None:

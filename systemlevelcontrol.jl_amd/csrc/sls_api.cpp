@@ -30,6 +30,7 @@
 #include "sls_residual.h"
 #include "sls_routing.h"
 #include "sls_symbolic.h"
+#include "sls_weights.h"
 
 namespace {
 std::mutex g_err_mu;
@@ -872,6 +873,14 @@ static int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_pla
     if ((rc = upload(pl, pl->opmap.row_pos, &pl->d_upd_pos)) || (rc = upload(pl, pl->opmap.zero, &pl->d_upd_zero))) return bail(rc);
     if ((rc = dalloc(pl, std::max<size_t>(nop, 1), &pl->d_upd_stage)) || (rc = dalloc(pl, 1, &pl->d_upd_rejected))) return bail(rc);
   }
+  if (S.wu.updatable) {
+    // weights update (SLS_PLAN_WEIGHTS_UPDATABLE): what sls_plan_update_weights reads and writes besides w_pool, all from the arena
+    const size_t nv = (size_t)(S.Nx + S.Nu);
+    if ((rc = upload(pl, S.wu.b2, &pl->d_w_b2)) || (rc = upload(pl, S.wu.owner, &pl->d_w_owner)) ||
+        (rc = upload(pl, S.wu.diag, const_cast<const double**>(&pl->d_w_diag)))) return bail(rc);
+    if (!S.wu.ridge.empty() && (rc = upload(pl, S.wu.ridge, &pl->d_w_ridge))) return bail(rc);
+    if ((rc = dalloc(pl, nv, &pl->d_w_stage)) || (rc = dalloc(pl, 1, &pl->d_w_rejected))) return bail(rc);
+  }
   for (auto& L : pl->launches)
     if (L.kind == LaunchKind::Twisted && L.four) {
       L.t4_off = pl->t4_records; pl->t4_records += L.nsub;
@@ -1135,6 +1144,33 @@ extern "C++" int sls::plan_create_localized(sls_ctx* ctx, int dev_slot, const sl
   if (e != hipSuccess) return bail(hipfail(ctx, e, "device symbolic route (fill pass)"));
   if (fl[1]) return bail(fail(ctx, SLS_EUNSUPPORTED, "device symbolic route: a mask row lies outside its column's index set (A without a full diagonal); pass the masks to sls_h2_sf_plan"));
   tick("device: fill pass");
+  if (S.wu.updatable) {
+    // updatable weights on this route: a record for every column with B1[c,c] ≠ 0, filled on the host by the update's own twin
+    // from the plan-time diagonals.  The index sets exist on the device only, so they come back once (4 B per local variable,
+    // flagged plans only); plan_finish drops the host copy again.
+    S.idx_pool.resize((size_t)idx_tot);
+    if (idx_tot) {
+      e = hipMemcpy(S.idx_pool.data(), cp.idx_pool, (size_t)idx_tot * sizeof(int32_t), hipMemcpyDeviceToHost);
+      if (e != hipSuccess) return bail(hipfail(ctx, e, "hipMemcpy D2H (index sets)"));
+    }
+    S.wu.b2.assign((size_t)Nx, 0.0);
+    for (int64_t c = 0; c < Nx; ++c) {
+      double bd = 0.0;
+      for (int64_t k = P->B1->colptr[c] - b1; k < P->B1->colptr[c + 1] - b1; ++k)
+        if (P->B1->rowval[k] - b1 == c) bd = P->B1->nzval ? P->B1->nzval[k] : 1.0;
+      if (bd == 0.0) continue;                                  // a b = 0 column keeps no record: its minimiser ignores the weights
+      SubDesc& sd = S.subs[(size_t)c];
+      sd.has_w = 1; sd.off_w = 2 * idx_off[(size_t)c];
+      S.wu.b2[(size_t)c] = bd * bd;
+      S.obj_pool[2 * (size_t)c] = 1.0;                          // the scale belongs to has_w = 0 columns
+    }
+    weights_owner_scale(S);
+    std::string wmsg;
+    const double* dg = S.wu.diag.data();
+    if (check_weights_update(S.wu, Nx, Nu, dg, dg + Nx, wmsg)) return bail(fail(ctx, SLS_EUNSUPPORTED, wmsg + " (plan-time weights)"));
+    S.w_pool.assign((size_t)(2 * idx_tot), 0.0);
+    if ((rc = weight_records_host(S, dg, dg + Nx, S.w_pool.data(), nullptr, nullptr, nullptr, wmsg))) return bail(fail(ctx, rc, wmsg));
+  }
   if (!a1_borrowed) (void)hipFree(a1);
   a1 = nullptr;
   if (a2_borrowed) { ctx->slots[dev_slot].ltab_in_use = true; pl->ltab_borrowed = true; }
@@ -1505,6 +1541,90 @@ int sls_plan_fetch_plant(sls_plan* plan, double* A_nzval, double* B2_nzval) {
     if (int rc = read_behind_update(plan, A_nzval, plan->kp.At_val, (size_t)plan->opmap.nnzA * sizeof(double))) return rc;
   if (B2_nzval)
     if (int rc = read_behind_update(plan, B2_nzval, plan->kp.Bt_val, (size_t)plan->opmap.nnzB * sizeof(double))) return rc;
+  return 0;
+}
+
+int sls_plan_update_weights(sls_plan* plan, void* hip_stream, const double* c1_diag, const double* d12_diag, int on_device) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  sls_ctx* ctx = plan->ctx;
+  const Symbolic::UpdatableWeights& W = plan->sym.wu;
+  if (!W.updatable) return fail(ctx, SLS_EINVAL, "sls_plan_update_weights: plan not built with SLS_PLAN_WEIGHTS_UPDATABLE");
+  if (!c1_diag && !d12_diag) return fail(ctx, SLS_EINVAL, "sls_plan_update_weights: c1_diag and d12_diag are both NULL");
+  const int64_t Nx = plan->sym.Nx, Nu = plan->sym.Nu;
+  if (!on_device) {                        // everything is checked before anything is enqueued: a refused update leaves the plan as it was
+    std::string msg;
+    if (int rc = check_weights_update(W, Nx, Nu, c1_diag, d12_diag, msg)) return fail(ctx, rc, msg);
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCHK(ctx, hipSetDevice(plan->dev));
+  if (!plan->ev_upd) HIPCHK(ctx, hipEventCreateWithFlags(&plan->ev_upd, hipEventDisableTiming));
+  const KernelParams& kp = plan->kp;
+  WeightsUpdateParams wp{};
+  wp.subs = kp.subs; wp.nsub = kp.nsub; wp.idx_pool = kp.idx_pool; wp.Nx = Nx; wp.Nu = Nu;
+  wp.b2 = plan->d_w_b2; wp.owner = plan->d_w_owner; wp.ridge = plan->d_w_ridge;
+  wp.w_pool = const_cast<double*>(kp.w_pool); wp.diag = plan->d_w_diag; wp.rejected = plan->d_w_rejected;
+  wp.dirty = plan->part.track ? plan->part.dirty : nullptr;
+  if (on_device) {
+    wp.new_c1 = c1_diag; wp.new_d12 = d12_diag;
+  } else {
+    // as the operator update: through the slot's pinned buffer (C1's values, then D12's) into the staging array
+    const size_t nx = (size_t)Nx, nu = (size_t)Nu;
+    double* pin = reinterpret_cast<double*>(slot_pinned(ctx, plan->slot, (nx + nu) * sizeof(double)));
+    const double* src1 = c1_diag; const double* src2 = d12_diag;
+    if (pin) {
+      if (c1_diag && nx) { std::memcpy(pin, c1_diag, nx * sizeof(double)); src1 = pin; }
+      if (d12_diag && nu) { std::memcpy(pin + nx, d12_diag, nu * sizeof(double)); src2 = pin + nx; }
+    }
+    if (c1_diag && nx) HIPCHK(ctx, hipMemcpyAsync(plan->d_w_stage, src1, nx * sizeof(double), hipMemcpyHostToDevice, st));
+    if (d12_diag && nu) HIPCHK(ctx, hipMemcpyAsync(plan->d_w_stage + nx, src2, nu * sizeof(double), hipMemcpyHostToDevice, st));
+    if (pin) {
+      sls_ctx::Slot& sl = ctx->slots[plan->slot];
+      if (!sl.pinned_busy) HIPCHK(ctx, hipEventCreateWithFlags(&sl.pinned_busy, hipEventDisableTiming));
+      HIPCHK(ctx, hipEventRecord(sl.pinned_busy, st));
+      sl.pinned_pending = true;
+    } else {
+      HIPCHK(ctx, hipStreamSynchronize(st));           // no pinned buffer: the copy has read the caller's arrays
+    }
+    wp.new_c1 = c1_diag ? plan->d_w_stage : nullptr;
+    wp.new_d12 = d12_diag ? plan->d_w_stage + nx : nullptr;
+  }
+  HIPCHK(ctx, hipMemsetAsync(plan->d_w_rejected, 0, sizeof(unsigned long long), st));
+  hipError_t e = launch_weights_update(wp, st);
+  if (e != hipSuccess) return hipfail(ctx, e, "launch weights_update_kernel");
+  // the four-wave kernel's plan-time data (prepared records, static blocks, setup images, weight tables) read the records
+  e = launch_twisted4_prepares(plan, st);
+  if (e != hipSuccess) return hipfail(ctx, e, "launch twisted4_prepare_kernel");
+  HIPCHK(ctx, hipEventRecord(plan->ev_upd, st));
+  plan->upd_recorded = true; plan->w_upd_recorded = true;
+  if (plan->refine) {
+    // which columns are near-singular depends on the weights too: the attached pass goes, last, as in sls_plan_update_plant
+    if (int rc = wait_plan_done(plan)) return rc;
+    sls_plan_destroy(plan->refine);
+    plan->refine = nullptr; plan->refine_dst.clear();
+  }
+  return 0;
+}
+
+int sls_plan_update_weights_result(sls_plan* plan, int64_t* n_rejected) {
+  if (!plan || !n_rejected) return fail(nullptr, SLS_EINVAL, "null argument");
+  *n_rejected = 0;
+  if (!plan->w_upd_recorded) return 0;
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  unsigned long long n = 0;
+  if (int rc = read_behind_update(plan, &n, plan->d_w_rejected, sizeof(n))) return rc;
+  *n_rejected = (int64_t)n;
+  return 0;
+}
+
+int sls_plan_fetch_weights(sls_plan* plan, double* c1_diag, double* d12_diag) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  if (!plan->sym.wu.updatable) return fail(plan->ctx, SLS_EINVAL, "sls_plan_fetch_weights: plan not built with SLS_PLAN_WEIGHTS_UPDATABLE");
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  const size_t nx = (size_t)plan->sym.Nx, nu = (size_t)plan->sym.Nu;
+  if (c1_diag)
+    if (int rc = read_behind_update(plan, c1_diag, plan->d_w_diag, nx * sizeof(double))) return rc;
+  if (d12_diag)
+    if (int rc = read_behind_update(plan, d12_diag, plan->d_w_diag + nx, nu * sizeof(double))) return rc;
   return 0;
 }
 

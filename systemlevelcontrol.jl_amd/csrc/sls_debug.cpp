@@ -18,6 +18,7 @@
 #include "sls_residual.h"
 #include "sls_routing.h"
 #include "sls_symbolic.h"
+#include "sls_weights.h"
 
 using namespace sls;
 
@@ -155,6 +156,69 @@ int sls_debug_affected_host(const sls_dims* dims, const sls_plant* P, const sls_
   std::fill(dirty, dirty + S.subs.size(), (uint8_t)0);
   rc = mark_affected_host(S, M, changed_A, changed_B2, dirty, msg);
   if (rc) return fail(nullptr, rc, msg);
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): the index-set-free part of the updatable shape rule.  Needs no device. */
+int sls_debug_weights_shape_check(const sls_dims* dims, const sls_plant* P, double* diag) {
+  Inputs in{dims, P, nullptr, nullptr, 0, nullptr, nullptr};
+  std::string msg;
+  if (!dims || !P) return fail(nullptr, SLS_EINVAL, "null dims/plant");
+  sls_dims d0 = *dims; d0.T = 1;                       // the masks are not looked at: validate the plant alone
+  {
+    // validate_inputs wants masks; an empty Nx×Nx / Nu×Nx pair of one time step serves
+    std::vector<int64_t> cp((size_t)dims->Nx + 1, dims->index_base);
+    sls_csc_bool sx{dims->Nx, dims->Nx, cp.data(), nullptr, nullptr}, su{dims->Nu, dims->Nx, cp.data(), nullptr, nullptr};
+    in.dims = &d0; in.Sx = &sx; in.Su = &su;
+    int rc = validate_inputs(in, msg);
+    if (rc) return fail(nullptr, rc, msg);
+  }
+  std::vector<double> dg;
+  int rc = weights_shape_check(dims, P, dg, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  if (diag) std::copy(dg.begin(), dg.end(), diag);
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): the weight records of the host symbolic pass and the host twin of
+   sls_plan_update_weights on them.  Needs no device. */
+int sls_debug_weights_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su, int64_t ngroups,
+                           const int64_t* group_ptr, const int64_t* group_cols, const double* ridge_x, const double* ridge_u,
+                           const double* c1_diag, const double* d12_diag, int strict, int64_t* n_w, int32_t* has_w, int64_t* off_w,
+                           int32_t* n_x, int32_t* n_u, double* w_pool, double* obj_pool, double* b2, double* diag, uint8_t* dirty,
+                           int64_t* n_rejected) {
+  Inputs in{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
+  std::string msg;
+  int rc = validate_inputs(in, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  in.reg_x = ridge_x; in.reg_u = ridge_u;
+  std::vector<int64_t> gptr, gcols;
+  normalise_groups(in, gptr, gcols);
+  Symbolic S;
+  S.want_packed = false; S.compact = false;
+  rc = build_symbolic(in, 0, (int64_t)gptr.size() - 1, S, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  const size_t ns = S.subs.size();
+  if (n_rejected) *n_rejected = 0;
+  if (dirty) std::fill(dirty, dirty + ns, (uint8_t)0);
+  int rcu = 0;
+  if (c1_diag || d12_diag) {
+    if (!S.wu.updatable) return fail(nullptr, SLS_EINVAL, "weights update: the symbolic pass was not made with SLS_PLAN_WEIGHTS_UPDATABLE");
+    if (strict) rcu = check_weights_update(S.wu, S.Nx, S.Nu, c1_diag, d12_diag, msg);
+    if (!rcu) rcu = weight_records_host(S, c1_diag, d12_diag, S.w_pool.data(), S.wu.diag.data(), dirty, n_rejected, msg);
+  }
+  if (n_w) *n_w = (int64_t)S.w_pool.size();
+  for (size_t q = 0; q < ns; ++q) {
+    if (has_w) has_w[q] = S.subs[q].has_w;
+    if (off_w) off_w[q] = S.subs[q].off_w;
+    if (n_x) n_x[q] = S.subs[q].n;
+    if (n_u) n_u[q] = S.subs[q].m;
+    if (b2) b2[q] = S.wu.updatable ? S.wu.b2[q] : 0.0;
+  }
+  if (w_pool) std::copy(S.w_pool.begin(), S.w_pool.end(), w_pool);
+  if (obj_pool) std::copy(S.obj_pool.begin(), S.obj_pool.end(), obj_pool);
+  if (diag && S.wu.updatable) std::copy(S.wu.diag.begin(), S.wu.diag.end(), diag);
+  if (rcu) return fail(nullptr, rcu, msg);
   return 0;
 }
 

@@ -348,6 +348,28 @@ struct OperatorUpdateParams {
   unsigned long long* rejected;   // entries refused (not finite, or non-zero on a plan-time zero): counted, not written
 };
 
+// ---- weights update (sls_update.hip: weights_update_kernel) ----
+// New diagonals of C1 / D12 for a plan built with SLS_PLAN_WEIGHTS_UPDATABLE.  Variable g < Nx is state g (its value: C1[g, g]),
+// variable Nx + j input j (D12[Nx + j, j]).  Per subproblem with a record (has_w = 1) the kernel rewrites hinv_x / hinv_u:
+// 1 / (b2[q]·v² + ridge[g]), each operation rounded once.  A value is accepted when it is finite and owner[g]·v² + ridge[g] > 0,
+// owner[g] being the smallest b² over the records that hold variable g (−1: no record holds it, any finite value is accepted):
+// the products are monotone in b², so the value then passes the plan-time rule in every record.  The same test decides in both
+// parts of the kernel, so a refused value is written nowhere and counted once.
+struct WeightsUpdateParams {
+  const SubDesc* subs;  int32_t nsub;
+  const int32_t* idx_pool;
+  int64_t Nx, Nu;
+  const double* new_c1;     // Nx new diagonal values, or NULL: C1 unchanged
+  const double* new_d12;    // Nu new diagonal values, or NULL: D12 unchanged
+  const double* b2;         // [nsub], by out_index
+  const double* owner;      // [Nx + Nu]
+  const double* ridge;      // [Nx + Nu], or NULL: no ridge term
+  double* w_pool;
+  double* diag;             // [Nx + Nu] the diagonals the plan holds now
+  unsigned long long* rejected;   // values refused: counted, not written
+  uint8_t* dirty;           // [nsub] by out_index, or NULL (sls_plan_track_changes off): set where a record value changed bits
+};
+
 // ---- partial re-solve (sls_partial.hip) ----
 // changed_entries_kernel: which entries an update is about to change.  Entry numbering, row_pos and zero as in
 // OperatorUpdateParams (`up`); row_of[k] is the plant row of CSC position k (At_colidx, then Bt_colidx).  chg is indexed like

@@ -72,6 +72,7 @@ hipError_t launch_objective(const ObjectiveParams& p, int lds_doubles, double* d
 hipError_t launch_residual(const ResidualParams& p, double* d_totals, hipStream_t stream);
 hipError_t launch_tile_invert(const double* d_A, int n, double* d_ws, double* d_out, bool mlds, hipStream_t stream);
 hipError_t launch_operator_update(const OperatorUpdateParams& p, hipStream_t stream);
+hipError_t launch_weights_update(const WeightsUpdateParams& p, hipStream_t stream);
 // sls_partial.hip: the entries an update changes, the subproblems they touch, the compacted launch lists of a selected run
 hipError_t launch_changed_entries(const ChangedEntriesParams& p, hipStream_t stream);
 hipError_t launch_mark_affected(const MarkAffectedParams& p, hipStream_t stream);

@@ -90,6 +90,17 @@ struct sls_plan {
   unsigned long long* d_upd_rejected = nullptr;
   hipEvent_t ev_upd = nullptr;
   bool upd_recorded = false;
+  // weights update (sls_plan_update_weights), only in a plan built with SLS_PLAN_WEIGHTS_UPDATABLE (sym.wu holds
+  // the host copies the host path checks against): b² per subproblem, the value rule's scale and the ridge per variable (NULL:
+  // none), the diagonals the plan holds now, a staging array for host values (Nx + Nu doubles each) and the refusal counter.
+  // An update records ev_upd like the operator update: both are "the plan's last update" to everything that waits for one.
+  const double* d_w_b2 = nullptr;
+  const double* d_w_owner = nullptr;
+  const double* d_w_ridge = nullptr;
+  double* d_w_diag = nullptr;
+  double* d_w_stage = nullptr;
+  unsigned long long* d_w_rejected = nullptr;
+  bool w_upd_recorded = false;
   // partial re-solve (sls_plan_execute_columns / _dirty, sls_plan_track_changes): one device allocation made by
   // the first of those calls (partial_ensure) — a plan that never uses them holds none of it and reports the same
   // workspace_bytes.  Layouts: sls_device.h (ChangedEntriesParams, MarkAffectedParams, CompactOrderParams).

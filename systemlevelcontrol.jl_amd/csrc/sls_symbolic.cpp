@@ -1,5 +1,6 @@
 // sls_symbolic.cpp — see sls_symbolic.h.  Pure host code (compiled by hipcc or g++).
 #include "sls_symbolic.h"
+#include "sls_weights.h"
 
 #include <algorithm>
 #include <cmath>
@@ -507,7 +508,17 @@ int localized_prepare(const sls_dims* dims, const sls_plant* P, int64_t d, doubl
     if ((P->C1 == nullptr) != (P->D12 == nullptr)) { msg = "C1 and D12 must be given together"; return SLS_EINVAL; }
   }
   Inputs in{dims, P, nullptr, nullptr, 0, nullptr, nullptr};
-  if (!weights_are_default(in)) {
+  S.wu.updatable = (dm.flags & SLS_PLAN_WEIGHTS_UPDATABLE) != 0;
+  if (S.wu.updatable) {
+    // the LQR shape with any diagonal values; D11 must be zero everywhere (this route knows no index set on the host)
+    if ((rc = weights_shape_check(dims, P, S.wu.diag, msg))) return rc;
+    const sls_plant P0{P->A, P->B1, P->B2, nullptr, P->D11, nullptr};
+    const Inputs in0{dims, &P0, nullptr, nullptr, 0, nullptr, nullptr};
+    if (!weights_are_default(in0)) {
+      msg = "SLS_PLAN_WEIGHTS_UPDATABLE: D11 has a non-zero; the device-resident symbolic route needs D11 = 0";
+      return SLS_EUNSUPPORTED;
+    }
+  } else if (!weights_are_default(in)) {
     msg = "the device-resident symbolic route is built for the 3-argument Plant's cost ([C1 D12] = I, D11 = 0); pass the masks to sls_h2_sf_plan for other weights";
     return SLS_EUNSUPPORTED;
   }
@@ -708,6 +719,14 @@ static int fill_range(const Inputs& in, const std::vector<int64_t>& gptr, const 
         else if (v != 0.0 && nc > 1 && map_x[r] >= 0 && std::binary_search(cols, cols + nc, r)) coupled = true;
       }
     }
+    if (S.wu.updatable) {
+      // an updatable plan (sls_weights.h): no coupled group, no D11 on a selected row
+      if (int rc = weights_group_check(in.dims, in.P, cols, nc, map_x.data(), map_u.data(), coupled, msg)) {
+        for (int32_t i = 0; i < n; ++i) map_x[gs.sx[i]] = -1;
+        for (int32_t i = 0; i < m; ++i) map_u[gs.su[i]] = -1;
+        return rc;
+      }
+    }
     if (coupled && nc > 64) {
       msg = "coupled column group of more than 64 columns: not supported by this build";
       for (int32_t i = 0; i < n; ++i) map_x[gs.sx[i]] = -1;
@@ -746,7 +765,7 @@ static int fill_range(const Inputs& in, const std::vector<int64_t>& gptr, const 
     const bool reg = in.reg_x || in.reg_u;
     auto rxv = [&](int32_t i) { return in.reg_x ? in.reg_x[gs.sx[i]] : 0.0; };
     auto ruv = [&](int32_t i) { return in.reg_u ? in.reg_u[gs.su[i]] : 0.0; };
-    const bool use_w = !def_w || coupled || reg;
+    const bool use_w = !def_w || coupled || reg || S.wu.updatable;
     if (use_w) {
       if (zcount.empty()) { zcount.assign(Nx + Nu, 0); d11col.assign(Nx + Nu, 0.0); }
       hdx.assign(n, 0.0); hdu.assign(m, 0.0);
@@ -844,6 +863,7 @@ static int fill_range(const Inputs& in, const std::vector<int64_t>& gptr, const 
       }
       }
       nfree_of[sd.out_index] = (int32_t)nfree;
+      if (S.wu.updatable) S.wu.b2[(size_t)sd.out_index] = bdiag[q] * bdiag[q];
       // weights record
       sd.has_w = 0; sd.off_w = 0;
       bool bad_w = false;
@@ -884,7 +904,7 @@ static int fill_range(const Inputs& in, const std::vector<int64_t>& gptr, const 
               for (int64_t z : touched) d11col[z] = 0.0;
             }
           }
-          bool ident = !any_d11 && !coupled && !reg;
+          bool ident = !any_d11 && !coupled && !reg && !S.wu.updatable;   // an updatable plan keeps a record for uniform weights too
           for (int32_t i = 0; i < n && ident; ++i) if (hdx[i] != hdx[0]) ident = false;
           for (int32_t i = 0; i < m && ident; ++i) if (hdu[i] != (n ? hdx[0] : hdu[0])) ident = false;
           for (int32_t i = 0; i < n; ++i) if (!(b2 * hdx[i] + rxv(i) > 0.0)) { msg = "zero cost weight on a state variable (singular Hessian): not supported"; bad_w = true; }
@@ -1004,6 +1024,16 @@ int build_symbolic(const Inputs& in, int64_t gbeg, int64_t gend, Symbolic& S, st
   double tdbg = clk();
   auto tick = [&](const char* what) { if (dbg_t) { const double n = clk(); std::fprintf(stderr, "[sls symbolic] %-24s %8.3f ms\n", what, 1e3 * (n - tdbg)); tdbg = n; } };
   const bool def_w = weights_are_default(in);
+  S.wu.updatable = (d.flags & SLS_PLAN_WEIGHTS_UPDATABLE) != 0;
+  if (S.wu.updatable) {
+    if (int rc = weights_shape_check(in.dims, in.P, S.wu.diag, msg)) return rc;
+    S.wu.ridge.clear();
+    if (in.reg_x || in.reg_u) {
+      S.wu.ridge.assign((size_t)(Nx + Nu), 0.0);
+      if (in.reg_x) std::copy(in.reg_x, in.reg_x + Nx, S.wu.ridge.begin());
+      if (in.reg_u) std::copy(in.reg_u, in.reg_u + Nu, S.wu.ridge.begin() + Nx);
+    }
+  }
   tick("operator CSR + defaults");
 
   // ---- the per-group work is independent and every pool slice has a size known from (ñx, ñu, T): three passes on host
@@ -1039,6 +1069,7 @@ int build_symbolic(const Inputs& in, int64_t gbeg, int64_t gend, Symbolic& S, st
   if (S.want_packed) S.compact = false;
   S.idx_pool.resize(idx_tot);
   S.subs.resize(sub_tot); S.sub_col.resize(sub_tot); S.obj_pool.resize(2 * sub_tot);
+  if (S.wu.updatable) S.wu.b2.assign((size_t)sub_tot, 0.0);
   std::vector<int32_t> nfree_of((size_t)sub_tot, 0);
   auto pass_b = [&]() -> int {
     if (S.compact) { S.cmask.resize(cw_tot); S.cbase.resize(2 * T * sub_tot); S.coff.resize(sub_tot); }
@@ -1106,6 +1137,7 @@ int build_symbolic(const Inputs& in, int64_t gbeg, int64_t gend, Symbolic& S, st
     parts[t] = RangePart();
   });
   tick("C: packed numbering");
+  if (S.wu.updatable) weights_owner_scale(S);
   // processing order: descending predicted cost (T+1)·ñx³ (longest first ⇒ short tail)
   S.order.resize(S.subs.size());
   std::iota(S.order.begin(), S.order.end(), 0);

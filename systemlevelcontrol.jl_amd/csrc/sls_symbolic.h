@@ -99,6 +99,15 @@ struct Symbolic {
   pool_vec<int32_t> cbase;              // per subproblem T × 2: value-array index of the first x / first u entry of the column
   pool_vec<int64_t> coff;               // per subproblem: its first word in cmask
   int64_t md_total = 0;                 // length of mask_pool / dest_pool (whether or not they are materialised on the host)
+  // Updatable cost weights (SLS_PLAN_WEIGHTS_UPDATABLE in sls_dims.flags; sls_weights.h).  `updatable` is an input
+  // of the pass: it checks the updatable shape, gives every column with b ≠ 0 a has_w = 1 record (uniform weights included) and
+  // leaves what sls_plan_update_weights needs: b² per subproblem (by out_index), the plan-time diagonals (C1's Nx values, then
+  // D12's Nu), the ridge per variable in the same numbering (empty: none) and, per variable, the smallest b² over the records
+  // that hold it (−1: none does) — the value rule's scale.
+  struct UpdatableWeights {
+    bool updatable = false;
+    std::vector<double> b2, diag, ridge, owner;
+  } wu;
   int32_t max_n = 0, max_m = 0, max_nnzA = 0, max_nnzB = 0;
   double flops_alg = 0.0, bytes_alg = 0.0;
   int64_t n_total_subproblems = 0;      // over ALL groups (for col_status indexing)

@@ -92,11 +92,13 @@ def default_context():
 class Plan:
     """Symbolic pass + device-resident tables for a shard of the groups (sls_h2_sf_plan)."""
 
-    def __init__(self, ctx: Context, P, S, groups=None, group_range=None, dev_slot=0, objective="h2"):
+    def __init__(self, ctx: Context, P, S, groups=None, group_range=None, dev_slot=0, objective="h2", updatable_weights=False):
+        """updatable_weights=True builds the plan with SLS_PLAN_WEIGHTS_UPDATABLE: `update_weights` can then give it new LQR
+        weights (C1 = [diag(q); 0], D12 = [0; diag(r)], D11 = 0 on the selected rows, no coupled group: SLSError otherwise)."""
         Sx, Su = S
         self.ctx = ctx
         self._lib = ctx._lib
-        self.m = _capi.Marshalled(P, Sx, Su, groups, flags=_objective_flags(objective))
+        self.m = _capi.Marshalled(P, Sx, Su, groups, flags=_plan_flags(objective, updatable_weights))
         ng = self.m.ngroups if groups is not None else P.Nx
         gb, ge = (0, ng) if group_range is None else group_range
         h = C.c_void_p()
@@ -114,15 +116,16 @@ class Plan:
         self._owned_values = []
 
     @classmethod
-    def localized(cls, ctx, P, d, T, alpha, dev_slot=0, objective="h2", index_base=0):
+    def localized(cls, ctx, P, d, T, alpha, dev_slot=0, objective="h2", index_base=0, updatable_weights=False):
         """sls_h2_sf_plan_localized: the plan of the README's (d, T, α) localization built from the plant alone — level sets,
         index sets, mask slices and destinations computed on the device, no mask array crosses PCIe.  Values come back in the
-        CSC order of `workloads.localization_masks_native(P.A, P.B2, d, T, alpha)`."""
+        CSC order of `workloads.localization_masks_native(P.A, P.B2, d, T, alpha)`.  updatable_weights=True: as in `Plan`; the
+        plant may then carry LQR weights other than the identity (D11 must be zero)."""
         self = cls.__new__(cls)
         self.ctx = ctx
         self._lib = ctx._lib
         empty = [sp.csc_matrix((P.Nx, P.Nx), dtype=bool)] * 0
-        self.m = _capi.Marshalled(P, empty, empty, None, index_base=index_base, flags=_objective_flags(objective))
+        self.m = _capi.Marshalled(P, empty, empty, None, index_base=index_base, flags=_plan_flags(objective, updatable_weights))
         self.m.dims.T = int(T)
         h = C.c_void_p()
         _capi.check(self._lib.sls_h2_sf_plan_localized(ctx.handle, dev_slot, C.byref(self.m.dims), C.byref(self.m.plant), int(d),
@@ -160,6 +163,10 @@ class Plan:
             own = self.m.own_plant_values()
             own["A"][:], own["B2"][:] = self.plant_values()
             self._plant_updated = False
+        if getattr(self, "_weights_updated", False):     # … and the weights it holds
+            own = self.m.own_plant_values()
+            own["C1"][:], own["D12"][:] = self.weights()
+            self._weights_updated = False
         n = C.c_int64()
         _capi.check(self._lib.sls_plan_refine(self.handle, *self.m.common_args(), stream, d_values, int(packed), C.byref(n)), self.ctx.handle)
         return n.value
@@ -213,6 +220,55 @@ class Plan:
         n = C.c_int64()
         _capi.check(self._lib.sls_plan_update_result(self.handle, C.byref(n)), self.ctx.handle)
         return n.value
+
+    # -- new LQR weights for a plan built with updatable_weights=True (sls_mi355x.h) --
+    def update_weights(self, C1=None, D12=None, stream=None):
+        """sls_plan_update_weights: new diagonals of C1 and / or D12, enqueued on `stream`; the next `execute` solves the
+        re-weighted problem without a rebuild.  Each argument is None (unchanged), a 1-D float64 array of the diagonal (Nx values
+        C1[i, i], Nu values D12[Nx + j, j]), a scipy sparse matrix of the LQR shape ([diag(q); 0] / [0; diag(r)], one stored entry per
+        column: ValueError otherwise; the diagonal is taken on the host) or a CUDA torch tensor of the diagonal, which selects
+        the device path (both arguments must then be tensors, or one of them None).  A value must be finite and leave the
+        Hessian positive (0.0 needs a ridge term): the host path raises SLSError (SLS_EINVAL) and leaves the plan untouched, the
+        device path skips such values and counts them (`update_weights_result`).  An attached refinement is dropped — call
+        `refine` again; it passes the plant with the weights the device holds (`weights`)."""
+        given = [(name, v) for name, v in (("C1", C1), ("D12", D12)) if v is not None]
+        if not given:
+            raise ValueError("update_weights: give C1, D12 or both")
+        on_device = [_is_device_tensor(v) for _, v in given]
+        if any(on_device) != all(on_device):
+            raise ValueError("update_weights: C1 and D12 must both be host arrays or both be device tensors")
+        Nx, Nu = int(self.m.dims.Nx), int(self.m.dims.Nu)
+        ptrs, keep = {"C1": None, "D12": None}, []
+        for name, v in given:
+            n, shift = (Nx, 0) if name == "C1" else (Nu, Nx)
+            if on_device[0]:
+                if v.dtype != _torch().float64 or v.dim() != 1 or not v.is_contiguous() or v.device.index != self.info["device"]:
+                    raise ValueError(f"update_weights: {name} must be a contiguous 1-D float64 tensor on the plan's device")
+                if v.numel() != n:
+                    raise ValueError(f"update_weights: {name} has {v.numel()} values, the diagonal has {n}")
+                ptrs[name] = v.data_ptr()
+            else:
+                d = _diag_of(name, v, n, shift, Nx + Nu)
+                keep.append(d)
+                ptrs[name] = d.ctypes.data
+        _capi.check(self._lib.sls_plan_update_weights(self.handle, stream, ptrs["C1"], ptrs["D12"], int(on_device[0])), self.ctx.handle)
+        self._weights_updated = True
+
+    def update_weights_result(self):
+        """sls_plan_update_weights_result: waits for the plan's last update and returns how many values the device path of the
+        last `update_weights` refused (0: applied in full; always 0 after a host-path update)."""
+        n = C.c_int64()
+        _capi.check(self._lib.sls_plan_update_weights_result(self.handle, C.byref(n)), self.ctx.handle)
+        return n.value
+
+    def weights(self):
+        """sls_plan_fetch_weights: (C1 diagonal, D12 diagonal) as the plan holds them on the device now — waits for the last
+        update; values its device path refused are at their old values."""
+        Nx, Nu = int(self.m.dims.Nx), int(self.m.dims.Nu)
+        a, b = np.zeros(max(Nx, 1)), np.zeros(max(Nu, 1))
+        dp = C.POINTER(C.c_double)
+        _capi.check(self._lib.sls_plan_fetch_weights(self.handle, a.ctypes.data_as(dp), b.ctypes.data_as(dp)), self.ctx.handle)
+        return a[:Nx], b[:Nu]
 
     # -- partial re-solve: only the columns a local plant change touched (sls_mi355x.h, DESIGN §3.8) --
     def execute_columns(self, d_values, subs, packed=False, stream=None):
@@ -463,6 +519,22 @@ def _nzval_of(name, v, nnz, m):
     return nz
 
 
+def _diag_of(name, v, n, shift, nz):
+    """The diagonal a host argument of `Plan.update_weights` stands for: a scipy matrix must have the LQR shape."""
+    if sp.issparse(v):
+        M = sp.csc_matrix(v)
+        if not M.has_sorted_indices:
+            M = M.copy(); M.sort_indices()
+        if M.shape != (nz, n) or M.nnz != n or not np.array_equal(M.indptr, np.arange(n + 1)) or \
+                not np.array_equal(M.indices, np.arange(n) + shift):
+            raise ValueError(f"update_weights: {name} must be {nz}×{n} with one stored entry per column, column j on row {shift} + j")
+        v = M.data
+    d = np.ascontiguousarray(v, dtype=np.float64)
+    if d.ndim != 1 or d.size != n:
+        raise ValueError(f"update_weights: {name} needs the {n} diagonal values (1-D), got shape {d.shape}")
+    return d
+
+
 class _WantObjective:
     """Turns the context's objective option on for one call and restores `off` afterwards (the option is off by default and
     these wrappers leave it as they found it: only calls that ask for the values pay for the evaluation)."""
@@ -676,6 +748,10 @@ def SLS_H2_localized(P, d, T, alpha, *, ctx: Context | None = None, return_info=
         warnings.warn(f"SLS_H2_localized: {rc} of {P.Nx} subproblems not solved — pass return_info=True for the per-column status",
                       RuntimeWarning, stacklevel=2)
     return Phix, Phiu
+
+
+def _plan_flags(objective, updatable_weights):
+    return _objective_flags(objective) | (_capi.SLS_PLAN_WEIGHTS_UPDATABLE if updatable_weights else 0)
 
 
 def _objective_flags(objective):
