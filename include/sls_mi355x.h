@@ -567,6 +567,61 @@ int  sls_controller_step(sls_controller* ctl, void* hip_stream, const double* d_
 int  sls_controller_info(const sls_controller* ctl, int64_t* n_entries, int64_t* steps_done, int64_t* state_bytes);
 void sls_controller_destroy(sls_controller* ctl);
 
+/* ---- closed-loop rollout of a resident Φ against an ensemble of plants (csrc/sls_rollout.hip, csrc/sls_rollout.h) ----
+ * How a Φ behaves on plants that are NOT the design model.  Every one of `nscen` scenarios has its own VALUES of A and B2 on the
+ * patterns given at plan time; B1 and Φ are shared.  Steps are numbered as for the controller; step k of scenario s is
+ *     ŵ_k     = x_k − β_k                                   (β_0 = 0; ŵ_j = 0 for j < 0)
+ *     u_k     = Σ_{τ=1..T}   Φu[τ]   · ŵ_{k+1−τ}
+ *     β_{k+1} = Σ_{τ=1..T−1} Φx[τ+1] · ŵ_{k+1−τ}
+ *     x_{k+1} = A⁽ˢ⁾·x_k + B1·w_k + B2⁽ˢ⁾·u_k
+ *     J⁽ˢ⁾   += Σ_i (q_i·x_k[i])² + Σ_j (r_j·u_k[j])²        peak_x⁽ˢ⁾ = max(peak_x⁽ˢ⁾, max_i |x_k[i]|), peak_u likewise
+ * x_0 comes from the reset (default 0; a non-zero x_0 acts as a disturbance at time 0: ŵ_0 = x_0).  After K steps in total J and
+ * the peaks cover k = 0 … K−1; the current state x_K is not counted yet.  With the design plant, x_0 = 0 and one run, the recorded
+ * x, u are rows 0 … steps−1 of sls_closed_loop_run bit for bit (the simulator's step restated on the controller's ring).  Device
+ * memory does not depend on the number of steps.  Cost and peaks are accumulated per row by exactly one owner each and reduced in
+ * a fixed order (sls_rollout.h): no floating-point atomics, bit-identical from run to run and however the steps are split into calls.
+ * sls_rollout_plan: dims, P->A, P->B1, P->B2 (patterns and initial values) and the masks are read.  Everything is allocated here: Φ
+ *   in row order, the mirrored ŵ ring of the controller, x and β (two copies each), the plant values per scenario in CSR order,
+ *   scenario innermost ([nnz(A)][nscen], [nnz(B2)][nscen], every scenario initialised from P), a staging buffer of
+ *   max(nnz(A), nnz(B2))·nscen doubles for the host path of set_plant, the weights q = 1, r = 1 and the per-row accumulators.  The
+ *   object starts in the reset state.  Limits and codes as sls_controller_plan: SLS_EUNSUPPORTED when (T+1)·Nx exceeds int32 or
+ *   nscen exceeds 65535·64; SLS_EINVAL for nscen < 1 or a dev_slot out of range.
+ * sls_rollout_load: d_values = Φ in the mask-order value array sls_plan_execute(packed = 0) fills (DEVICE), as sls_controller_load;
+ *   state, accumulators and the step counter are NOT touched, so Φ may be swapped in the middle of a rollout.
+ * sls_rollout_set_plant: new plant values, in the caller's CSC nzval order — the convention of sls_plan_update_plant and
+ *   sls_plan_fetch_plant, so a plan's current values pass straight through.  NULL keeps what is there.  per_scenario = 0: one
+ *   array of nnz values, broadcast to all scenarios; per_scenario = 1: [nnz][nscen], scenario innermost.  on_device = 1: DEVICE
+ *   arrays, read by a gather kernel on the stream (they must stay valid until it has run); on_device = 0: HOST arrays, copied to the
+ *   staging buffer first — this path waits for the stream until the copy is done.  THE VALUES ARE NOT VALIDATED: no finite rule and
+ *   no zero rule apply (a rollout has no kernel selection that depends on them); a NaN or an unstable plant simply shows in x, u
+ *   and the cost.
+ * sls_rollout_set_weights: q [Nx], rr [Nu] (NULL keeps; HOST or DEVICE by on_device; the host path waits for its copy) — the
+ *   arrays of sls_plan_fetch_weights can be passed as they are.  Takes effect from the next step on; what is accumulated stays.
+ * sls_rollout_reset: clears the ring, β, x, the accumulators and the step count; d_x0 [Nx][nscen] (DEVICE) or NULL for x_0 = 0.
+ * sls_rollout_run: `steps` steps from the current state.  d_w [steps][Nw][nscen] (DEVICE) or NULL; d_x [steps][Nx][nscen] and
+ *   d_u [steps][Nu][nscen] (DEVICE, each nullable) record x_k, u_k of the steps run — with both NULL only cost and peaks accumulate.
+ *   One kernel launch per step; the call enqueues on `hip_stream` (NULL = null stream) and returns, allocates nothing and never
+ *   waits.  steps = 0 is a no-op.  SLS_EINVAL before the first load or for steps < 0; SLS_EUNSUPPORTED on a stream that is being
+ *   captured (the ring slot and the buffer parity are launch arguments); the object stays usable.
+ * sls_rollout_stats: d_cost, d_peak_x, d_peak_u [nscen] each (DEVICE, nullable), of the steps run since the last reset; enqueued.
+ * sls_rollout_fetch: the same into HOST arrays (nullable) plus x_now [Nx][nscen], the current state x_K; waits for the stream.
+ * sls_rollout_info (each output nullable): stored-true Φ entries a step reads (12 B each), steps enqueued since the last reset,
+ *   device bytes of the state (what a reset clears) and of the per-scenario plant values (a step reads them once: 8·nnz·nscen B).
+ * The caller issues the calls of one object on one stream or orders them with events. */
+typedef struct sls_rollout sls_rollout;
+int  sls_rollout_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx,
+                      const sls_csc_bool* Su, int64_t nscen, sls_rollout** out);
+int  sls_rollout_load(sls_rollout* r, void* hip_stream, const double* d_values);
+int  sls_rollout_set_plant(sls_rollout* r, void* hip_stream, const double* A_nzval, const double* B2_nzval, int on_device,
+                           int per_scenario);
+int  sls_rollout_set_weights(sls_rollout* r, void* hip_stream, const double* q, const double* rr, int on_device);
+int  sls_rollout_reset(sls_rollout* r, void* hip_stream, const double* d_x0);
+int  sls_rollout_run(sls_rollout* r, void* hip_stream, const double* d_w, int64_t steps, double* d_x, double* d_u);
+int  sls_rollout_stats(sls_rollout* r, void* hip_stream, double* d_cost, double* d_peak_x, double* d_peak_u);
+int  sls_rollout_fetch(sls_rollout* r, void* hip_stream, double* x_now, double* cost, double* peak_x, double* peak_u);
+int  sls_rollout_info(const sls_rollout* r, int64_t* n_entries, int64_t* steps_done, int64_t* state_bytes, int64_t* plant_bytes);
+void sls_rollout_destroy(sls_rollout* r);
+
 /* ---- closed-loop 𝓛₁ and 𝓗∞ norms of a resident Φ (csrc/sls_norms.hip) ----
  * The two norms SLS designs are judged by beside the 𝓗₂ cost.  Built from the masks alone, like the controller.  Rows are the Nx
  * state rows followed by the Nu input rows, N = Nx + Nu; for t = 0 … T−1 (0-based)

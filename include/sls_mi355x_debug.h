@@ -181,6 +181,29 @@ int sls_debug_norms_h2_host(const sls_dims* dims, const sls_csc_bool* Sx, const 
 int sls_debug_norms_cov_host(const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su, const double* values, const double* cz,
                              const double* b, int64_t npairs, const int64_t* pair_i, const int64_t* pair_j, double* cov);
 
+/* The plan-time tables of the ensemble rollout (sls_rollout_plan; csrc/sls_rollout.cpp: build_rollout_tables) beyond the
+ * controller's: A and B2 by rows (A_ptr / B2_ptr [Nx + 1], A_idx / B2_idx column per CSR entry, ascending inside a row), A_src /
+ * B2_src — the position in the caller's CSC nzval array the gather of sls_rollout_set_plant reads for each CSR entry — B2_owner
+ * (1 where the entry's state row is the first, ascending, that stores the entry's column: that wave counts u_j in cost and
+ * peak) and the orphan actuators (empty B2 column; counted by a wave of their own), ascending.  *n_entries: stored-true Φ
+ * entries; *n_orphan.  Every output is nullable.  Needs no device. */
+int sls_debug_rollout_tables(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su, int64_t* n_entries,
+                             int64_t* n_orphan, int32_t* A_ptr, int32_t* A_idx, int32_t* A_src, int32_t* B2_ptr, int32_t* B2_idx,
+                             int32_t* B2_src, uint8_t* B2_owner, int32_t* orphan);
+
+/* Host twin of a whole rollout (csrc/sls_rollout.cpp: RolloutHost — the tables, the mirrored ring, the double buffers, the owner
+ * flags and the stats reduction of the device object in serial loops, rows accumulated in long double and rounded to double
+ * where the device stores one): plan with P, load `values` (Φ in mask order, HOST), set_plant(A_nzval, B2_nzval, per_scenario)
+ * (CSC order, NULL keeps P's), set_weights(q, rr) (NULL = ones), reset(x0) (NULL = 0), then `steps` steps with w
+ * [steps][Nw][nscen] or NULL — as ONE run when nchunks = 0, else as nchunks runs of chunks[c] steps (they must add up to steps).
+ * values2 non-NULL: that Φ is loaded before step switch_step, state kept.  Outputs, each nullable: x [steps][Nx][nscen],
+ * u [steps][Nu][nscen], x_end [Nx][nscen] (the state after the last step), cost, peak_x, peak_u [nscen].  Needs no device. */
+int sls_debug_rollout_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su, const double* values,
+                           int64_t nscen, const double* A_nzval, const double* B2_nzval, int per_scenario, const double* q,
+                           const double* rr, const double* x0, const double* w, int64_t steps, const int64_t* chunks, int64_t nchunks,
+                           const double* values2, int64_t switch_step, double* x, double* u, double* x_end, double* cost,
+                           double* peak_x, double* peak_u);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@
 module SLSMI355X
 
 using SparseArrays
-export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, update_weights!, weights, SLS_PLAN_WEIGHTS_UPDATABLE, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!, Norms, l1, hinf, h2, covariance_pattern!, covariance
+export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, update_weights!, weights, SLS_PLAN_WEIGHTS_UPDATABLE, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!, Rollout, set_plant!, set_weights!, run!, stats, Norms, l1, hinf, h2, covariance_pattern!, covariance
 
 const LIB = get(ENV, "SLS_MI355X_LIB", "libsls_mi355x.so")
 
@@ -247,6 +247,75 @@ step!(c::Controller, d_x::Ptr{Cvoid}, d_u::Ptr{Cvoid}; d_what::Ptr{Cvoid}=C_NULL
                      c.handle, stream, d_x, d_u, d_what))
 function Base.close(c::Controller)
     c.handle != C_NULL && (ccall((:sls_controller_destroy, LIB), Cvoid, (Ptr{Cvoid},), c.handle); c.handle = C_NULL)
+    return nothing
+end
+
+"""
+    r = Rollout(ctx, P, [𝓢ₓ,𝓢ᵤ]; nscen=1, dev_slot=0)
+    load!(r, d_values);  set_plant!(r, A_nzval, B2_nzval; per_scenario=false);  set_weights!(r, q, rr)
+    reset!(r; d_x0=C_NULL);  run!(r, steps; d_w=C_NULL, d_x=C_NULL, d_u=C_NULL);  cost, peak_x, peak_u, x_now = stats(r)
+
+`sls_rollout_*`: the closed-loop rollout of the Φ on the device against an ensemble of plants — scenario `s` has its own values of
+`A` and `B₂` on `P`'s non-zero patterns (every scenario starts from `P`'s values), `B₁` and Φ are shared; the LQR cost
+`Σ_k Σ_i (q_i x_k[i])² + Σ_j (r_j u_k[j])²` and the peaks of `|x|`, `|u|` are accumulated on the device and memory does not depend on
+the number of steps.  `set_plant!` takes `nzval` vectors in `P`'s own CSC order (`nothing` keeps; `per_scenario=true`: a
+`nscen × nnz` matrix, scenario innermost in memory) and is not validated; `set_weights!` takes `q` (`Nx`) and `rr` (`Nu`).  `reset!`,
+`run!` and `load!` enqueue on `stream` and return (`d_w`, `d_x`, `d_u`, `d_x0`: device pointers, `[steps][N·][nscen]`); `stats` waits
+and returns host vectors of length `nscen` and the current state (`nscen × Nx`).  `close(r)` frees it.  NOT EXECUTED in the build
+container, like the rest of this file.
+"""
+mutable struct Rollout
+    handle::Ptr{Cvoid}
+    Nx::Int; Nu::Int; nscen::Int
+end
+function Rollout(ctx::Ptr{Cvoid}, P, 𝓢::AbstractVector; nscen::Integer=1, dev_slot::Integer=0)
+    𝓢ₓ, 𝓢ᵤ = 𝓢
+    f64(M) = SparseMatrixCSC{Float64,Int}(M)
+    A, B1, B2 = f64(P.A), f64(P.B₁), f64(P.B₂)
+    Sx = [SparseMatrixCSC{Bool,Int}(S) for S in 𝓢ₓ];  Su = [SparseMatrixCSC{Bool,Int}(S) for S in 𝓢ᵤ]
+    mats = [csc(A), csc(B1), csc(B2)]
+    sx = [csc(S) for S in Sx];  su = [csc(S) for S in Su]
+    dims = Ref(Dims(P.Nx, P.Nu, P.Nz, P.Nw, length(Sx), 1, UInt32(0)))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve A B1 B2 mats Sx Su sx su begin
+        pm = pointer(mats)
+        plant = Ref(PlantPtrs(pm, pm + sizeof(CscF64), pm + 2sizeof(CscF64), Ptr{CscF64}(C_NULL), Ptr{CscF64}(C_NULL), Ptr{CscF64}(C_NULL)))
+        rc = ccall((:sls_rollout_plan, LIB), Cint, (Ptr{Cvoid}, Cint, Ref{Dims}, Ref{PlantPtrs}, Ptr{CscBool}, Ptr{CscBool}, Int64, Ref{Ptr{Cvoid}}),
+                   ctx, dev_slot, dims, plant, sx, su, nscen, h)
+    end
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx)))
+    return Rollout(h[], P.Nx, P.Nu, nscen)
+end
+load!(r::Rollout, d_values::Ptr{Cvoid}; stream::Ptr{Cvoid}=C_NULL) =
+    _ctl_check(ccall((:sls_rollout_load, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), r.handle, stream, d_values))
+_nzptr(v) = v === nothing ? Ptr{Float64}(C_NULL) : pointer(v)
+function set_plant!(r::Rollout, A_nzval::Union{Nothing,Array{Float64}}, B2_nzval::Union{Nothing,Array{Float64}}; per_scenario::Bool=false,
+                    stream::Ptr{Cvoid}=C_NULL)
+    GC.@preserve A_nzval B2_nzval begin                                 # host arrays: the call returns after they have been copied
+        _ctl_check(ccall((:sls_rollout_set_plant, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint, Cint),
+                         r.handle, stream, _nzptr(A_nzval), _nzptr(B2_nzval), 0, per_scenario ? 1 : 0))
+    end
+end
+function set_weights!(r::Rollout, q::Union{Nothing,Vector{Float64}}, rr::Union{Nothing,Vector{Float64}}; stream::Ptr{Cvoid}=C_NULL)
+    GC.@preserve q rr begin
+        _ctl_check(ccall((:sls_rollout_set_weights, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint),
+                         r.handle, stream, _nzptr(q), _nzptr(rr), 0))
+    end
+end
+reset!(r::Rollout; d_x0::Ptr{Cvoid}=C_NULL, stream::Ptr{Cvoid}=C_NULL) =
+    _ctl_check(ccall((:sls_rollout_reset, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), r.handle, stream, d_x0))
+run!(r::Rollout, steps::Integer; d_w::Ptr{Cvoid}=C_NULL, d_x::Ptr{Cvoid}=C_NULL, d_u::Ptr{Cvoid}=C_NULL, stream::Ptr{Cvoid}=C_NULL) =
+    _ctl_check(ccall((:sls_rollout_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                     r.handle, stream, d_w, steps, d_x, d_u))
+function stats(r::Rollout; stream::Ptr{Cvoid}=C_NULL)
+    cost, px, pu = zeros(r.nscen), zeros(r.nscen), zeros(r.nscen)
+    x = zeros(r.nscen, r.Nx)                                            # column-major (nscen, Nx) = the library's [Nx][nscen]
+    _ctl_check(ccall((:sls_rollout_fetch, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                     r.handle, stream, x, cost, px, pu))
+    return cost, px, pu, x
+end
+function Base.close(r::Rollout)
+    r.handle != C_NULL && (ccall((:sls_rollout_destroy, LIB), Cvoid, (Ptr{Cvoid},), r.handle); r.handle = C_NULL)
     return nothing
 end
 

@@ -94,6 +94,8 @@ EXPORTS = [
     "sls_plan_residual", "sls_plan_fetch_residual",
     "sls_controller_plan", "sls_controller_load", "sls_controller_reset", "sls_controller_step", "sls_controller_info",
     "sls_controller_destroy",
+    "sls_rollout_plan", "sls_rollout_load", "sls_rollout_set_plant", "sls_rollout_set_weights", "sls_rollout_reset", "sls_rollout_run",
+    "sls_rollout_stats", "sls_rollout_fetch", "sls_rollout_info", "sls_rollout_destroy",
     "sls_norms_plan", "sls_norms_load", "sls_norms_l1", "sls_norms_hinf", "sls_norms_fetch_l1", "sls_norms_fetch_hinf", "sls_norms_info",
     "sls_norms_destroy", "sls_norms_h2", "sls_norms_fetch_h2", "sls_norms_cov_pattern", "sls_norms_cov", "sls_norms_fetch_cov",
 ]
@@ -209,6 +211,17 @@ def load_library(path: str | None = None):
     lib.sls_controller_step.restype = C.c_int; lib.sls_controller_step.argtypes = [vp, vp, vp, vp, vp]
     lib.sls_controller_info.restype = C.c_int; lib.sls_controller_info.argtypes = [vp, i64p, i64p, i64p]
     lib.sls_controller_destroy.restype = None; lib.sls_controller_destroy.argtypes = [vp]
+    planted = [C.POINTER(sls_dims), C.POINTER(sls_plant), C.POINTER(sls_csc_bool), C.POINTER(sls_csc_bool)]
+    lib.sls_rollout_plan.restype = C.c_int; lib.sls_rollout_plan.argtypes = [vp, C.c_int] + planted + [C.c_int64, C.POINTER(vp)]
+    lib.sls_rollout_load.restype = C.c_int; lib.sls_rollout_load.argtypes = [vp, vp, vp]
+    lib.sls_rollout_set_plant.restype = C.c_int; lib.sls_rollout_set_plant.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
+    lib.sls_rollout_set_weights.restype = C.c_int; lib.sls_rollout_set_weights.argtypes = [vp, vp, vp, vp, C.c_int]
+    lib.sls_rollout_reset.restype = C.c_int; lib.sls_rollout_reset.argtypes = [vp, vp, vp]
+    lib.sls_rollout_run.restype = C.c_int; lib.sls_rollout_run.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
+    lib.sls_rollout_stats.restype = C.c_int; lib.sls_rollout_stats.argtypes = [vp, vp, vp, vp, vp]
+    lib.sls_rollout_fetch.restype = C.c_int; lib.sls_rollout_fetch.argtypes = [vp, vp, dp, dp, dp, dp]
+    lib.sls_rollout_info.restype = C.c_int; lib.sls_rollout_info.argtypes = [vp, i64p, i64p, i64p, i64p]
+    lib.sls_rollout_destroy.restype = None; lib.sls_rollout_destroy.argtypes = [vp]
     lib.sls_norms_plan.restype = C.c_int; lib.sls_norms_plan.argtypes = [vp, C.c_int] + masks + [dp, dp, C.c_int64, C.POINTER(vp)]
     lib.sls_norms_load.restype = C.c_int; lib.sls_norms_load.argtypes = [vp, vp, vp]
     lib.sls_norms_l1.restype = C.c_int; lib.sls_norms_l1.argtypes = [vp, vp, vp, vp, vp]
@@ -235,6 +248,11 @@ def load_library(path: str | None = None):
     lib.sls_debug_controller_tables.argtypes = masks + [i64p, i32p, i32p, i32p, i32p]
     lib.sls_debug_controller_host.restype = C.c_int
     lib.sls_debug_controller_host.argtypes = masks + [dp, C.c_int64, C.c_int64, dp, dp, dp]
+    lib.sls_debug_rollout_tables.restype = C.c_int
+    lib.sls_debug_rollout_tables.argtypes = planted + [i64p, i64p, i32p, i32p, i32p, i32p, i32p, i32p, C.POINTER(C.c_uint8), i32p]
+    lib.sls_debug_rollout_host.restype = C.c_int
+    lib.sls_debug_rollout_host.argtypes = planted + [dp, C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int64, i64p, C.c_int64, dp, C.c_int64,
+                                           dp, dp, dp, dp, dp, dp]
     lib.sls_debug_residual_host.restype = C.c_int
     lib.sls_debug_residual_host.argtypes = common + [dpp, dpp, dp, dp, dp, dp, i64p, dp, i64p, dp, i64p, i32p, C.c_int64]
     lib.sls_debug_objective_host.restype = C.c_int
