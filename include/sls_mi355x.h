@@ -622,6 +622,48 @@ int  sls_rollout_fetch(sls_rollout* r, void* hip_stream, double* x_now, double* 
 int  sls_rollout_info(const sls_rollout* r, int64_t* n_entries, int64_t* steps_done, int64_t* state_bytes, int64_t* plant_bytes);
 void sls_rollout_destroy(sls_rollout* r);
 
+/* ---- robust-stability margins of a resident Φ for an ensemble of plants (csrc/sls_margin.hip, csrc/sls_margin.h) ----
+ * For which plants of an ensemble is the loop GUARANTEED stable, and how much can it amplify a bounded disturbance?  A finite
+ * rollout cannot say; the defect of the achievability constraint can.  The controller of sls_controller_* on plant s,
+ * x_{k+1} = A⁽ˢ⁾·x_k + B2⁽ˢ⁾·u_k + w̃_k, reconstructs a disturbance that obeys exactly
+ *     ŵ_{k+1} = w̃_k − Σ_{τ=0..T−1} D⁽ˢ⁾[τ]·ŵ_{k−τ}
+ *     D⁽ˢ⁾[τ] = Φx[τ+1] − A⁽ˢ⁾·Φx[τ] − B2⁽ˢ⁾·Φu[τ]           (0-based slices; Φx[0] := I, Φx[T] := 0)
+ * and x = Φx ∗ ŵ, u = Φu ∗ ŵ.  The loop on plant s is internally stable when ‖D⁽ˢ⁾‖ < 1 in an induced norm,
+ *     ‖D‖_𝓛₁ = max_i Σ_τ Σ_j |D[τ][i,j]|       ‖D‖_𝓔₁ = max_j Σ_τ Σ_i |D[τ][i,j]|,
+ * and then ‖ŵ‖∞ ≤ ‖w̃‖∞ / (1 − ‖D‖_𝓛₁): every 𝓛₁ bound of sls_norms_l1 degrades by at most that factor.  A stored-false mask
+ * entry is 0 and is never read; no value of Sx[0] is ever read.  D has a pattern that depends on the non-zero patterns only
+ * (sls_margin.h); an entry's value is one fma chain over CSR row i of A⁽ˢ⁾, then of B2⁽ˢ⁾, in ascending position.
+ * sls_margin_plan: dims, P->A, P->B2 (patterns and initial values; P->B1 is checked and not used) and the masks are read.
+ *   Everything is allocated here: Φ by columns, the defect pattern by columns and by rows, the plant values per scenario as in
+ *   sls_rollout_plan (every scenario initialised from P) with the staging buffer of set_plant, a scratch of 8·n_defect·nscen B
+ *   that holds |D| of every pattern entry, and the result buffer of the fetch.  Codes and limits as sls_rollout_plan:
+ *   SLS_EUNSUPPORTED when (T+1)·Nx exceeds int32, nscen exceeds 65535·64 or the defect pattern exceeds int32; SLS_EINVAL for
+ *   nscen < 1 or a dev_slot out of range.
+ * sls_margin_load: d_values = Φ in the mask-order value array sls_plan_execute(packed = 0) fills (DEVICE), gathered by columns.
+ * sls_margin_set_plant: exactly the contract of sls_rollout_set_plant (CSC nzval order, NULL keeps, on_device, per_scenario; the
+ *   host path waits for its copy; THE VALUES ARE NOT VALIDATED).
+ * sls_margin_run: outputs on the DEVICE, each may be NULL, scenario innermost: d_row_l1 [Nx][nscen] = Σ_τ Σ_j |D⁽ˢ⁾[τ][i,j]|,
+ *   d_col_l1 [Nx][nscen] = Σ_τ Σ_i |D⁽ˢ⁾[τ][i,j]|, d_totals [2][nscen] = ‖D⁽ˢ⁾‖_𝓛₁ then ‖D⁽ˢ⁾‖_𝓔₁.  Three launches; the call
+ *   enqueues on `hip_stream` (NULL = null stream), allocates nothing and never waits.  A row or column without a pattern entry
+ *   reports exactly 0.0.  A NaN in Φ or in a scenario's plant values gives +inf in the sums it reaches in that scenario and
+ *   nothing elsewhere.  Every sum has one fixed order and one owner, no floating-point atomics: bit-identical from call to call,
+ *   and the numbers of scenario s do not depend on nscen, on the scenario's position, on the other scenarios' values or on how
+ *   the values arrived (shared or per scenario, host or device).  SLS_EINVAL before the first load; the object stays usable.
+ * sls_margin_fetch: the same passes into the object's buffer, copied to HOST arrays (each nullable); waits for the stream.
+ * sls_margin_info (each output nullable): stored-true Φ entries outside Sx[0], pattern entries of D, all device bytes of the
+ *   object (the scratch included) and those of the per-scenario plant values.
+ * The caller issues the calls of one object on one stream or orders them with events. */
+typedef struct sls_margin sls_margin;
+int  sls_margin_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx,
+                     const sls_csc_bool* Su, int64_t nscen, sls_margin** out);
+int  sls_margin_load(sls_margin* m, void* hip_stream, const double* d_values);
+int  sls_margin_set_plant(sls_margin* m, void* hip_stream, const double* A_nzval, const double* B2_nzval, int on_device,
+                          int per_scenario);
+int  sls_margin_run(sls_margin* m, void* hip_stream, double* d_row_l1, double* d_col_l1, double* d_totals);
+int  sls_margin_fetch(sls_margin* m, void* hip_stream, double* row_l1, double* col_l1, double* totals);
+int  sls_margin_info(const sls_margin* m, int64_t* n_entries, int64_t* n_defect, int64_t* device_bytes, int64_t* plant_bytes);
+void sls_margin_destroy(sls_margin* m);
+
 /* ---- closed-loop 𝓛₁ and 𝓗∞ norms of a resident Φ (csrc/sls_norms.hip) ----
  * The two norms SLS designs are judged by beside the 𝓗₂ cost.  Built from the masks alone, like the controller.  Rows are the Nx
  * state rows followed by the Nu input rows, N = Nx + Nu; for t = 0 … T−1 (0-based)

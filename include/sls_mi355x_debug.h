@@ -204,6 +204,29 @@ int sls_debug_rollout_host(const sls_dims* dims, const sls_plant* P, const sls_c
                            const double* values2, int64_t switch_step, double* x, double* u, double* x_end, double* cost,
                            double* peak_x, double* peak_u);
 
+/* The plan-time tables of the robust-stability margins (sls_margin_plan; csrc/sls_margin.cpp: build_margin_tables).  Φ by
+ * columns WITHOUT Sx[0]: phi_seg[Nx·T + 1] — column j, slice τ (0-based) is the segment [phi_seg[j·T + τ], phi_seg[j·T + τ + 1]) —
+ * phi_row (state row i, or Nx + m for input row m; ascending inside a segment) and phi_perm (the entry's index in the mask-order
+ * value array).  The defect pattern by columns: def_ptr[Nx + 1], def_key[d] = τ·Nx + i ascending inside a column, def_start[d] =
+ * the position of Φx[τ+1][i,j] in the Φ list or −1; by rows: row_ptr[Nx + 1] and row_perm, the positions d of row i's entries,
+ * ascending.  The plant by rows with the gather's source positions as in sls_debug_rollout_tables.  *n_entries: stored-true Φ
+ * entries outside Sx[0]; *n_defect.  Every output is nullable: call with the two counts first for the lengths.  Needs no device. */
+int sls_debug_margin_tables(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su, int64_t* n_entries,
+                            int64_t* n_defect, int32_t* phi_seg, int32_t* phi_row, int32_t* phi_perm, int32_t* def_ptr, int32_t* def_key,
+                            int32_t* def_start, int32_t* row_ptr, int32_t* row_perm, int32_t* A_ptr, int32_t* A_idx, int32_t* A_src,
+                            int32_t* B2_ptr, int32_t* B2_idx, int32_t* B2_src);
+
+/* Host twin of sls_margin_plan + load + set_plant + run (csrc/sls_margin.cpp: margin_host — the same tables, the same fma chain
+ * per entry (csrc/sls_margin.h: margin_entry), the sums in long double rounded once).  values: Φ in mask order (HOST); A_nzval /
+ * B2_nzval: CSC order, NULL keeps P's, [nnz] or [nnz][nscen] by per_scenario.  Outputs, each nullable: row_l1, col_l1
+ * [Nx][nscen], totals [2][nscen]; and the error model of each: row_n / col_n [Nx] = the number N of terms (start values and
+ * products) that went into the output, row_s / col_s [Nx][nscen] = the sum S of their absolute values; tot_n [2], tot_s
+ * [2][nscen] = the maxima over rows / columns.  A double evaluation in any order lies within 2·N·2⁻⁵³·S of the exact value.
+ * Needs no device. */
+int sls_debug_margin_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su, const double* values,
+                          int64_t nscen, const double* A_nzval, const double* B2_nzval, int per_scenario, double* row_l1, double* col_l1,
+                          double* totals, int64_t* row_n, int64_t* col_n, int64_t* tot_n, double* row_s, double* col_s, double* tot_s);
+
 #ifdef __cplusplus
 }
 #endif

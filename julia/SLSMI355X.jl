@@ -11,7 +11,7 @@
 module SLSMI355X
 
 using SparseArrays
-export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, update_weights!, weights, SLS_PLAN_WEIGHTS_UPDATABLE, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!, Rollout, set_plant!, set_weights!, run!, stats, Norms, l1, hinf, h2, covariance_pattern!, covariance
+export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, update_weights!, weights, SLS_PLAN_WEIGHTS_UPDATABLE, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!, Rollout, set_plant!, set_weights!, run!, stats, Margin, margins, Norms, l1, hinf, h2, covariance_pattern!, covariance
 
 const LIB = get(ENV, "SLS_MI355X_LIB", "libsls_mi355x.so")
 
@@ -316,6 +316,59 @@ function stats(r::Rollout; stream::Ptr{Cvoid}=C_NULL)
 end
 function Base.close(r::Rollout)
     r.handle != C_NULL && (ccall((:sls_rollout_destroy, LIB), Cvoid, (Ptr{Cvoid},), r.handle); r.handle = C_NULL)
+    return nothing
+end
+
+"""
+    m = Margin(ctx, P, [𝓢ₓ,𝓢ᵤ]; nscen=1, dev_slot=0)
+    load!(m, d_values);  set_plant!(m, A_nzval, B2_nzval; per_scenario=false);  row_l1, col_l1, l1, e1 = margins(m)
+
+`sls_margin_*`: robust-stability margins of the Φ on the device for an ensemble of plants — scenario `s` has its own values of `A`
+and `B₂` on `P`'s non-zero patterns (every scenario starts from `P`'s values).  `D⁽ˢ⁾[τ] = Φₓ[τ+1] − A⁽ˢ⁾Φₓ[τ] − B₂⁽ˢ⁾Φᵤ[τ]` (0-based
+slices, `Φₓ[0] := I`); `row_l1` and `col_l1` (`nscen × Nx`) are its absolute row and column sums, `l1[s] = ‖D⁽ˢ⁾‖_𝓛₁` and
+`e1[s] = ‖D⁽ˢ⁾‖_𝓔₁` their maxima: below 1 the loop on plant `s` is internally stable, and `‖ŵ‖∞ ≤ ‖w̃‖∞/(1 − l1[s])`.  `set_plant!`
+is the rollout's; `margins` waits.  `close(m)` frees it.  NOT EXECUTED in the build container, like the rest of this file.
+"""
+mutable struct Margin
+    handle::Ptr{Cvoid}
+    Nx::Int; Nu::Int; nscen::Int
+end
+function Margin(ctx::Ptr{Cvoid}, P, 𝓢::AbstractVector; nscen::Integer=1, dev_slot::Integer=0)
+    𝓢ₓ, 𝓢ᵤ = 𝓢
+    f64(M) = SparseMatrixCSC{Float64,Int}(M)
+    A, B1, B2 = f64(P.A), f64(P.B₁), f64(P.B₂)
+    Sx = [SparseMatrixCSC{Bool,Int}(S) for S in 𝓢ₓ];  Su = [SparseMatrixCSC{Bool,Int}(S) for S in 𝓢ᵤ]
+    mats = [csc(A), csc(B1), csc(B2)]
+    sx = [csc(S) for S in Sx];  su = [csc(S) for S in Su]
+    dims = Ref(Dims(P.Nx, P.Nu, P.Nz, P.Nw, length(Sx), 1, UInt32(0)))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve A B1 B2 mats Sx Su sx su begin
+        pm = pointer(mats)
+        plant = Ref(PlantPtrs(pm, pm + sizeof(CscF64), pm + 2sizeof(CscF64), Ptr{CscF64}(C_NULL), Ptr{CscF64}(C_NULL), Ptr{CscF64}(C_NULL)))
+        rc = ccall((:sls_margin_plan, LIB), Cint, (Ptr{Cvoid}, Cint, Ref{Dims}, Ref{PlantPtrs}, Ptr{CscBool}, Ptr{CscBool}, Int64, Ref{Ptr{Cvoid}}),
+                   ctx, dev_slot, dims, plant, sx, su, nscen, h)
+    end
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx)))
+    return Margin(h[], P.Nx, P.Nu, nscen)
+end
+load!(m::Margin, d_values::Ptr{Cvoid}; stream::Ptr{Cvoid}=C_NULL) =
+    _ctl_check(ccall((:sls_margin_load, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), m.handle, stream, d_values))
+function set_plant!(m::Margin, A_nzval::Union{Nothing,Array{Float64}}, B2_nzval::Union{Nothing,Array{Float64}}; per_scenario::Bool=false,
+                    stream::Ptr{Cvoid}=C_NULL)
+    GC.@preserve A_nzval B2_nzval begin                                 # host arrays: the call returns after they have been copied
+        _ctl_check(ccall((:sls_margin_set_plant, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint, Cint),
+                         m.handle, stream, _nzptr(A_nzval), _nzptr(B2_nzval), 0, per_scenario ? 1 : 0))
+    end
+end
+function margins(m::Margin; stream::Ptr{Cvoid}=C_NULL)
+    row, col = zeros(m.nscen, m.Nx), zeros(m.nscen, m.Nx)               # column-major (nscen, Nx) = the library's [Nx][nscen]
+    tot = zeros(m.nscen, 2)
+    _ctl_check(ccall((:sls_margin_fetch, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                     m.handle, stream, row, col, tot))
+    return row, col, tot[:, 1], tot[:, 2]
+end
+function Base.close(m::Margin)
+    m.handle != C_NULL && (ccall((:sls_margin_destroy, LIB), Cvoid, (Ptr{Cvoid},), m.handle); m.handle = C_NULL)
     return nothing
 end
 

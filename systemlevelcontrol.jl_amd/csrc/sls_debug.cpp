@@ -12,6 +12,7 @@
 
 #include "../../include/sls_mi355x.h"
 #include "../../include/sls_mi355x_debug.h"
+#include "sls_margin.h"
 #include "sls_norms.h"
 #include "sls_objective.h"
 #include "sls_plan.h"
@@ -445,6 +446,38 @@ int sls_debug_norms_cov_host(const sls_dims* dims, const sls_csc_bool* Sx, const
   int rc = build_norms_operator(dims, Sx, Su, Op, msg);
   if (!rc) rc = norms_cov_host(Op, values, cz, b, dims->index_base, npairs, pair_i, pair_j, cov, msg);
   if (rc) return fail(nullptr, rc, "sls_debug_norms_cov_host: " + msg);
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): the plan-time tables of sls_margin_plan (csrc/sls_margin.cpp).  Needs no device. */
+int sls_debug_margin_tables(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su, int64_t* n_entries,
+                            int64_t* n_defect, int32_t* phi_seg, int32_t* phi_row, int32_t* phi_perm, int32_t* def_ptr, int32_t* def_key,
+                            int32_t* def_start, int32_t* row_ptr, int32_t* row_perm, int32_t* A_ptr, int32_t* A_idx, int32_t* A_src,
+                            int32_t* B2_ptr, int32_t* B2_idx, int32_t* B2_src) {
+  MarginTables Tb;
+  std::string msg;
+  int rc = build_margin_tables(dims, P, Sx, Su, Tb, msg);
+  if (rc) return fail(nullptr, rc, "sls_debug_margin_tables: " + msg);
+  if (n_entries) *n_entries = (int64_t)Tb.phi_perm.size();
+  if (n_defect) *n_defect = (int64_t)Tb.def_key.size();
+  auto put = [](const std::vector<int32_t>& v, int32_t* o) { if (o) std::copy(v.begin(), v.end(), o); };
+  put(Tb.phi_seg, phi_seg); put(Tb.phi_row, phi_row); put(Tb.phi_perm, phi_perm);
+  put(Tb.def_ptr, def_ptr); put(Tb.def_key, def_key); put(Tb.def_start, def_start); put(Tb.row_ptr, row_ptr); put(Tb.row_perm, row_perm);
+  const FirOperator& F = Tb.R.F;
+  put(F.A.ptr, A_ptr); put(F.A.idx, A_idx); put(Tb.R.A_src, A_src); put(F.B2.ptr, B2_ptr); put(F.B2.idx, B2_idx); put(Tb.R.B2_src, B2_src);
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): host twin of plan + load + set_plant + run (csrc/sls_margin.cpp).  Needs no device. */
+int sls_debug_margin_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su, const double* values,
+                          int64_t nscen, const double* A_nzval, const double* B2_nzval, int per_scenario, double* row_l1, double* col_l1,
+                          double* totals, int64_t* row_n, int64_t* col_n, int64_t* tot_n, double* row_s, double* col_s, double* tot_s) {
+  MarginTables Tb;
+  std::string msg;
+  int rc = build_margin_tables(dims, P, Sx, Su, Tb, msg);
+  if (!rc) rc = margin_host(Tb, values, nscen, A_nzval, B2_nzval, per_scenario != 0, row_l1, col_l1, totals, row_n, col_n, tot_n, row_s, col_s,
+                            tot_s, msg);
+  if (rc) return fail(nullptr, rc, "sls_debug_margin_host: " + msg);
   return 0;
 }
 
