@@ -664,6 +664,37 @@ int  sls_margin_fetch(sls_margin* m, void* hip_stream, double* row_l1, double* c
 int  sls_margin_info(const sls_margin* m, int64_t* n_entries, int64_t* n_defect, int64_t* device_bytes, int64_t* plant_bytes);
 void sls_margin_destroy(sls_margin* m);
 
+/* ---- worst-case 𝓛₁ margin over a box of plants (csrc/sls_margin_box.h, csrc/sls_margin_box.hip), on the same object ----
+ * Every stored A[i,k], B2[i,m] of scenario s is known to ± a radius round the centre sls_margin_set_plant set.  Rows of D
+ * decouple and a row's absolute sum is convex in the row's coefficients, so max over the box of ‖D‖_𝓛₁ = max_i max_σ f_i(σ) over
+ * the 2^b_i sign patterns σ of the row's b_i uncertain coefficients: exact, and the plant that takes every row's arg-max vertex
+ * attains all of them at once.  The ACTIVE LIST of row i: its CSR entries of A, then of B2, whose radius is > 0 in at least one
+ * scenario; bit b of a vertex code set means centre + radius.  A row with more than 10 active coefficients reports the triangle
+ * bound Σ|d⁰| + Σ_b ρ_b·Σ|φ_b| (an upper bound; exact = 0, vertex −1).
+ * sls_margin_fetch_plant: the plant values as they are on the device — the centres of the box — to HOST arrays [nnz][nscen] in the
+ *   CSC nzval order (each nullable); waits for the stream.
+ * sls_margin_set_radius: HOST arrays in the CSC nzval order of A / B2, NULL = zeros, [nnz] or [nnz][nscen] by per_scenario.  A
+ *   radius that is negative or not finite: SLS_EINVAL, the object unchanged.  A setup call: builds the active lists on the host,
+ *   allocates (the first time) and waits for the device.  SLS_EUNSUPPORTED when Nx·nscen exceeds int32.
+ * sls_margin_box_run: outputs on the DEVICE, each may be NULL, scenario innermost: d_row_wc [Nx][nscen] = the row's largest
+ *   vertex sum, d_row_vertex [Nx][nscen] = its code (ties: the lowest; −1 for a bound row), d_totals [nscen] = max_i d_row_wc =
+ *   the worst ‖D‖_𝓛₁ of the box.  Two launches; enqueues on `hip_stream`, allocates nothing and never waits.  Sums in the one
+ *   order of sls_margin_run: with every radius 0, d_row_wc is its d_row_l1 bit for bit.  The numbers of scenario s do not depend
+ *   on nscen, its position, the other scenarios or the call (the codes do, through the shared active lists; so does which rows
+ *   are exact).  NaN as in sls_margin_run.  SLS_EINVAL before the first load or the first set_radius; the object stays usable.
+ * sls_margin_box_fetch: the same pass into the object's buffer, copied to HOST arrays (each nullable); row_exact [Nx].  Waits.
+ * sls_margin_box_worst_plant: box_fetch, then HOST arrays [nnz][nscen] in CSC nzval order (each nullable): centre ± radius by
+ *   every row's vertex, centre + radius in a bound row.  Fit for sls_margin_set_plant / sls_rollout_set_plant (per_scenario).
+ * sls_margin_box_info (each nullable; SLS_EINVAL before a set_radius): the longest active list, the rows on the bound path, the
+ *   vertex sums one scenario evaluates (Σ 2^b_i over the exact rows), the device bytes set_radius allocated. */
+int  sls_margin_fetch_plant(sls_margin* m, void* hip_stream, double* A_nzval, double* B2_nzval);
+int  sls_margin_set_radius(sls_margin* m, const double* A_rad, const double* B2_rad, int per_scenario);
+int  sls_margin_box_run(sls_margin* m, void* hip_stream, double* d_row_wc, int64_t* d_row_vertex, double* d_totals);
+int  sls_margin_box_fetch(sls_margin* m, void* hip_stream, double* row_wc, int64_t* row_vertex, uint8_t* row_exact, double* totals);
+int  sls_margin_box_worst_plant(sls_margin* m, void* hip_stream, double* A_nzval, double* B2_nzval);
+int  sls_margin_box_info(const sls_margin* m, int64_t* max_bits, int64_t* n_inexact_rows, int64_t* n_vertex_sums,
+                         int64_t* device_bytes);
+
 /* ---- closed-loop 𝓛₁ and 𝓗∞ norms of a resident Φ (csrc/sls_norms.hip) ----
  * The two norms SLS designs are judged by beside the 𝓗₂ cost.  Built from the masks alone, like the controller.  Rows are the Nx
  * state rows followed by the Nu input rows, N = Nx + Nu; for t = 0 … T−1 (0-based)

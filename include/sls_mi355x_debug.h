@@ -227,6 +227,26 @@ int sls_debug_margin_host(const sls_dims* dims, const sls_plant* P, const sls_cs
                           int64_t nscen, const double* A_nzval, const double* B2_nzval, int per_scenario, double* row_l1, double* col_l1,
                           double* totals, int64_t* row_n, int64_t* col_n, int64_t* tot_n, double* row_s, double* col_s, double* tot_s);
 
+/* Host twin of sls_margin_plan + load + set_plant + set_radius + box_run (csrc/sls_margin_box.cpp: margin_box_host — the same
+ * tables and active lists, d⁰ by margin_entry_signed, every vertex in long double rounded once).  Plant values as above; A_rad /
+ * B2_rad: CSC order, NULL = zeros, [nnz] or [nnz][nscen] by rad_per_scenario (SLS_EINVAL for a negative or non-finite radius).
+ * Outputs, each nullable: row_wc, row_vertex [Nx][nscen], row_exact [Nx], totals [nscen], the worst plant A_worst / B2_worst
+ * [nnz][nscen] (CSC order), the active lists act_ptr [Nx + 1] and act_ent [≤ nnz(A) + nnz(B2)] (coefficient c < nnz(A): CSR entry
+ * c of A, else CSR entry c − nnz(A) of B2), and the error model of row_wc: row_n [Nx] = the number N of terms (start values, centre
+ * products, ρ·φ products), row_s [Nx][nscen] = the sum S of their absolute values; a double evaluation of a vertex sum or of the
+ * triangle bound lies within 2·N·2⁻⁵³·S of its exact value.  Needs no device. */
+int sls_debug_margin_box_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su, const double* values,
+                              int64_t nscen, const double* A_nzval, const double* B2_nzval, int per_scenario, const double* A_rad,
+                              const double* B2_rad, int rad_per_scenario, double* row_wc, int64_t* row_vertex, uint8_t* row_exact,
+                              double* totals, int64_t* row_n, double* row_s, double* A_worst, double* B2_worst, int32_t* act_ptr,
+                              int32_t* act_ent);
+/* fabs(margin_entry_signed) against margin_entry (csrc/sls_margin_box.h, csrc/sls_margin.h) on every pattern entry and scenario of
+ * the plant given as above: *n_entries = the entries compared, *n_mismatch = those whose 64 bits differ, *n_negative = those whose
+ * signed value is below 0 (so that the comparison is not empty).  Needs no device. */
+int sls_debug_margin_entry_signed(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                                  const double* values, int64_t nscen, const double* A_nzval, const double* B2_nzval, int per_scenario,
+                                  int64_t* n_entries, int64_t* n_mismatch, int64_t* n_negative);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@
 module SLSMI355X
 
 using SparseArrays
-export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, update_weights!, weights, SLS_PLAN_WEIGHTS_UPDATABLE, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!, Rollout, set_plant!, set_weights!, run!, stats, Margin, margins, Norms, l1, hinf, h2, covariance_pattern!, covariance
+export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, update_weights!, weights, SLS_PLAN_WEIGHTS_UPDATABLE, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!, Rollout, set_plant!, set_weights!, run!, stats, Margin, margins, set_radius!, box_margins, worst_plant, Norms, l1, hinf, h2, covariance_pattern!, covariance
 
 const LIB = get(ENV, "SLS_MI355X_LIB", "libsls_mi355x.so")
 
@@ -332,6 +332,7 @@ is the rollout's; `margins` waits.  `close(m)` frees it.  NOT EXECUTED in the bu
 mutable struct Margin
     handle::Ptr{Cvoid}
     Nx::Int; Nu::Int; nscen::Int
+    nnzA::Int; nnzB2::Int
 end
 function Margin(ctx::Ptr{Cvoid}, P, 𝓢::AbstractVector; nscen::Integer=1, dev_slot::Integer=0)
     𝓢ₓ, 𝓢ᵤ = 𝓢
@@ -349,7 +350,7 @@ function Margin(ctx::Ptr{Cvoid}, P, 𝓢::AbstractVector; nscen::Integer=1, dev_
                    ctx, dev_slot, dims, plant, sx, su, nscen, h)
     end
     rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx)))
-    return Margin(h[], P.Nx, P.Nu, nscen)
+    return Margin(h[], P.Nx, P.Nu, nscen, nnz(A), nnz(B2))
 end
 load!(m::Margin, d_values::Ptr{Cvoid}; stream::Ptr{Cvoid}=C_NULL) =
     _ctl_check(ccall((:sls_margin_load, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), m.handle, stream, d_values))
@@ -366,6 +367,35 @@ function margins(m::Margin; stream::Ptr{Cvoid}=C_NULL)
     _ctl_check(ccall((:sls_margin_fetch, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
                      m.handle, stream, row, col, tot))
     return row, col, tot[:, 1], tot[:, 2]
+end
+"""
+    set_radius!(m, A_rad, B2_rad; per_scenario=false);  row_wc, vertex, exact, l1_wc = box_margins(m);  A_nzval, B2_nzval = worst_plant(m)
+
+The worst case over a box of plants (`sls_margin_set_radius`, `sls_margin_box_*`): every stored `A[i,k]`, `B₂[i,m]` is known to ± a
+radius (host arrays in `nzval` order, `nothing` = zeros, `nnz` values or `nscen × nnz`) round the centre `set_plant!` set.  `row_wc`
+(`nscen × Nx`) is the largest absolute row sum of `D` over the box, `vertex` the sign pattern that attains it (bit `b` set: centre +
+radius of the row's `b`-th active coefficient; `-1`: a row with more than 10 active coefficients, which reports the triangle bound and
+has `exact` false), `l1_wc[s]` the worst `‖D‖_𝓛₁`: below 1 the loop is stable on every plant of the box.  `worst_plant` returns the
+plant (`nscen × nnz` each) that takes every row's vertex, fit for `set_plant!(…; per_scenario=true)` here and on a `Rollout`.
+`set_radius!` is a setup call (allocates, waits); the others wait for `stream`.  NOT EXECUTED in the build container.
+"""
+function set_radius!(m::Margin, A_rad::Union{Nothing,Array{Float64}}, B2_rad::Union{Nothing,Array{Float64}}; per_scenario::Bool=false)
+    GC.@preserve A_rad B2_rad begin
+        _ctl_check(ccall((:sls_margin_set_radius, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint),
+                         m.handle, _nzptr(A_rad), _nzptr(B2_rad), per_scenario ? 1 : 0))
+    end
+end
+function box_margins(m::Margin; stream::Ptr{Cvoid}=C_NULL)
+    row, ver = zeros(m.nscen, m.Nx), zeros(Int64, m.nscen, m.Nx)        # column-major (nscen, Nx) = the library's [Nx][nscen]
+    ex, tot = zeros(UInt8, m.Nx), zeros(m.nscen)
+    _ctl_check(ccall((:sls_margin_box_fetch, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Ptr{UInt8}, Ptr{Float64}),
+                     m.handle, stream, row, ver, ex, tot))
+    return row, ver, ex .!= 0, tot
+end
+function worst_plant(m::Margin; stream::Ptr{Cvoid}=C_NULL)
+    A, B2 = zeros(m.nscen, m.nnzA), zeros(m.nscen, m.nnzB2)             # column-major (nscen, nnz) = the library's [nnz][nscen]
+    _ctl_check(ccall((:sls_margin_box_worst_plant, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), m.handle, stream, A, B2))
+    return A, B2
 end
 function Base.close(m::Margin)
     m.handle != C_NULL && (ccall((:sls_margin_destroy, LIB), Cvoid, (Ptr{Cvoid},), m.handle); m.handle = C_NULL)

@@ -98,6 +98,7 @@ EXPORTS = [
     "sls_rollout_stats", "sls_rollout_fetch", "sls_rollout_info", "sls_rollout_destroy",
     "sls_margin_plan", "sls_margin_load", "sls_margin_set_plant", "sls_margin_run", "sls_margin_fetch", "sls_margin_info",
     "sls_margin_destroy",
+    "sls_margin_fetch_plant", "sls_margin_set_radius", "sls_margin_box_run", "sls_margin_box_fetch", "sls_margin_box_worst_plant", "sls_margin_box_info",
     "sls_norms_plan", "sls_norms_load", "sls_norms_l1", "sls_norms_hinf", "sls_norms_fetch_l1", "sls_norms_fetch_hinf", "sls_norms_info",
     "sls_norms_destroy", "sls_norms_h2", "sls_norms_fetch_h2", "sls_norms_cov_pattern", "sls_norms_cov", "sls_norms_fetch_cov",
 ]
@@ -231,6 +232,12 @@ def load_library(path: str | None = None):
     lib.sls_margin_fetch.restype = C.c_int; lib.sls_margin_fetch.argtypes = [vp, vp, dp, dp, dp]
     lib.sls_margin_info.restype = C.c_int; lib.sls_margin_info.argtypes = [vp, i64p, i64p, i64p, i64p]
     lib.sls_margin_destroy.restype = None; lib.sls_margin_destroy.argtypes = [vp]
+    lib.sls_margin_fetch_plant.restype = C.c_int; lib.sls_margin_fetch_plant.argtypes = [vp, vp, dp, dp]
+    lib.sls_margin_set_radius.restype = C.c_int; lib.sls_margin_set_radius.argtypes = [vp, dp, dp, C.c_int]
+    lib.sls_margin_box_run.restype = C.c_int; lib.sls_margin_box_run.argtypes = [vp, vp, vp, vp, vp]
+    lib.sls_margin_box_fetch.restype = C.c_int; lib.sls_margin_box_fetch.argtypes = [vp, vp, dp, i64p, C.POINTER(C.c_uint8), dp]
+    lib.sls_margin_box_worst_plant.restype = C.c_int; lib.sls_margin_box_worst_plant.argtypes = [vp, vp, dp, dp]
+    lib.sls_margin_box_info.restype = C.c_int; lib.sls_margin_box_info.argtypes = [vp, i64p, i64p, i64p, i64p]
     lib.sls_norms_plan.restype = C.c_int; lib.sls_norms_plan.argtypes = [vp, C.c_int] + masks + [dp, dp, C.c_int64, C.POINTER(vp)]
     lib.sls_norms_load.restype = C.c_int; lib.sls_norms_load.argtypes = [vp, vp, vp]
     lib.sls_norms_l1.restype = C.c_int; lib.sls_norms_l1.argtypes = [vp, vp, vp, vp, vp]
@@ -263,6 +270,11 @@ def load_library(path: str | None = None):
     lib.sls_debug_margin_tables.argtypes = planted + [i64p, i64p] + [i32p] * 14
     lib.sls_debug_margin_host.restype = C.c_int
     lib.sls_debug_margin_host.argtypes = planted + [dp, C.c_int64, dp, dp, C.c_int, dp, dp, dp, i64p, i64p, i64p, dp, dp, dp]
+    lib.sls_debug_margin_box_host.restype = C.c_int
+    lib.sls_debug_margin_box_host.argtypes = planted + [dp, C.c_int64, dp, dp, C.c_int, dp, dp, C.c_int, dp, i64p, C.POINTER(C.c_uint8), dp,
+                                                        i64p, dp, dp, dp, i32p, i32p]
+    lib.sls_debug_margin_entry_signed.restype = C.c_int
+    lib.sls_debug_margin_entry_signed.argtypes = planted + [dp, C.c_int64, dp, dp, C.c_int, i64p, i64p, i64p]
     lib.sls_debug_rollout_host.restype = C.c_int
     lib.sls_debug_rollout_host.argtypes = planted + [dp, C.c_int64, dp, dp, C.c_int, dp, dp, dp, dp, C.c_int64, i64p, C.c_int64, dp, C.c_int64,
                                            dp, dp, dp, dp, dp, dp]

@@ -13,6 +13,7 @@
 #include "../../include/sls_mi355x.h"
 #include "../../include/sls_mi355x_debug.h"
 #include "sls_margin.h"
+#include "sls_margin_box.h"
 #include "sls_norms.h"
 #include "sls_objective.h"
 #include "sls_plan.h"
@@ -478,6 +479,40 @@ int sls_debug_margin_host(const sls_dims* dims, const sls_plant* P, const sls_cs
   if (!rc) rc = margin_host(Tb, values, nscen, A_nzval, B2_nzval, per_scenario != 0, row_l1, col_l1, totals, row_n, col_n, tot_n, row_s, col_s,
                             tot_s, msg);
   if (rc) return fail(nullptr, rc, "sls_debug_margin_host: " + msg);
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): host twin of plan + load + set_plant + set_radius + box_run (csrc/sls_margin_box.cpp).
+   Needs no device. */
+int sls_debug_margin_box_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su, const double* values,
+                              int64_t nscen, const double* A_nzval, const double* B2_nzval, int per_scenario, const double* A_rad,
+                              const double* B2_rad, int rad_per_scenario, double* row_wc, int64_t* row_vertex, uint8_t* row_exact,
+                              double* totals, int64_t* row_n, double* row_s, double* A_worst, double* B2_worst, int32_t* act_ptr,
+                              int32_t* act_ent) {
+  MarginTables Tb;
+  std::string msg;
+  int rc = build_margin_tables(dims, P, Sx, Su, Tb, msg);
+  if (!rc) rc = margin_box_host(Tb, values, nscen, A_nzval, B2_nzval, per_scenario != 0, A_rad, B2_rad, rad_per_scenario != 0, row_wc, row_vertex,
+                                row_exact, totals, row_n, row_s, A_worst, B2_worst, msg);
+  if (!rc && (act_ptr || act_ent)) {
+    MarginBoxLists L;
+    rc = build_margin_box_lists(Tb.R.F.A.ptr, Tb.R.A_src, Tb.R.F.B2.ptr, Tb.R.B2_src, nscen, A_rad, B2_rad, rad_per_scenario != 0, L, msg);
+    if (!rc && act_ptr) std::copy(L.act_ptr.begin(), L.act_ptr.end(), act_ptr);
+    if (!rc && act_ent) std::copy(L.act_ent.begin(), L.act_ent.end(), act_ent);
+  }
+  if (rc) return fail(nullptr, rc, "sls_debug_margin_box_host: " + msg);
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): fabs(margin_entry_signed) against margin_entry, bit for bit.  Needs no device. */
+int sls_debug_margin_entry_signed(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                                  const double* values, int64_t nscen, const double* A_nzval, const double* B2_nzval, int per_scenario,
+                                  int64_t* n_entries, int64_t* n_mismatch, int64_t* n_negative) {
+  MarginTables Tb;
+  std::string msg;
+  int rc = build_margin_tables(dims, P, Sx, Su, Tb, msg);
+  if (!rc) rc = margin_entry_signed_check(Tb, values, nscen, A_nzval, B2_nzval, per_scenario != 0, n_entries, n_mismatch, n_negative, msg);
+  if (rc) return fail(nullptr, rc, "sls_debug_margin_entry_signed: " + msg);
   return 0;
 }
 

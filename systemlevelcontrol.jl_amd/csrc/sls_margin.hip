@@ -14,7 +14,8 @@
 //                              makes scenario s independent of nscen.
 //   margin_totals_kernel       one wave per chunk of 8 scenarios: the two maxima.
 // load and the device path of set_plant are one gather launch each.  load, set_plant (device path), run allocate nothing and
-// never wait.
+// never wait.  The worst case over a box of plants (sls_margin_set_radius, sls_margin_box_*; semantics in sls_margin_box.h, kernels
+// in sls_margin_box.hip) lives on the same object: set_radius is a setup call, box_run enqueues two launches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +26,7 @@
 #include "../../include/sls_mi355x.h"
 #include "sls_internal.h"
 #include "sls_margin.h"
+#include "sls_margin_box.h"
 
 namespace {
 
@@ -144,6 +146,16 @@ struct sls_margin {
   int scn = 1;                         // scenario slots per wave: smallest power of two ≥ nscen, at most 64
   size_t device_bytes = 0, plant_bytes = 0;
   bool loaded = false;
+  // the box of sls_margin_set_radius (sls_margin_box.h): the plant by rows stays on the host for the active lists and the worst
+  // plant; the second arena (active lists, radii, results) is allocated by the first set_radius
+  std::vector<int32_t> h_A_ptr, h_A_src, h_B2_ptr, h_B2_src;
+  sls::MarginBoxLists box;
+  sls::MarginBoxView bview{};
+  void* box_arena = nullptr;
+  double *d_box_wc = nullptr, *d_box_tot = nullptr;
+  long long* d_box_vertex = nullptr;
+  size_t box_bytes = 0;
+  bool has_radius = false;
 };
 
 using namespace sls;
@@ -201,6 +213,7 @@ int sls_margin_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_
   M->ctx = ctx; M->dev = ctx->devs[dev_slot];
   M->n_entries = (int64_t)Tb.phi_perm.size(); M->n_defect = (int64_t)Tb.def_key.size();
   M->nnzA = (int64_t)F.A.val.size(); M->nnzB = (int64_t)F.B2.val.size();
+  M->h_A_ptr = F.A.ptr; M->h_A_src = Tb.R.A_src; M->h_B2_ptr = F.B2.ptr; M->h_B2_src = Tb.R.B2_src;
   hipError_t e = hipSetDevice(M->dev);
   if (e != hipSuccess) { delete M; return hipfail(ctx, e, "hipSetDevice"); }
   // one arena: uploaded tables first, then the buffers the object owns
@@ -337,10 +350,138 @@ int sls_margin_info(const sls_margin* M, int64_t* n_entries, int64_t* n_defect, 
   return 0;
 }
 
+/* ---- the worst case over a box of plants (sls_margin_box.h; kernels in sls_margin_box.hip) ---- */
+
+int sls_margin_fetch_plant(sls_margin* M, void* hip_stream, double* A_nzval, double* B2_nzval) {
+  if (!M) return fail(nullptr, SLS_EINVAL, "sls_margin_fetch_plant: null margin");
+  sls_ctx* ctx = M->ctx;
+  HIPCHK(ctx, hipSetDevice(M->dev));
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  const size_t ns = (size_t)M->kp.v.nscen;
+  double* out[2] = {A_nzval, B2_nzval};
+  const double* d_val[2] = {M->d_A_val, M->d_B2_val};
+  const std::vector<int32_t>* src[2] = {&M->h_A_src, &M->h_B2_src};
+  std::vector<double> csr;
+  for (int m = 0; m < 2; ++m) {
+    if (!out[m] || src[m]->empty()) continue;
+    csr.resize(src[m]->size() * ns);
+    HIPCHK(ctx, hipMemcpyAsync(csr.data(), d_val[m], csr.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    for (size_t e = 0; e < src[m]->size(); ++e) std::copy(csr.begin() + e * ns, csr.begin() + (e + 1) * ns, out[m] + (size_t)(*src[m])[e] * ns);
+  }
+  return 0;
+}
+
+int sls_margin_set_radius(sls_margin* M, const double* A_rad, const double* B2_rad, int per_scenario) {
+  if (!M) return fail(nullptr, SLS_EINVAL, "sls_margin_set_radius: null margin");
+  sls_ctx* ctx = M->ctx;
+  const long long ns = M->kp.v.nscen, Nx = M->kp.v.Nx;
+  if (Nx * ns > 0x7fffffffLL) return fail(ctx, SLS_EUNSUPPORTED, "sls_margin_set_radius: Nx·nscen exceeds the row pass's grid");
+  MarginBoxLists L;
+  std::string msg;
+  int rc = build_margin_box_lists(M->h_A_ptr, M->h_A_src, M->h_B2_ptr, M->h_B2_src, ns, A_rad, B2_rad, per_scenario != 0, L, msg);
+  if (rc) return fail(ctx, rc, "sls_margin_set_radius: " + msg);
+  HIPCHK(ctx, hipSetDevice(M->dev));
+  auto al = [](size_t b) { return (std::max<size_t>(b, 16) + 255) / 256 * 256; };
+  const size_t b_ptr = al((size_t)(Nx + 1) * 4), b_ent = al((size_t)(M->nnzA + M->nnzB) * 4), b_ra = al((size_t)(M->nnzA * ns) * 8);
+  const size_t b_rb = al((size_t)(M->nnzB * ns) * 8), b_rows = al((size_t)(Nx * ns) * 8), b_tot = al((size_t)ns * 8);
+  if (!M->box_arena) {                                         // sizes depend on the plan alone: allocated once
+    void* a = nullptr;
+    const size_t total = b_ptr + b_ent + b_ra + b_rb + 2 * b_rows + b_tot;
+    HIPCHK(ctx, hipMalloc(&a, total));
+    M->box_arena = a; M->box_bytes = total;
+    unsigned char* base = static_cast<unsigned char*>(a);
+    M->bview.act_ptr = reinterpret_cast<const int32_t*>(base); base += b_ptr;
+    M->bview.act_ent = reinterpret_cast<const int32_t*>(base); base += b_ent;
+    M->bview.A_rad = reinterpret_cast<const double*>(base); base += b_ra;
+    M->bview.B2_rad = reinterpret_cast<const double*>(base); base += b_rb;
+    M->d_box_wc = reinterpret_cast<double*>(base); base += b_rows;
+    M->d_box_vertex = reinterpret_cast<long long*>(base); base += b_rows;
+    M->d_box_tot = reinterpret_cast<double*>(base);
+    M->bview.nnzA = (int32_t)M->nnzA;
+  }
+  HIPCHK(ctx, hipDeviceSynchronize());                         // a run in flight still reads the lists
+  struct Up { const void* dst; const void* src; size_t bytes; };
+  const Up ups[4] = {{M->bview.act_ptr, L.act_ptr.data(), L.act_ptr.size() * 4}, {M->bview.act_ent, L.act_ent.data(), L.act_ent.size() * 4},
+                     {M->bview.A_rad, L.A_rad.data(), L.A_rad.size() * 8}, {M->bview.B2_rad, L.B2_rad.data(), L.B2_rad.size() * 8}};
+  for (const Up& u : ups)
+    if (u.bytes) HIPCHK(ctx, hipMemcpy(const_cast<void*>(u.dst), u.src, u.bytes, hipMemcpyHostToDevice));
+  M->box = std::move(L);
+  M->has_radius = true;
+  return 0;
+}
+
+namespace {
+int box_ready(sls_margin* M, const char* who) {
+  if (!M->loaded) return fail(M->ctx, SLS_EINVAL, std::string(who) + ": no Φ loaded (sls_margin_load first)");
+  if (!M->has_radius) return fail(M->ctx, SLS_EINVAL, std::string(who) + ": no radii set (sls_margin_set_radius first)");
+  return 0;
+}
+int enqueue_box(sls_margin* M, hipStream_t st, double* d_wc, long long* d_vertex, double* d_tot) {
+  const MarginBoxParams bp{M->kp, M->bview};
+  HIPCHK(M->ctx, launch_margin_box(bp, st, d_wc, d_vertex, d_tot));
+  return 0;
+}
+}  // namespace
+
+int sls_margin_box_run(sls_margin* M, void* hip_stream, double* d_row_wc, int64_t* d_row_vertex, double* d_totals) {
+  if (!M) return fail(nullptr, SLS_EINVAL, "sls_margin_box_run: null margin");
+  int rc = box_ready(M, "sls_margin_box_run");
+  if (rc) return rc;
+  HIPCHK(M->ctx, hipSetDevice(M->dev));
+  static_assert(sizeof(long long) == sizeof(int64_t), "vertex codes are int64");
+  return enqueue_box(M, static_cast<hipStream_t>(hip_stream), d_row_wc ? d_row_wc : M->d_box_wc,
+                     d_row_vertex ? reinterpret_cast<long long*>(d_row_vertex) : M->d_box_vertex, d_totals ? d_totals : M->d_box_tot);
+}
+
+int sls_margin_box_fetch(sls_margin* M, void* hip_stream, double* row_wc, int64_t* row_vertex, uint8_t* row_exact, double* totals) {
+  if (!M) return fail(nullptr, SLS_EINVAL, "sls_margin_box_fetch: null margin");
+  sls_ctx* ctx = M->ctx;
+  int rc = box_ready(M, "sls_margin_box_fetch");
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(M->dev));
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  const size_t rows = (size_t)(M->kp.v.Nx * M->kp.v.nscen) * 8;
+  if ((rc = enqueue_box(M, st, M->d_box_wc, M->d_box_vertex, M->d_box_tot))) return rc;
+  if (row_wc && rows) HIPCHK(ctx, hipMemcpyAsync(row_wc, M->d_box_wc, rows, hipMemcpyDeviceToHost, st));
+  if (row_vertex && rows) HIPCHK(ctx, hipMemcpyAsync(row_vertex, M->d_box_vertex, rows, hipMemcpyDeviceToHost, st));
+  if (totals) HIPCHK(ctx, hipMemcpyAsync(totals, M->d_box_tot, (size_t)M->kp.v.nscen * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  if (row_exact) std::copy(M->box.exact.begin(), M->box.exact.end(), row_exact);
+  return 0;
+}
+
+int sls_margin_box_worst_plant(sls_margin* M, void* hip_stream, double* A_nzval, double* B2_nzval) {
+  if (!M) return fail(nullptr, SLS_EINVAL, "sls_margin_box_worst_plant: null margin");
+  sls_ctx* ctx = M->ctx;
+  const long long ns = M->kp.v.nscen, Nx = M->kp.v.Nx;
+  std::vector<int64_t> vertex((size_t)(Nx * ns));
+  int rc = sls_margin_box_fetch(M, hip_stream, nullptr, vertex.data(), nullptr, nullptr);
+  if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  std::vector<double> A_cen((size_t)(M->nnzA * ns)), B2_cen((size_t)(M->nnzB * ns));
+  if (!A_cen.empty()) HIPCHK(ctx, hipMemcpyAsync(A_cen.data(), M->d_A_val, A_cen.size() * 8, hipMemcpyDeviceToHost, st));
+  if (!B2_cen.empty()) HIPCHK(ctx, hipMemcpyAsync(B2_cen.data(), M->d_B2_val, B2_cen.size() * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  margin_box_worst_plant(M->h_A_ptr, M->h_A_src, M->h_B2_ptr, M->h_B2_src, M->box, A_cen.data(), B2_cen.data(), vertex.data(), A_nzval, B2_nzval);
+  return 0;
+}
+
+int sls_margin_box_info(const sls_margin* M, int64_t* max_bits, int64_t* n_inexact_rows, int64_t* n_vertex_sums, int64_t* device_bytes) {
+  if (!M) return fail(nullptr, SLS_EINVAL, "sls_margin_box_info: null margin");
+  if (!M->has_radius) return fail(M->ctx, SLS_EINVAL, "sls_margin_box_info: no radii set (sls_margin_set_radius first)");
+  if (max_bits) *max_bits = M->box.max_bits;
+  if (n_inexact_rows) *n_inexact_rows = M->box.n_inexact_rows;
+  if (n_vertex_sums) *n_vertex_sums = M->box.n_vertex_sums;
+  if (device_bytes) *device_bytes = (int64_t)M->box_bytes;
+  return 0;
+}
+
 void sls_margin_destroy(sls_margin* M) {
   if (!M) return;
   (void)hipSetDevice(M->dev);
   if (M->arena) (void)hipFree(M->arena);
+  if (M->box_arena) (void)hipFree(M->box_arena);
   delete M;
 }
 
