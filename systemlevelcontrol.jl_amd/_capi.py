@@ -328,6 +328,47 @@ def check(rc: int, ctx=None):
 
 
 # ---------------------------------------------------------------------------
+# device arguments of the objects that evaluate a resident Φ
+# ---------------------------------------------------------------------------
+def _is_tensor(a):
+    t = sys.modules.get("torch")
+    return t is not None and isinstance(a, t.Tensor)
+
+
+def _dev_ptr(a, n, what):
+    """device pointer of a torch tensor (checked: float64, contiguous, on a GPU, n elements) or a raw pointer / None"""
+    if _is_tensor(a):
+        t = sys.modules["torch"]
+        if not a.is_cuda or a.dtype != t.float64 or not a.is_contiguous() or a.numel() != n:
+            raise ValueError(f"{what} must be a contiguous float64 device tensor of {n} elements")
+        return a.data_ptr()
+    return a
+
+
+def plant_value_args(A, B2, nnz_A, nnz_B2, nscen, per_scenario):
+    """The plant arguments of a `set_plant`: (A pointer, B2 pointer, on_device, arrays to keep alive during the call), or None
+    when both are None.  Each of A / B2: None, a host array, or a device tensor; nnz values, or nnz·nscen with per_scenario."""
+    given = [(name, v, nnz) for name, v, nnz in (("A", A, nnz_A), ("B2", B2, nnz_B2)) if v is not None]
+    if not given:
+        return None
+    dev = [_is_tensor(v) for _, v, _ in given]
+    if any(dev) != all(dev):
+        raise ValueError("set_plant: A and B2 must both be host arrays or both be device tensors")
+    ptrs, keep = {"A": None, "B2": None}, []
+    for name, v, nnz in given:
+        n = nnz * (nscen if per_scenario else 1)
+        if dev[0]:
+            ptrs[name] = _dev_ptr(v, n, f"set_plant: {name}")
+        else:
+            a = np.ascontiguousarray(v, dtype=np.float64)
+            if a.size != n:
+                raise ValueError(f"set_plant: {name} has {a.size} values, expected {n}")
+            keep.append(a)
+            ptrs[name] = a.ctypes.data
+    return ptrs["A"], ptrs["B2"], int(dev[0]), keep
+
+
+# ---------------------------------------------------------------------------
 # marshalling helpers: keep the numpy arrays alive next to the ctypes structs
 # ---------------------------------------------------------------------------
 class Marshalled:

@@ -12,11 +12,11 @@ The step runs in libsls_mi355x.so (sls_controller_*: one HIP kernel per step); t
 from __future__ import annotations
 
 import ctypes as C
-import sys
 
 import numpy as np
 
 from . import _capi
+from ._capi import _dev_ptr, _is_tensor
 
 
 def _dims_of(P_or_dims):
@@ -25,16 +25,6 @@ def _dims_of(P_or_dims):
         return int(P_or_dims.Nx), int(P_or_dims.Nu)
     Nx, Nu = P_or_dims
     return int(Nx), int(Nu)
-
-
-def _ptr(a, n, what):
-    """device pointer of a torch tensor (checked: float64, contiguous, on a GPU, n elements) or a raw pointer / None"""
-    t = sys.modules.get("torch")
-    if t is not None and isinstance(a, t.Tensor):
-        if not a.is_cuda or a.dtype != t.float64 or not a.is_contiguous() or a.numel() != n:
-            raise ValueError(f"{what} must be a contiguous float64 device tensor of {n} elements")
-        return a.data_ptr()
-    return a
 
 
 class Controller:
@@ -67,8 +57,7 @@ class Controller:
 
     def load(self, d_values, stream=None):
         """Φ from the mask-order device array `Plan.execute(packed=False)` fills (tensor or pointer); β, the history and k stay."""
-        t = sys.modules.get("torch")
-        if t is not None and isinstance(d_values, t.Tensor):
+        if _is_tensor(d_values):
             d_values = d_values.data_ptr()
         _capi.check(self._lib.sls_controller_load(self.handle, stream, d_values), self.ctx.handle)
 
@@ -85,8 +74,8 @@ class Controller:
                 import torch
                 self._u = torch.empty((self.Nu, self.nscen), dtype=torch.float64, device=torch.device("cuda", self.device))
             u = self._u
-        _capi.check(self._lib.sls_controller_step(self.handle, stream, _ptr(x, self.Nx * self.nscen, "x"),
-                                                  _ptr(u, self.Nu * self.nscen, "u"), _ptr(what, self.Nx * self.nscen, "what")),
+        _capi.check(self._lib.sls_controller_step(self.handle, stream, _dev_ptr(x, self.Nx * self.nscen, "x"),
+                                                  _dev_ptr(u, self.Nu * self.nscen, "u"), _dev_ptr(what, self.Nx * self.nscen, "what")),
                     self.ctx.handle)
         return u
 

@@ -24,7 +24,9 @@
 
 #include "../../include/sls_mi355x.h"
 #include "sls_internal.h"
+#include "sls_object.h"
 #include "sls_symbolic.h"
+#include "sls_wave_util.h"
 
 namespace {
 
@@ -40,20 +42,6 @@ struct LoopParams {
 };
 
 constexpr int kWavesPerBlock = 4;
-
-__global__ void gather_rows_kernel(const double* __restrict__ values, const int32_t* __restrict__ perm, long long n,
-                                   double* __restrict__ vals) {
-  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) vals[k] = values[perm[k]];
-}
-
-// sum over the lanes that share `lane % SCN` (the scenario slot); result in every lane of the group
-template <int SCN>
-__device__ __forceinline__ double entry_lanes_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= SCN; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // lanes = (entry slot le, scenario slot ls): lane = le·SCN + ls.  SCN scenarios share a wave; 64/SCN entries in flight.
 template <int SCN>
@@ -84,12 +72,12 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) closed_loop_step_kernel(L
   };
   if (row >= p.Nx) {                                           // actuator that drives no state: u only
     const int j = p.orphan[row - p.Nx];
-    const double uj = entry_lanes_sum<SCN>(fir(p.u_ptr[j], p.u_ptr[j + 1]));
+    const double uj = sls::lane_group_sum<SCN>(fir(p.u_ptr[j], p.u_ptr[j + 1]));
     if (le == 0 && live) p.u[((long long)(k - 1) * p.Nu + j) * ns + scen] = uj;
     return;
   }
   const int i = row;
-  const double beta = entry_lanes_sum<SCN>(fir(p.beta_ptr[i], p.beta_ptr[i + 1]));
+  const double beta = sls::lane_group_sum<SCN>(fir(p.beta_ptr[i], p.beta_ptr[i + 1]));
   double part = 0.0;                                           // A·x[k−1] + B1·w[k−1], this lane's share
   const double* __restrict__ xprev = p.x + (long long)(k - 1) * p.Nx * ns + sc;
   for (int e = p.A_ptr[i] + le; e < p.A_ptr[i + 1]; e += NE) part = fma(p.A_val[e], xprev[(long long)p.A_idx[e] * ns], part);
@@ -97,10 +85,10 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) closed_loop_step_kernel(L
     const double* __restrict__ wprev = p.w + (long long)(k - 1) * p.Nw * ns + sc;
     for (int e = p.B1_ptr[i] + le; e < p.B1_ptr[i + 1]; e += NE) part = fma(p.B1_val[e], wprev[(long long)p.B1_idx[e] * ns], part);
   }
-  double xi = entry_lanes_sum<SCN>(part);
+  double xi = sls::lane_group_sum<SCN>(part);
   for (int e = p.B2_ptr[i]; e < p.B2_ptr[i + 1]; ++e) {
     const int j = p.B2_idx[e];
-    const double uj = entry_lanes_sum<SCN>(fir(p.u_ptr[j], p.u_ptr[j + 1]));
+    const double uj = sls::lane_group_sum<SCN>(fir(p.u_ptr[j], p.u_ptr[j + 1]));
     xi = fma(p.B2_val[e], uj, xi);
     if (le == 0 && live) p.u[((long long)(k - 1) * p.Nu + j) * ns + scen] = uj;
   }
@@ -155,8 +143,7 @@ using namespace sls;
 namespace {
 
 int enqueue_steps(sls_loop* L, const LoopParams& p, int64_t steps, hipStream_t st) {
-  int scn = 1;
-  while (scn < 64 && scn < p.nscen) scn <<= 1;
+  const int scn = scenario_slots(p.nscen);
   const size_t slab = (size_t)p.Nx * p.nscen * sizeof(double);
   HIPCHK(L->ctx, hipMemsetAsync(p.what, 0, slab * (p.T + 1), st));                       // ŵ = 0 up to and including t = 1
   HIPCHK(L->ctx, hipMemsetAsync(p.x, 0, slab, st));                                      // x[:,1] = 0
@@ -185,35 +172,17 @@ int sls_closed_loop_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const
   L->n_entries = (int64_t)F.hoff.size();
   hipError_t e = hipSetDevice(L->dev);
   if (e != hipSuccess) { delete L; return hipfail(ctx, e, "hipSetDevice"); }
-  // one arena for the operator tables
-  struct Req { const void* src; size_t bytes; const void** out; };
-  std::vector<Req> reqs;
-  auto add = [&](const auto& v, const auto** out) {
-    reqs.push_back({v.data(), v.size() * sizeof(v[0]), reinterpret_cast<const void**>(out)});
-  };
+  // one arena: the operator tables, then Φ in row order
+  Arena ar;
   LoopParams& kp = L->kp;
-  add(F.beta_ptr, &kp.beta_ptr); add(F.u_ptr, &kp.u_ptr); add(F.hoff, &kp.hoff); add(F.perm, &L->d_perm);
-  add(F.A.ptr, &kp.A_ptr); add(F.A.idx, &kp.A_idx); add(F.A.val, &kp.A_val);
-  add(F.B1.ptr, &kp.B1_ptr); add(F.B1.idx, &kp.B1_idx); add(F.B1.val, &kp.B1_val);
-  add(F.B2.ptr, &kp.B2_ptr); add(F.B2.idx, &kp.B2_idx); add(F.B2.val, &kp.B2_val);
-  add(F.orphan, &kp.orphan);
-  auto al = [](size_t b) { return (std::max<size_t>(b, 16) + 255) / 256 * 256; };
-  size_t total = 0;
-  for (auto& r : reqs) total += al(r.bytes);
-  const size_t vals_off = total;
-  total += al((size_t)std::max<int64_t>(L->n_entries, 1) * sizeof(double));
-  e = hipMalloc(&L->arena, total);
-  if (e != hipSuccess) { delete L; return hipfail(ctx, e, "hipMalloc (closed-loop operator)"); }
-  size_t off = 0;
-  for (auto& r : reqs) {
-    if (r.bytes) {
-      e = hipMemcpy(static_cast<unsigned char*>(L->arena) + off, r.src, r.bytes, hipMemcpyHostToDevice);
-      if (e != hipSuccess) { (void)hipFree(L->arena); delete L; return hipfail(ctx, e, "hipMemcpy H2D (closed-loop operator)"); }
-    }
-    *r.out = static_cast<unsigned char*>(L->arena) + off;
-    off += al(r.bytes);
-  }
-  L->d_vals = reinterpret_cast<double*>(static_cast<unsigned char*>(L->arena) + vals_off);
+  ar.table(F.beta_ptr, &kp.beta_ptr); ar.table(F.u_ptr, &kp.u_ptr); ar.table(F.hoff, &kp.hoff); ar.table(F.perm, &L->d_perm);
+  ar.table(F.A.ptr, &kp.A_ptr); ar.table(F.A.idx, &kp.A_idx); ar.table(F.A.val, &kp.A_val);
+  ar.table(F.B1.ptr, &kp.B1_ptr); ar.table(F.B1.idx, &kp.B1_idx); ar.table(F.B1.val, &kp.B1_val);
+  ar.table(F.B2.ptr, &kp.B2_ptr); ar.table(F.B2.idx, &kp.B2_idx); ar.table(F.B2.val, &kp.B2_val);
+  ar.table(F.orphan, &kp.orphan);
+  ar.buffer((size_t)std::max<int64_t>(L->n_entries, 1), &L->d_vals);
+  rc = ar.commit(ctx, &L->arena, "hipMalloc (closed-loop operator)", "hipMemcpy H2D (closed-loop operator)");
+  if (rc) { delete L; return rc; }
   kp.vals = L->d_vals;
   kp.Nx = (int)F.Nx; kp.Nu = (int)F.Nu; kp.Nw = (int)F.Nw; kp.T = (int)F.T; kp.n_orphan = (int)F.orphan.size();
   // host vectors are no longer needed
@@ -242,12 +211,7 @@ int sls_closed_loop_run(sls_loop* L, void* hip_stream, const double* d_values, c
   LoopParams p = L->kp;
   p.nscen = nscen; p.w = d_w; p.x = d_x; p.u = d_u; p.what = L->d_what;
   HIPCHK(ctx, hipEventRecord(L->ev0, st));
-  if (L->n_entries > 0) {                                      // Φ: mask order → row order
-    const int bs = 256;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((L->n_entries + bs - 1) / bs)), dim3(bs), 0, st, d_values, L->d_perm,
-                       (long long)L->n_entries, L->d_vals);
-    HIPCHK(ctx, hipGetLastError());
-  }
+  if (int rc = launch_gather_phi(ctx, d_values, L->d_perm, L->n_entries, L->d_vals, st)) return rc;   // Φ: mask order → row order
   static const bool no_graph = sls_knob("SLS_NO_GRAPH") != nullptr;
   if (no_graph || steps < 3) {
     int rc = enqueue_steps(L, p, steps, st);

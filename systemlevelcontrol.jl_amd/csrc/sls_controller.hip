@@ -22,27 +22,15 @@
 #include "../../include/sls_mi355x_debug.h"
 #include "sls_controller.h"
 #include "sls_internal.h"
+#include "sls_object.h"
 #include "sls_symbolic.h"
+#include "sls_wave_util.h"
 
 namespace {
 
 using sls::ControllerParams;
 
 constexpr int kWavesPerBlock = 4;
-
-__global__ void controller_gather_kernel(const double* __restrict__ values, const int32_t* __restrict__ perm, long long n,
-                                         double* __restrict__ vals) {
-  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) vals[k] = values[perm[k]];
-}
-
-// sum over the lanes that share `lane % SCN` (the scenario slot); result in every lane of the group
-template <int SCN>
-__device__ __forceinline__ double entry_lanes_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= SCN; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // s: ring slot of this step, par: which β copy holds β_k.  x [Nx][nscen], u [Nu][nscen], what_out [Nx][nscen] or NULL.
 template <int SCN>
@@ -76,7 +64,7 @@ controller_step_kernel(ControllerParams p, int s, int par, const double* __restr
     a3 = fma(v3, rd(h3), a3);
   }
   for (; e < end; e += NE) a0 = fma(p.vals[e], rd(p.hoff[e]), a0);
-  const double sum = entry_lanes_sum<SCN>((a0 + a1) + (a2 + a3));
+  const double sum = sls::lane_group_sum<SCN>((a0 + a1) + (a2 + a3));
   if (le != 0 || !live) return;
   if (row >= p.Nx) {                                           // u row
     u[(long long)(row - p.Nx) * ns + scen] = sum;
@@ -133,15 +121,11 @@ extern "C" {
 
 int sls_controller_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_csc_bool* Sx, const sls_csc_bool* Su,
                         int64_t nscen, sls_controller** out) {
-  if (!ctx) return fail(nullptr, SLS_EINVAL, "sls_controller_plan: null context");
-  if (!out || !dims || !Sx || !Su) return fail(ctx, SLS_EINVAL, "sls_controller_plan: null argument");
-  *out = nullptr;
-  if (dev_slot < 0 || dev_slot >= (int)ctx->devs.size()) return fail(ctx, SLS_EINVAL, "sls_controller_plan: dev_slot out of range");
-  if (nscen < 1) return fail(ctx, SLS_EINVAL, "sls_controller_plan: nscen must be >= 1");
-  if (nscen > 65535LL * 64) return fail(ctx, SLS_EUNSUPPORTED, "sls_controller_plan: nscen exceeds 65535 chunks of 64 scenarios");
+  int rc = check_plan_args(ctx, "sls_controller_plan", out, dims && Sx && Su, dev_slot, nscen);
+  if (rc) return rc;
   FirOperator F;
   std::string msg;
-  int rc = build_controller_operator(dims, Sx, Su, F, msg);
+  rc = build_controller_operator(dims, Sx, Su, F, msg);
   if (rc) return fail(ctx, rc, "sls_controller_plan: " + msg);
   if (F.Nx + F.Nu > 0x7ffffff0LL) return fail(ctx, SLS_EUNSUPPORTED, "sls_controller_plan: Nx + Nu exceeds int32");
   sls_controller* L = new (std::nothrow) sls_controller();
@@ -152,30 +136,21 @@ int sls_controller_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const 
   row_ptr.insert(row_ptr.end(), F.u_ptr.begin() + 1, F.u_ptr.end());
   hipError_t e = hipSetDevice(L->dev);
   if (e != hipSuccess) { delete L; return hipfail(ctx, e, "hipSetDevice"); }
-  auto al = [](size_t b) { return (std::max<size_t>(b, 16) + 255) / 256 * 256; };
-  const size_t b_ptr = al(row_ptr.size() * sizeof(int32_t)), b_ent = al((size_t)L->n_entries * sizeof(int32_t));
-  const size_t b_vals = al((size_t)L->n_entries * sizeof(double));
-  const size_t b_beta = al((size_t)controller_beta_doubles(F.Nx, nscen) * sizeof(double));
-  const size_t b_hist = al((size_t)controller_hist_doubles(F.Nx, F.T, nscen) * sizeof(double));
-  e = hipMalloc(&L->arena, b_ptr + 2 * b_ent + b_vals + b_beta + b_hist);
-  if (e != hipSuccess) { delete L; return hipfail(ctx, e, "hipMalloc (controller)"); }
-  unsigned char* base = static_cast<unsigned char*>(L->arena);
+  Arena ar;
   ControllerParams& kp = L->kp;
-  kp.row_ptr = reinterpret_cast<const int32_t*>(base);
-  kp.hoff = reinterpret_cast<const int32_t*>(base + b_ptr);
-  L->d_perm = reinterpret_cast<const int32_t*>(base + b_ptr + b_ent);
-  L->d_vals = reinterpret_cast<double*>(base + b_ptr + 2 * b_ent);
+  ar.table(row_ptr, &kp.row_ptr); ar.table(F.hoff, &kp.hoff); ar.table(F.perm, &L->d_perm);
+  ar.buffer((size_t)L->n_entries, &L->d_vals);
+  L->state_off = ar.bytes();
+  ar.buffer((size_t)controller_beta_doubles(F.Nx, nscen), &kp.beta);
+  ar.buffer((size_t)controller_hist_doubles(F.Nx, F.T, nscen), &kp.hist);
+  L->state_bytes = ar.bytes() - L->state_off;
+  rc = ar.commit(ctx, &L->arena, "hipMalloc (controller)", "sls_controller_plan: upload");
+  if (rc) { delete L; return rc; }
   kp.vals = L->d_vals;
-  L->state_off = b_ptr + 2 * b_ent + b_vals; L->state_bytes = b_beta + b_hist;
-  kp.beta = reinterpret_cast<double*>(base + L->state_off);
-  kp.hist = reinterpret_cast<double*>(base + L->state_off + b_beta);
   kp.Nx = (int32_t)F.Nx; kp.Nu = (int32_t)F.Nu; kp.T = (int32_t)F.T; kp.R = (int32_t)controller_ring_slots(F.T);
   kp.nscen = nscen;
-  while (L->scn < 64 && L->scn < nscen) L->scn <<= 1;
-  e = hipMemcpy(base, row_ptr.data(), row_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess && L->n_entries) e = hipMemcpy(base + b_ptr, F.hoff.data(), (size_t)L->n_entries * sizeof(int32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess && L->n_entries) e = hipMemcpy(base + b_ptr + b_ent, F.perm.data(), (size_t)L->n_entries * sizeof(int32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(base + L->state_off, 0, L->state_bytes);             // the state after a reset
+  L->scn = scenario_slots(nscen);
+  e = hipMemset(static_cast<unsigned char*>(L->arena) + L->state_off, 0, L->state_bytes);   // the state after a reset
   if (e == hipSuccess) e = hipDeviceSynchronize();                                          // plan time may wait; the calls below never do
   if (e != hipSuccess) { (void)hipFree(L->arena); delete L; return hipfail(ctx, e, "sls_controller_plan: upload"); }
   *out = L;
@@ -186,12 +161,8 @@ int sls_controller_load(sls_controller* L, void* hip_stream, const double* d_val
   if (!L) return fail(nullptr, SLS_EINVAL, "sls_controller_load: null controller");
   if (!d_values && L->n_entries > 0) return fail(L->ctx, SLS_EINVAL, "sls_controller_load: null device pointer");
   HIPCHK(L->ctx, hipSetDevice(L->dev));
-  if (L->n_entries > 0) {                                      // Φ: mask order → row order
-    const int bs = 256;
-    hipLaunchKernelGGL(controller_gather_kernel, dim3((unsigned)((L->n_entries + bs - 1) / bs)), dim3(bs), 0,
-                       static_cast<hipStream_t>(hip_stream), d_values, L->d_perm, (long long)L->n_entries, L->d_vals);
-    HIPCHK(L->ctx, hipGetLastError());
-  }
+  // Φ: mask order → row order
+  if (int rc = launch_gather_phi(L->ctx, d_values, L->d_perm, L->n_entries, L->d_vals, static_cast<hipStream_t>(hip_stream))) return rc;
   L->loaded = true;
   return 0;
 }

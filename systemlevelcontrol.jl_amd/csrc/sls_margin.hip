@@ -13,8 +13,8 @@
 //                              not depend on nscen and the lane layout of the first kernel never enters a sum, which is what
 //                              makes scenario s independent of nscen.
 //   margin_totals_kernel       one wave per chunk of 8 scenarios: the two maxima.
-// load and the device path of set_plant are one gather launch each.  load, set_plant (device path), run allocate nothing and
-// never wait.  The worst case over a box of plants (sls_margin_set_radius, sls_margin_box_*; semantics in sls_margin_box.h, kernels
+// load and set_plant are the shared gathers of sls_object.h.  load, set_plant (device path), run allocate nothing and never
+// wait.  The worst case over a box of plants (sls_margin_set_radius, sls_margin_box_*; semantics in sls_margin_box.h, kernels
 // in sls_margin_box.hip) lives on the same object: set_radius is a setup call, box_run enqueues two launches.
 #include <hip/hip_runtime.h>
 
@@ -27,27 +27,14 @@
 #include "sls_internal.h"
 #include "sls_margin.h"
 #include "sls_margin_box.h"
+#include "sls_object.h"
+#include "sls_wave_util.h"
 
 namespace {
 
 using sls::MarginParams;
 
 constexpr int kWavesPerBlock = 4;
-
-__global__ void margin_gather_phi_kernel(const double* __restrict__ values, const int32_t* __restrict__ perm, long long n,
-                                         double* __restrict__ vals) {
-  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) vals[k] = values[perm[k]];
-}
-
-// dst[e][s] = src[from[e]][s] (per_scenario) or src[from[e]] (broadcast): CSC → CSR, scenario innermost; n = nnz·nscen
-__global__ void margin_gather_plant_kernel(const double* __restrict__ src, const int32_t* __restrict__ from, long long n, long long ns,
-                                           int per_scenario, double* __restrict__ dst) {
-  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const long long e = k / ns, s = k - e * ns;
-  dst[k] = per_scenario ? src[(long long)from[e] * ns + s] : src[from[e]];
-}
 
 // lanes = (entry slot le, scenario slot ls), lane = le·SCN + ls; the wave evaluates NE = 64/SCN consecutive pattern entries
 template <int SCN>
@@ -104,8 +91,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) margin_sums_kernel(Margin
     const long long beg = p.def_ptr[list - p.v.Nx];
     sum = sls::margin_slot_sum(p.def_ptr[list - p.v.Nx + 1] - p.def_ptr[list - p.v.Nx], q, [&](int32_t k) { return sv[(beg + k) * ns]; });
   }
-#pragma unroll
-  for (int off = 32; off >= SS; off >>= 1) sum += __shfl_xor(sum, off, 64);
+  sum = sls::lane_group_sum<SS>(sum);
   static_assert(SS * SQ == 64, "one wave");
   if (q == 0 && live) (list < p.v.Nx ? row_l1 : col_l1)[(long long)(list < p.v.Nx ? list : list - p.v.Nx) * ns + scen] = sls::margin_report(sum);
 }
@@ -136,11 +122,11 @@ __global__ void __launch_bounds__(64) margin_totals_kernel(const double* __restr
 struct sls_margin {
   sls_ctx* ctx = nullptr;
   int dev = 0;
-  int64_t n_entries = 0, n_defect = 0, nnzA = 0, nnzB = 0;
+  int64_t n_entries = 0, n_defect = 0;
   void* arena = nullptr;               // tables, Φ by columns, plant values, staging, scratch, results
-  const int32_t *d_perm = nullptr, *d_A_src = nullptr, *d_B2_src = nullptr;
-  double *d_phi = nullptr, *d_A_val = nullptr, *d_B2_val = nullptr;
-  double* d_stage = nullptr;           // max(nnz(A), nnz(B₂))·nscen doubles: where the host path of set_plant lands
+  const int32_t* d_perm = nullptr;
+  double* d_phi = nullptr;
+  sls::PlantEnsemble plant;
   double* d_result = nullptr;          // row_l1 [Nx][nscen], col_l1 [Nx][nscen], totals [2][nscen]
   MarginParams kp{};
   int scn = 1;                         // scenario slots per wave: smallest power of two ≥ nscen, at most 64
@@ -162,17 +148,6 @@ using namespace sls;
 
 namespace {
 
-int enqueue_plant_gather(sls_margin* M, hipStream_t st, const double* d_src, const int32_t* d_from, int64_t nnz, int per_scenario,
-                         double* d_dst) {
-  const long long n = (long long)nnz * M->kp.v.nscen;
-  if (n == 0) return 0;
-  const int bs = 256;
-  hipLaunchKernelGGL(margin_gather_plant_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, st, d_src, d_from, n, M->kp.v.nscen,
-                     per_scenario, d_dst);
-  HIPCHK(M->ctx, hipGetLastError());
-  return 0;
-}
-
 // the three passes; every destination is a device pointer and not NULL
 int enqueue_run(sls_margin* M, hipStream_t st, double* d_row, double* d_col, double* d_tot) {
   const MarginParams& p = M->kp;
@@ -193,84 +168,44 @@ extern "C" {
 
 int sls_margin_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
                     int64_t nscen, sls_margin** out) {
-  if (!ctx) return fail(nullptr, SLS_EINVAL, "sls_margin_plan: null context");
-  if (!out || !dims || !P || !Sx || !Su) return fail(ctx, SLS_EINVAL, "sls_margin_plan: null argument");
-  *out = nullptr;
-  if (dev_slot < 0 || dev_slot >= (int)ctx->devs.size()) return fail(ctx, SLS_EINVAL, "sls_margin_plan: dev_slot out of range");
-  if (nscen < 1) return fail(ctx, SLS_EINVAL, "sls_margin_plan: nscen must be >= 1");
-  if (nscen > 65535LL * 64) return fail(ctx, SLS_EUNSUPPORTED, "sls_margin_plan: nscen exceeds 65535 chunks of 64 scenarios");
+  int rc = check_plan_args(ctx, "sls_margin_plan", out, dims && P && Sx && Su, dev_slot, nscen);
+  if (rc) return rc;
   MarginTables Tb;
   std::string msg;
-  int rc = build_margin_tables(dims, P, Sx, Su, Tb, msg);
+  rc = build_margin_tables(dims, P, Sx, Su, Tb, msg);
   if (rc) return fail(ctx, rc, "sls_margin_plan: " + msg);
   const FirOperator& F = Tb.R.F;
   const int64_t Nx = Tb.Nx;
-  const int64_t n_gather = (int64_t)std::max(F.A.val.size(), F.B2.val.size()) * nscen;
-  if (n_gather / 256 + 1 > 0x7fffffffLL) return fail(ctx, SLS_EUNSUPPORTED, "sls_margin_plan: nnz·nscen exceeds the gather's grid");
+  if ((rc = PlantEnsemble::check_size(ctx, "sls_margin_plan", F.A.val.size(), F.B2.val.size(), nscen))) return rc;
   if (2 * Nx * (nscen / kMarginSumScen + 1) / 4 + 1 > 0x7fffffffLL) return fail(ctx, SLS_EUNSUPPORTED, "sls_margin_plan: Nx·nscen exceeds the sum pass's grid");
   sls_margin* M = new (std::nothrow) sls_margin();
   if (!M) return fail(ctx, SLS_ENOMEM, "sls_margin_plan: out of memory");
   M->ctx = ctx; M->dev = ctx->devs[dev_slot];
   M->n_entries = (int64_t)Tb.phi_perm.size(); M->n_defect = (int64_t)Tb.def_key.size();
-  M->nnzA = (int64_t)F.A.val.size(); M->nnzB = (int64_t)F.B2.val.size();
   M->h_A_ptr = F.A.ptr; M->h_A_src = Tb.R.A_src; M->h_B2_ptr = F.B2.ptr; M->h_B2_src = Tb.R.B2_src;
   hipError_t e = hipSetDevice(M->dev);
   if (e != hipSuccess) { delete M; return hipfail(ctx, e, "hipSetDevice"); }
   // one arena: uploaded tables first, then the buffers the object owns
-  struct Req { const void* src; size_t bytes; const void** out; };
-  std::vector<Req> reqs;
-  auto add = [&](const auto& v, const auto** o) { reqs.push_back({v.data(), v.size() * sizeof(v[0]), reinterpret_cast<const void**>(o)}); };
+  Arena ar;
   MarginParams& kp = M->kp;
-  add(Tb.phi_seg, &kp.v.phi_seg); add(Tb.phi_row, &kp.v.phi_row); add(Tb.phi_perm, &M->d_perm);
-  add(F.A.ptr, &kp.v.A_ptr); add(F.A.idx, &kp.v.A_idx); add(F.B2.ptr, &kp.v.B2_ptr); add(F.B2.idx, &kp.v.B2_idx);
-  add(Tb.R.A_src, &M->d_A_src); add(Tb.R.B2_src, &M->d_B2_src);
-  add(Tb.def_ptr, &kp.def_ptr); add(Tb.def_col, &kp.def_col); add(Tb.def_key, &kp.def_key); add(Tb.def_start, &kp.def_start);
-  add(Tb.row_ptr, &kp.row_ptr); add(Tb.row_perm, &kp.row_perm);
-  auto al = [](size_t b) { return (std::max<size_t>(b, 16) + 255) / 256 * 256; };
-  size_t total = 0;
-  for (auto& r : reqs) total += al(r.bytes);
-  const size_t D = sizeof(double);
-  const size_t b_phi = al((size_t)M->n_entries * D), b_A = al((size_t)(M->nnzA * nscen) * D), b_B = al((size_t)(M->nnzB * nscen) * D);
-  const size_t b_stage = al((size_t)n_gather * D), b_scr = al((size_t)(M->n_defect * nscen) * D), b_res = al((size_t)((2 * Nx + 2) * nscen) * D);
-  const size_t off_phi = total, off_A = off_phi + b_phi, off_B = off_A + b_A, off_stage = off_B + b_B, off_scr = off_stage + b_stage;
-  const size_t off_res = off_scr + b_scr;
-  M->device_bytes = off_res + b_res;
-  M->plant_bytes = b_A + b_B;
-  e = hipMalloc(&M->arena, M->device_bytes);
-  if (e != hipSuccess) { delete M; return hipfail(ctx, e, "hipMalloc (margin)"); }
-  unsigned char* base = static_cast<unsigned char*>(M->arena);
-  size_t off = 0;
-  for (auto& r : reqs) {
-    if (r.bytes) {
-      e = hipMemcpy(base + off, r.src, r.bytes, hipMemcpyHostToDevice);
-      if (e != hipSuccess) { (void)hipFree(M->arena); delete M; return hipfail(ctx, e, "hipMemcpy H2D (margin tables)"); }
-    }
-    *r.out = base + off;
-    off += al(r.bytes);
-  }
-  M->d_phi = reinterpret_cast<double*>(base + off_phi); kp.v.phi_val = M->d_phi;
-  M->d_A_val = reinterpret_cast<double*>(base + off_A); kp.v.A_val = M->d_A_val;
-  M->d_B2_val = reinterpret_cast<double*>(base + off_B); kp.v.B2_val = M->d_B2_val;
-  M->d_stage = reinterpret_cast<double*>(base + off_stage);
-  kp.scratch = reinterpret_cast<double*>(base + off_scr);
-  M->d_result = reinterpret_cast<double*>(base + off_res);
+  ar.table(Tb.phi_seg, &kp.v.phi_seg); ar.table(Tb.phi_row, &kp.v.phi_row); ar.table(Tb.phi_perm, &M->d_perm);
+  ar.table(F.A.ptr, &kp.v.A_ptr); ar.table(F.A.idx, &kp.v.A_idx); ar.table(F.B2.ptr, &kp.v.B2_ptr); ar.table(F.B2.idx, &kp.v.B2_idx);
+  M->plant.lay_out_tables(ar, Tb.R.A_src, Tb.R.B2_src);
+  ar.table(Tb.def_ptr, &kp.def_ptr); ar.table(Tb.def_col, &kp.def_col); ar.table(Tb.def_key, &kp.def_key);
+  ar.table(Tb.def_start, &kp.def_start); ar.table(Tb.row_ptr, &kp.row_ptr); ar.table(Tb.row_perm, &kp.row_perm);
+  ar.buffer((size_t)M->n_entries, &M->d_phi);
+  M->plant_bytes = M->plant.lay_out_values(ar, nscen);
+  ar.buffer((size_t)(M->n_defect * nscen), &kp.scratch);
+  ar.buffer((size_t)((2 * Nx + 2) * nscen), &M->d_result);
+  M->device_bytes = ar.bytes();
+  rc = ar.commit(ctx, &M->arena, "hipMalloc (margin)", "hipMemcpy H2D (margin tables)");
+  if (rc) { delete M; return rc; }
+  kp.v.phi_val = M->d_phi; kp.v.A_val = M->plant.d_A_val; kp.v.B2_val = M->plant.d_B2_val;
   kp.n_defect = M->n_defect;
   kp.v.Nx = (int32_t)Nx; kp.v.Nu = (int32_t)Tb.Nu; kp.v.T = (int32_t)Tb.T; kp.v.nscen = nscen;
-  while (M->scn < 64 && M->scn < nscen) M->scn <<= 1;
-  // every scenario starts from P's values: the broadcast gather from the CSC arrays, staged like a host-path set_plant
-  rc = 0;
-  const double* init[2] = {P->A->nzval, P->B2->nzval};
-  const int64_t nnz[2] = {M->nnzA, M->nnzB};
-  const int32_t* from[2] = {M->d_A_src, M->d_B2_src};
-  double* dst[2] = {M->d_A_val, M->d_B2_val};
-  for (int m = 0; m < 2 && e == hipSuccess && !rc; ++m) {
-    if (!nnz[m]) continue;
-    if (init[m]) e = hipMemcpy(M->d_stage, init[m], (size_t)nnz[m] * D, hipMemcpyHostToDevice);
-    else { std::vector<double> one((size_t)nnz[m], 1.0); e = hipMemcpy(M->d_stage, one.data(), (size_t)nnz[m] * D, hipMemcpyHostToDevice); }
-    if (e == hipSuccess) rc = enqueue_plant_gather(M, nullptr, M->d_stage, from[m], nnz[m], 0, dst[m]);
-    if (e == hipSuccess && !rc) e = hipDeviceSynchronize();
-  }
-  if (e != hipSuccess || rc) { (void)hipFree(M->arena); delete M; return rc ? rc : hipfail(ctx, e, "sls_margin_plan: upload"); }
+  M->scn = scenario_slots(nscen);
+  rc = M->plant.init_from(ctx, P, "sls_margin_plan: upload");
+  if (rc) { (void)hipFree(M->arena); delete M; return rc; }
   *out = M;
   return 0;
 }
@@ -279,38 +214,16 @@ int sls_margin_load(sls_margin* M, void* hip_stream, const double* d_values) {
   if (!M) return fail(nullptr, SLS_EINVAL, "sls_margin_load: null margin");
   if (!d_values && M->n_entries > 0) return fail(M->ctx, SLS_EINVAL, "sls_margin_load: null device pointer");
   HIPCHK(M->ctx, hipSetDevice(M->dev));
-  if (M->n_entries > 0) {                                      // Φ: mask order → by columns
-    const int bs = 256;
-    hipLaunchKernelGGL(margin_gather_phi_kernel, dim3((unsigned)((M->n_entries + bs - 1) / bs)), dim3(bs), 0,
-                       static_cast<hipStream_t>(hip_stream), d_values, M->d_perm, (long long)M->n_entries, M->d_phi);
-    HIPCHK(M->ctx, hipGetLastError());
-  }
+  // Φ: mask order → by columns
+  if (int rc = launch_gather_phi(M->ctx, d_values, M->d_perm, M->n_entries, M->d_phi, static_cast<hipStream_t>(hip_stream))) return rc;
   M->loaded = true;
   return 0;
 }
 
 int sls_margin_set_plant(sls_margin* M, void* hip_stream, const double* A_nzval, const double* B2_nzval, int on_device, int per_scenario) {
   if (!M) return fail(nullptr, SLS_EINVAL, "sls_margin_set_plant: null margin");
-  sls_ctx* ctx = M->ctx;
-  HIPCHK(ctx, hipSetDevice(M->dev));
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  const double* src[2] = {A_nzval, B2_nzval};
-  const int64_t nnz[2] = {M->nnzA, M->nnzB};
-  const int32_t* from[2] = {M->d_A_src, M->d_B2_src};
-  double* dst[2] = {M->d_A_val, M->d_B2_val};
-  for (int m = 0; m < 2; ++m) {
-    if (!src[m] || !nnz[m]) continue;
-    const double* d_src = src[m];
-    if (!on_device) {                                          // host arrays land in the staging buffer; the caller's array is free on return
-      const size_t bytes = (size_t)nnz[m] * (per_scenario ? (size_t)M->kp.v.nscen : 1) * sizeof(double);
-      HIPCHK(ctx, hipMemcpyAsync(M->d_stage, src[m], bytes, hipMemcpyHostToDevice, st));
-      HIPCHK(ctx, hipStreamSynchronize(st));
-      d_src = M->d_stage;
-    }
-    int rc = enqueue_plant_gather(M, st, d_src, from[m], nnz[m], per_scenario ? 1 : 0, dst[m]);
-    if (rc) return rc;
-  }
-  return 0;
+  HIPCHK(M->ctx, hipSetDevice(M->dev));
+  return M->plant.set(M->ctx, static_cast<hipStream_t>(hip_stream), A_nzval, B2_nzval, on_device, per_scenario);
 }
 
 int sls_margin_run(sls_margin* M, void* hip_stream, double* d_row_l1, double* d_col_l1, double* d_totals) {
@@ -359,7 +272,7 @@ int sls_margin_fetch_plant(sls_margin* M, void* hip_stream, double* A_nzval, dou
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   const size_t ns = (size_t)M->kp.v.nscen;
   double* out[2] = {A_nzval, B2_nzval};
-  const double* d_val[2] = {M->d_A_val, M->d_B2_val};
+  const double* d_val[2] = {M->plant.d_A_val, M->plant.d_B2_val};
   const std::vector<int32_t>* src[2] = {&M->h_A_src, &M->h_B2_src};
   std::vector<double> csr;
   for (int m = 0; m < 2; ++m) {
@@ -382,23 +295,15 @@ int sls_margin_set_radius(sls_margin* M, const double* A_rad, const double* B2_r
   int rc = build_margin_box_lists(M->h_A_ptr, M->h_A_src, M->h_B2_ptr, M->h_B2_src, ns, A_rad, B2_rad, per_scenario != 0, L, msg);
   if (rc) return fail(ctx, rc, "sls_margin_set_radius: " + msg);
   HIPCHK(ctx, hipSetDevice(M->dev));
-  auto al = [](size_t b) { return (std::max<size_t>(b, 16) + 255) / 256 * 256; };
-  const size_t b_ptr = al((size_t)(Nx + 1) * 4), b_ent = al((size_t)(M->nnzA + M->nnzB) * 4), b_ra = al((size_t)(M->nnzA * ns) * 8);
-  const size_t b_rb = al((size_t)(M->nnzB * ns) * 8), b_rows = al((size_t)(Nx * ns) * 8), b_tot = al((size_t)ns * 8);
-  if (!M->box_arena) {                                         // sizes depend on the plan alone: allocated once
-    void* a = nullptr;
-    const size_t total = b_ptr + b_ent + b_ra + b_rb + 2 * b_rows + b_tot;
-    HIPCHK(ctx, hipMalloc(&a, total));
-    M->box_arena = a; M->box_bytes = total;
-    unsigned char* base = static_cast<unsigned char*>(a);
-    M->bview.act_ptr = reinterpret_cast<const int32_t*>(base); base += b_ptr;
-    M->bview.act_ent = reinterpret_cast<const int32_t*>(base); base += b_ent;
-    M->bview.A_rad = reinterpret_cast<const double*>(base); base += b_ra;
-    M->bview.B2_rad = reinterpret_cast<const double*>(base); base += b_rb;
-    M->d_box_wc = reinterpret_cast<double*>(base); base += b_rows;
-    M->d_box_vertex = reinterpret_cast<long long*>(base); base += b_rows;
-    M->d_box_tot = reinterpret_cast<double*>(base);
-    M->bview.nnzA = (int32_t)M->nnzA;
+  if (!M->box_arena) {                                         // sizes depend on the plan alone: allocated once, filled below
+    const size_t nnzA = (size_t)M->plant.nnzA, nnzB = (size_t)M->plant.nnzB;
+    Arena ar;
+    ar.buffer((size_t)(Nx + 1), &M->bview.act_ptr); ar.buffer(nnzA + nnzB, &M->bview.act_ent);
+    ar.buffer(nnzA * ns, &M->bview.A_rad); ar.buffer(nnzB * ns, &M->bview.B2_rad);
+    ar.buffer((size_t)(Nx * ns), &M->d_box_wc); ar.buffer((size_t)(Nx * ns), &M->d_box_vertex); ar.buffer((size_t)ns, &M->d_box_tot);
+    if ((rc = ar.commit(ctx, &M->box_arena, "hipMalloc(&a, total)", ""))) return rc;   // what: the call text a HIPCHK reports here
+    M->box_bytes = ar.bytes();
+    M->bview.nnzA = (int32_t)nnzA;
   }
   HIPCHK(ctx, hipDeviceSynchronize());                         // a run in flight still reads the lists
   struct Up { const void* dst; const void* src; size_t bytes; };
@@ -459,9 +364,9 @@ int sls_margin_box_worst_plant(sls_margin* M, void* hip_stream, double* A_nzval,
   int rc = sls_margin_box_fetch(M, hip_stream, nullptr, vertex.data(), nullptr, nullptr);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  std::vector<double> A_cen((size_t)(M->nnzA * ns)), B2_cen((size_t)(M->nnzB * ns));
-  if (!A_cen.empty()) HIPCHK(ctx, hipMemcpyAsync(A_cen.data(), M->d_A_val, A_cen.size() * 8, hipMemcpyDeviceToHost, st));
-  if (!B2_cen.empty()) HIPCHK(ctx, hipMemcpyAsync(B2_cen.data(), M->d_B2_val, B2_cen.size() * 8, hipMemcpyDeviceToHost, st));
+  std::vector<double> A_cen((size_t)(M->plant.nnzA * ns)), B2_cen((size_t)(M->plant.nnzB * ns));
+  if (!A_cen.empty()) HIPCHK(ctx, hipMemcpyAsync(A_cen.data(), M->plant.d_A_val, A_cen.size() * 8, hipMemcpyDeviceToHost, st));
+  if (!B2_cen.empty()) HIPCHK(ctx, hipMemcpyAsync(B2_cen.data(), M->plant.d_B2_val, B2_cen.size() * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
   margin_box_worst_plant(M->h_A_ptr, M->h_A_src, M->h_B2_ptr, M->h_B2_src, M->box, A_cen.data(), B2_cen.data(), vertex.data(), A_nzval, B2_nzval);
   return 0;

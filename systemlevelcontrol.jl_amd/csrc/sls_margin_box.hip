@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sls_margin_box.h"
+#include "sls_wave_util.h"
 
 namespace {
 
@@ -78,8 +79,7 @@ __device__ __forceinline__ void box_exact_row(const MarginBoxParams& bp, const i
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {                             // the slots of every vertex, then the lane's best in ascending code
-#pragma unroll
-      for (int off = 32; off >= SQ; off >>= 1) s[r] += __shfl_xor(s[r], off, 64);
+      s[r] = sls::lane_group_sum<SQ>(s[r]);
       const double val = sls::margin_report(s[r]);
       if (val > best) { best = val; best_code = pass * (8 * R) + r * 8 + vl; }
     }
@@ -130,8 +130,7 @@ __global__ void __launch_bounds__(64) margin_box_rows_kernel(MarginBoxParams bp,
           else { double phi; if (sls::margin_box_factor(p.v, bp.b.nnzA, ent[c - 1], p.def_col[d], p.def_key[d], phi)) val = fabs(phi); }
           s += val;
         }
-#pragma unroll
-      for (int off = 32; off >= SQ; off >>= 1) s += __shfl_xor(s, off, 64);
+      s = sls::lane_group_sum<SQ>(s);
       for (int k = 0; k < SQ; ++k) {                          // lanes 0 … 7 hold the eight columns of this pass
         const double col = __shfl(s, k, 64);
         const int cc = c0 + k;

@@ -32,7 +32,9 @@
 #include "../../include/sls_mi355x_debug.h"
 #include "sls_internal.h"
 #include "sls_norms.h"
+#include "sls_object.h"
 #include "sls_symbolic.h"
+#include "sls_wave_util.h"
 
 namespace {
 
@@ -46,12 +48,6 @@ __global__ void norms_gather_kernel(const double* __restrict__ values, const int
   if (k >= n2) return;
   const double v = values[perm[k]];
   vals[k] = w ? v * w[k] : v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 struct L1Params {
@@ -79,7 +75,7 @@ __global__ void __launch_bounds__(kBlock) norms_l1_kernel(L1Params p) {
     a0 += fabs(vals[e]); a1 += fabs(vals[e + 64]); a2 += fabs(vals[e + 128]); a3 += fabs(vals[e + 192]);
   }
   for (; e < end; e += 64) a0 += fabs(vals[e]);
-  const double s = sls::norms_l1_report(wave_sum((a0 + a1) + (a2 + a3)));
+  const double s = sls::norms_l1_report(sls::lane_group_sum<1>((a0 + a1) + (a2 + a3)));
   if (lane != 0) return;
   p.res[line] = s;
   double* out = col ? p.col_out : p.row_out;
@@ -126,7 +122,7 @@ __global__ void __launch_bounds__(kBlock) norms_h2_kernel(L1Params p) {
     a0 = fma(v0, v0, a0); a1 = fma(v1, v1, a1); a2 = fma(v2, v2, a2); a3 = fma(v3, v3, a3);
   }
   for (; e < end; e += 64) { const double v = vals[e]; a0 = fma(v, v, a0); }
-  const double s = sls::norms_l1_report(wave_sum((a0 + a1) + (a2 + a3)));
+  const double s = sls::norms_l1_report(sls::lane_group_sum<1>((a0 + a1) + (a2 + a3)));
   if (lane != 0) return;
   p.res[line] = s;
   double* out = col ? p.col_out : p.row_out;
@@ -139,7 +135,7 @@ __global__ void __launch_bounds__(kBlock) norms_h2_totals_kernel(const double* _
   __shared__ double lds[2 * kWavesPerBlock];
   double s = 0.0;
   for (int i = threadIdx.x; i < N; i += kBlock) s += res[i];
-  s = wave_sum(s);
+  s = sls::lane_group_sum<1>(s);
   if ((threadIdx.x & 63) == 0) lds[kWavesPerBlock + (threadIdx.x >> 6)] = s;
   const double m = block_max(res, N, lds);                      // its barriers publish the sums as well
   if (threadIdx.x != 0) return;
@@ -199,7 +195,7 @@ __global__ void __launch_bounds__(kBlock) norms_cov_kernel(CovParams p) {
       }
       lo = hi;
     }
-    acc = wave_sum(acc);
+    acc = sls::lane_group_sum<1>(acc);
     if (lane == 0) {
       p.res[q] = acc;
       if (p.out) p.out[q] = acc;
@@ -322,7 +318,7 @@ __global__ void __launch_bounds__(kBlock) norms_norm2_kernel(const double* __res
   const int f = blockIdx.x;
   double s = 0.0;
   for (int i = threadIdx.x; i < nlines; i += kBlock) s += part[(long long)i * F + f];
-  s = wave_sum(s);
+  s = sls::lane_group_sum<1>(s);
   if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x != 0) return;
@@ -444,8 +440,7 @@ int enqueue_hinf(sls_norms* L, hipStream_t st, const double* omega, int64_t nfre
   } else {
     HIPCHK(ctx, hipStreamSynchronize(st));
   }
-  int scn = 1;
-  while (scn < 64 && scn < F) scn <<= 1;
+  const int scn = scenario_slots(F);
   double* res_sigma = L->d_res + N + Nx + 2;
   const long long nv = (long long)Nx * F;
   hipLaunchKernelGGL(norms_init_kernel, dim3((unsigned)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, Nx, F, L->d_v, L->d_part);
@@ -511,33 +506,24 @@ int sls_norms_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_c
   L->n_entries = n; L->max_freq = max_freq; L->Nx = Nx; L->Nu = Op.Nu; L->T = T; L->index_base = dims->index_base;
   hipError_t e = hipSetDevice(L->dev);
   if (e != hipSuccess) { delete L; return hipfail(ctx, e, "hipSetDevice"); }
-  auto al = [](size_t b_) { return (std::max<size_t>(b_, 16) + 255) / 256 * 256; };
-  const size_t b_rp = al((size_t)(N + 1) * 4), b_cp = al((size_t)(Nx + 1) * 4), b_key = al((size_t)n * 4), b_perm = al((size_t)n * 8);
-  const size_t b_w = weighted ? al((size_t)n * 16) : 0, b_vals = al((size_t)n * 16);
-  const size_t b_v = al((size_t)Nx * max_freq * 16), b_y = al((size_t)N * max_freq * 16), b_tw = al((size_t)T * max_freq * 16);
-  const size_t b_part = al((size_t)N * max_freq * 8), b_scale = al((size_t)max_freq * 8);
-  const size_t n_res = (size_t)(N + Nx + 2 + max_freq + 2), b_res = al(n_res * 8);
-  L->arena_bytes = b_rp + b_cp + 2 * b_key + b_perm + b_w + b_vals + b_v + b_y + b_tw + b_part + b_scale + b_res;
-  e = hipMalloc(&L->arena, L->arena_bytes);
-  if (e != hipSuccess) { delete L; return hipfail(ctx, e, "hipMalloc (norms)"); }
-  unsigned char* base = static_cast<unsigned char*>(L->arena);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { unsigned char* p = base + o; o += bytes; return p; };
-  unsigned char *p_rp = take(b_rp), *p_cp = take(b_cp), *p_rk = take(b_key), *p_ck = take(b_key), *p_perm = take(b_perm);
-  unsigned char* p_w = weighted ? take(b_w) : nullptr;
-  L->d_row_ptr = reinterpret_cast<const int32_t*>(p_rp); L->d_col_ptr = reinterpret_cast<const int32_t*>(p_cp);
-  L->d_row_key = reinterpret_cast<const int32_t*>(p_rk); L->d_col_key = reinterpret_cast<const int32_t*>(p_ck);
-  L->d_perm = reinterpret_cast<const int32_t*>(p_perm); L->d_w = reinterpret_cast<const double*>(p_w);
-  L->d_vals = reinterpret_cast<double*>(take(b_vals));
-  L->d_v = reinterpret_cast<double2*>(take(b_v)); L->d_y = reinterpret_cast<double2*>(take(b_y)); L->d_tw = reinterpret_cast<double2*>(take(b_tw));
-  L->d_part = reinterpret_cast<double*>(take(b_part)); L->d_scale = reinterpret_cast<double*>(take(b_scale));
-  L->d_res = reinterpret_cast<double*>(take(b_res));
-  auto up = [&](void* dst, const void* src, size_t bytes) { if (e == hipSuccess && bytes) e = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); };
-  up(p_rp, Op.row_ptr.data(), (size_t)(N + 1) * 4); up(p_cp, Op.col_ptr.data(), (size_t)(Nx + 1) * 4);
-  up(p_rk, Op.row_key.data(), (size_t)n * 4); up(p_ck, Op.col_key.data(), (size_t)n * 4);
-  up(p_perm, Op.row_perm.data(), (size_t)n * 4); up(p_perm + (size_t)n * 4, Op.col_perm.data(), (size_t)n * 4);
-  if (weighted) { up(p_w, w_row.data(), (size_t)n * 8); up(p_w + (size_t)n * 8, w_col.data(), (size_t)n * 8); }
-  if (e == hipSuccess) e = hipMemset(L->d_res, 0, b_res);
+  // the two permutations share a block, row order then column order, and so do the two weight arrays; no weights, no block
+  std::vector<int32_t> perm(Op.row_perm);
+  perm.insert(perm.end(), Op.col_perm.begin(), Op.col_perm.end());
+  std::vector<double> w(w_row);
+  w.insert(w.end(), w_col.begin(), w_col.end());
+  Arena ar;
+  ar.table(Op.row_ptr, &L->d_row_ptr); ar.table(Op.col_ptr, &L->d_col_ptr); ar.table(Op.row_key, &L->d_row_key);
+  ar.table(Op.col_key, &L->d_col_key); ar.table(perm, &L->d_perm);
+  if (weighted) ar.table(w, &L->d_w);
+  ar.buffer(2 * (size_t)n, &L->d_vals);
+  ar.buffer((size_t)(Nx * max_freq), &L->d_v); ar.buffer((size_t)(N * max_freq), &L->d_y); ar.buffer((size_t)(T * max_freq), &L->d_tw);
+  ar.buffer((size_t)(N * max_freq), &L->d_part); ar.buffer((size_t)max_freq, &L->d_scale);
+  const size_t n_res = (size_t)(N + Nx + 2 + max_freq + 2);
+  ar.buffer(n_res, &L->d_res);
+  L->arena_bytes = ar.bytes();
+  rc = ar.commit(ctx, &L->arena, "hipMalloc (norms)", "sls_norms_plan: upload");
+  if (rc) { delete L; return rc; }
+  e = hipMemset(L->d_res, 0, Arena::al(n_res * 8));
   if (e == hipSuccess) e = hipDeviceSynchronize();              // plan time may wait; load, l1 and hinf never do
   if (e != hipSuccess) { (void)hipFree(L->arena); delete L; return hipfail(ctx, e, "sls_norms_plan: upload"); }
   *out = L;
@@ -618,7 +604,9 @@ int sls_norms_cov_pattern(sls_norms* L, int64_t npairs, const int64_t* pair_i, c
   if (int rc = norms_cov_check(L->Nx + L->Nu, L->index_base, npairs, pair_i, pair_j, msg)) return fail(L->ctx, rc, "sls_norms_cov_pattern: " + msg);
   HIPCHK(L->ctx, hipSetDevice(L->dev));
   void* arena = nullptr;
-  size_t bytes = 0, b_pair = 0;
+  size_t bytes = 0;
+  const int32_t* d_pair = nullptr;
+  double* d_cov = nullptr;
   if (npairs > 0) {
     std::vector<int32_t> pr;
     try { pr.resize(2 * (size_t)npairs); } catch (const std::bad_alloc&) { return fail(L->ctx, SLS_ENOMEM, "sls_norms_cov_pattern: out of memory"); }
@@ -626,20 +614,19 @@ int sls_norms_cov_pattern(sls_norms* L, int64_t npairs, const int64_t* pair_i, c
       pr[2 * (size_t)p] = (int32_t)(pair_i[p] - L->index_base);
       pr[2 * (size_t)p + 1] = (int32_t)(pair_j[p] - L->index_base);
     }
-    b_pair = ((size_t)npairs * 8 + 255) / 256 * 256;
-    bytes = b_pair + ((size_t)npairs * 8 + 255) / 256 * 256;
-    hipError_t e = hipMalloc(&arena, bytes);
-    if (e != hipSuccess) return hipfail(L->ctx, e, "hipMalloc (covariance pattern)");
-    e = hipMemcpy(arena, pr.data(), (size_t)npairs * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(static_cast<unsigned char*>(arena) + b_pair, 0, bytes - b_pair);
+    Arena ar;
+    ar.table(pr, &d_pair);
+    ar.buffer((size_t)npairs, &d_cov);
+    bytes = ar.bytes();
+    if (int rc = ar.commit(L->ctx, &arena, "hipMalloc (covariance pattern)", "sls_norms_cov_pattern: upload")) return rc;
+    const hipError_t e = hipMemset(d_cov, 0, Arena::al((size_t)npairs * 8));
     if (e != hipSuccess) { (void)hipFree(arena); return hipfail(L->ctx, e, "sls_norms_cov_pattern: upload"); }
   }
   const hipError_t idle = hipDeviceSynchronize();                 // the new list is up, and no pass reads the old buffers any more
   if (idle != hipSuccess) { if (arena) (void)hipFree(arena); return hipfail(L->ctx, idle, "sls_norms_cov_pattern: hipDeviceSynchronize"); }
   if (L->cov_arena) (void)hipFree(L->cov_arena);
   L->cov_arena = arena; L->cov_bytes = bytes; L->npairs = npairs;
-  L->d_pair = static_cast<const int32_t*>(arena);
-  L->d_cov = arena ? reinterpret_cast<double*>(static_cast<unsigned char*>(arena) + b_pair) : nullptr;
+  L->d_pair = d_pair; L->d_cov = d_cov;
   return 0;
 }
 

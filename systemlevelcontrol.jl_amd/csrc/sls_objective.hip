@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sls_objective.h"
+#include "sls_wave_util.h"
 
 namespace sls {
 
@@ -23,12 +24,6 @@ namespace {
 
 constexpr int kObjRegs = 4;          // weight registers per lane of the diagonal build
 constexpr int kObjBlock = 256;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);   // a + b == b + a: every lane ends with the same bits
-  return v;
-}
 
 // sum over the 256 threads of a workgroup, fixed tree; result in every thread
 __device__ __forceinline__ double block_sum_f64(double v, double* red) {
@@ -74,7 +69,7 @@ __global__ __launch_bounds__(kObjBlock) void objective_diag_kernel(ObjectivePara
     if (!SON) into = __builtin_fma(g2, z, into);
   };
   // one time step of the column; the sum of norms needs the wave's sum per step (a cross-lane operation: no unrolling across it)
-  auto norm_of = [&](double qt) { qt = wave_sum_f64(qt); return sqrt(hw ? qt : scale * qt); };
+  auto norm_of = [&](double qt) { qt = lane_group_sum<1>(qt); return sqrt(hw ? qt : scale * qt); };
   if (nm <= 64 * kObjRegs) {
     double wr[kObjRegs], gr[kObjRegs];
 #pragma unroll
@@ -105,7 +100,7 @@ __global__ __launch_bounds__(kObjBlock) void objective_diag_kernel(ObjectivePara
   }
   double val;
   if (SON) val = acc + c0;                                               // the same bits in every lane already
-  else { acc = wave_sum_f64(acc); val = hw ? acc + c0 : scale * acc + c0; }
+  else { acc = lane_group_sum<1>(acc); val = hw ? acc + c0 : scale * acc + c0; }
   if (lane == 0) p.col_objective[oi] = val;
 }
 

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sls_residual.h"
+#include "sls_wave_util.h"
 
 namespace sls {
 
@@ -26,14 +27,8 @@ namespace {
 constexpr int kResBlock = 256;
 constexpr int kResCache = 8;         // entries of a row kept in registers across the time steps
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);   // a + b == b + a: every lane ends with the same bits
-  return v;
-}
-
-// maximum of non-negative values (a NaN has already become +inf: resid_max)
-__device__ __forceinline__ double wave_max_f64(double v) {
+// maximum of non-negative values (a NaN has already become +inf: resid_max); not wave_max_f64 of sls_wave_util.h, which is fmax
+__device__ __forceinline__ double wave_resid_max(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = resid_max(v, __shfl_xor(v, off));
   return v;
@@ -129,9 +124,9 @@ __global__ __launch_bounds__(kResBlock) void residual_kernel(ResidualParams p) {
       l1 += fabs(d);
     }
   }
-  mx = wave_max_f64(mx);
-  hmx = wave_max_f64(hmx);
-  l1 = wave_sum_f64(l1);
+  mx = wave_resid_max(mx);
+  hmx = wave_resid_max(hmx);
+  l1 = lane_group_sum<1>(l1);
   if (lane == 0) {
     p.res_inf[sd.out_index] = mx;
     p.halo_inf[sd.out_index] = hmx;

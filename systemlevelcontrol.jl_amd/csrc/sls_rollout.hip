@@ -10,8 +10,8 @@
 // x_k − β_k for the entries of lag 1.
 //
 // The step counter lives on the host and advances at enqueue; the ring slot and the buffer parity are launch arguments, which is
-// why a run refuses a capturing stream.  load, reset, run, stats and the device paths of set_plant / set_weights allocate nothing
-// and never wait.
+// why a run refuses a capturing stream.  The arena, load and set_plant are the shared ones of sls_object.h.  load, reset, run,
+// stats and the device paths of set_plant / set_weights allocate nothing and never wait.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,29 +22,16 @@
 #include "../../include/sls_mi355x.h"
 #include "../../include/sls_mi355x_debug.h"
 #include "sls_internal.h"
+#include "sls_object.h"
 #include "sls_rollout.h"
 #include "sls_symbolic.h"
+#include "sls_wave_util.h"
 
 namespace {
 
 using sls::RolloutParams;
 
 constexpr int kWavesPerBlock = 4;
-
-__global__ void rollout_gather_phi_kernel(const double* __restrict__ values, const int32_t* __restrict__ perm, long long n,
-                                          double* __restrict__ vals) {
-  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) vals[k] = values[perm[k]];
-}
-
-// dst[e][s] = src[from[e]][s] (per_scenario) or src[from[e]] (broadcast): CSC → CSR, scenario innermost; n = nnz·nscen
-__global__ void rollout_gather_plant_kernel(const double* __restrict__ src, const int32_t* __restrict__ from, long long n, long long ns,
-                                            int per_scenario, double* __restrict__ dst) {
-  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const long long e = k / ns, s = k - e * ns;
-  dst[k] = per_scenario ? src[(long long)from[e] * ns + s] : src[from[e]];
-}
 
 // one scenario per thread, rows ascending (sls_rollout.h: STATS)
 __global__ void rollout_stats_kernel(const double* __restrict__ acc_cost, const double* __restrict__ acc_peak, int Nx, int Nu, long long ns,
@@ -63,14 +50,6 @@ __global__ void rollout_stats_kernel(const double* __restrict__ acc_cost, const 
   if (cost) cost[s] = c;
   if (peak_x) peak_x[s] = px;
   if (peak_u) peak_u[s] = pu;
-}
-
-// sum over the lanes that share `lane % SCN` (the scenario slot); result in every lane of the group
-template <int SCN>
-__device__ __forceinline__ double entry_lanes_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= SCN; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // s: ring slot of this step, par: which copies hold x_k and β_k.  w [Nw][nscen] or NULL; x_rec [Nx][nscen] / u_rec [Nu][nscen]
@@ -132,7 +111,7 @@ rollout_step_kernel(RolloutParams p, int s, int par, const double* __restrict__ 
   if (row >= p.Nx) {                                           // actuator that drives no state: u only, counted here
     const int j = p.orphan[row - p.Nx];
     const Acc au = fetch(writer, Nx + j, p.r + j);
-    const double uj = entry_lanes_sum<SCN>(fir(p.u_ptr[j], p.u_ptr[j + 1]));
+    const double uj = sls::lane_group_sum<SCN>(fir(p.u_ptr[j], p.u_ptr[j + 1]));
     if (writer) {
       if (u_rec) u_rec[(long long)j * ns + scen] = uj;
       count(au, Nx + j, uj);
@@ -145,19 +124,19 @@ rollout_step_kernel(RolloutParams p, int s, int par, const double* __restrict__ 
   const Acc ax = fetch(writer, i, p.q + i);
   double xv = 0.0, bv = 0.0;                                   // x_k[i], β_k[i] of the lane that stores ŵ_k[i]
   if (writer) { xv = p.x[cur]; bv = p.beta[cur]; }
-  const double beta = entry_lanes_sum<SCN>(fir(p.beta_ptr[i], p.beta_ptr[i + 1]));
+  const double beta = sls::lane_group_sum<SCN>(fir(p.beta_ptr[i], p.beta_ptr[i + 1]));
   double part = 0.0;                                           // A⁽ˢ⁾·x_k + B1·w_k, this lane's share
   for (int e = p.A_ptr[i] + le; e < p.A_ptr[i + 1]; e += NE) part = fma(p.A_val[(long long)e * ns + sc], xk[(long long)p.A_idx[e] * ns], part);
   if (w) {
     const double* __restrict__ wk = w + sc;
     for (int e = p.B1_ptr[i] + le; e < p.B1_ptr[i + 1]; e += NE) part = fma(p.B1_val[e], wk[(long long)p.B1_idx[e] * ns], part);
   }
-  double xi = entry_lanes_sum<SCN>(part);
+  double xi = sls::lane_group_sum<SCN>(part);
   for (int e = p.B2_ptr[i]; e < p.B2_ptr[i + 1]; ++e) {
     const int j = p.B2_idx[e];
     const bool mine = writer && p.B2_own[e];
     const Acc au = fetch(mine, Nx + j, p.r + j);
-    const double uj = entry_lanes_sum<SCN>(fir(p.u_ptr[j], p.u_ptr[j + 1]));
+    const double uj = sls::lane_group_sum<SCN>(fir(p.u_ptr[j], p.u_ptr[j + 1]));
     xi = fma(p.B2_val[(long long)e * ns + sc], uj, xi);
     if (writer && u_rec) u_rec[(long long)j * ns + scen] = uj;
     if (mine) count(au, Nx + j, uj);
@@ -198,11 +177,11 @@ hipError_t launch_rollout_step(int scn, const RolloutParams& p, int s, int par, 
 struct sls_rollout {
   sls_ctx* ctx = nullptr;
   int dev = 0;
-  int64_t n_entries = 0, nnzA = 0, nnzB = 0;
+  int64_t n_entries = 0;
   void* arena = nullptr;               // tables, Φ in row order, weights, plant values, staging, results, state
-  const int32_t *d_perm = nullptr, *d_A_src = nullptr, *d_B2_src = nullptr;
-  double *d_vals = nullptr, *d_A_val = nullptr, *d_B2_val = nullptr, *d_q = nullptr, *d_r = nullptr;
-  double* d_stage = nullptr;           // max(nnz(A), nnz(B₂))·nscen doubles: where the host path of set_plant lands
+  const int32_t* d_perm = nullptr;
+  double *d_vals = nullptr, *d_q = nullptr, *d_r = nullptr;
+  sls::PlantEnsemble plant;
   double* d_result = nullptr;          // [3][nscen]: cost, peak_x, peak_u of sls_rollout_fetch
   RolloutParams kp{};
   int scn = 1;                         // scenario slots per wave: smallest power of two ≥ nscen, at most 64
@@ -224,112 +203,63 @@ int enqueue_stats(sls_rollout* L, hipStream_t st, double* d_cost, double* d_peak
   return 0;
 }
 
-int enqueue_plant_gather(sls_rollout* L, hipStream_t st, const double* d_src, const int32_t* d_from, int64_t nnz, int per_scenario,
-                         double* d_dst) {
-  const long long n = (long long)nnz * L->kp.nscen;
-  if (n == 0) return 0;
-  const int bs = 256;
-  hipLaunchKernelGGL(rollout_gather_plant_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, st, d_src, d_from, n, L->kp.nscen,
-                     per_scenario, d_dst);
-  HIPCHK(L->ctx, hipGetLastError());
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
 
 int sls_rollout_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
                      int64_t nscen, sls_rollout** out) {
-  if (!ctx) return fail(nullptr, SLS_EINVAL, "sls_rollout_plan: null context");
-  if (!out || !dims || !P || !Sx || !Su) return fail(ctx, SLS_EINVAL, "sls_rollout_plan: null argument");
-  *out = nullptr;
-  if (dev_slot < 0 || dev_slot >= (int)ctx->devs.size()) return fail(ctx, SLS_EINVAL, "sls_rollout_plan: dev_slot out of range");
-  if (nscen < 1) return fail(ctx, SLS_EINVAL, "sls_rollout_plan: nscen must be >= 1");
-  if (nscen > 65535LL * 64) return fail(ctx, SLS_EUNSUPPORTED, "sls_rollout_plan: nscen exceeds 65535 chunks of 64 scenarios");
+  int rc = check_plan_args(ctx, "sls_rollout_plan", out, dims && P && Sx && Su, dev_slot, nscen);
+  if (rc) return rc;
   RolloutTables Tb;
   std::string msg;
-  int rc = build_rollout_tables(dims, P, Sx, Su, Tb, msg);
+  rc = build_rollout_tables(dims, P, Sx, Su, Tb, msg);
   if (rc) return fail(ctx, rc, "sls_rollout_plan: " + msg);
   FirOperator& F = Tb.F;
   if (F.Nx + F.Nu > 0x7ffffff0LL) return fail(ctx, SLS_EUNSUPPORTED, "sls_rollout_plan: Nx + Nu exceeds int32");
-  const int64_t n_gather = (int64_t)std::max(F.A.val.size(), F.B2.val.size()) * nscen;
-  if (n_gather / 256 + 1 > 0x7fffffffLL) return fail(ctx, SLS_EUNSUPPORTED, "sls_rollout_plan: nnz·nscen exceeds the gather's grid");
+  if ((rc = PlantEnsemble::check_size(ctx, "sls_rollout_plan", F.A.val.size(), F.B2.val.size(), nscen))) return rc;
   sls_rollout* L = new (std::nothrow) sls_rollout();
   if (!L) return fail(ctx, SLS_ENOMEM, "sls_rollout_plan: out of memory");
   L->ctx = ctx; L->dev = ctx->devs[dev_slot];
-  L->n_entries = (int64_t)F.hoff.size(); L->nnzA = (int64_t)F.A.val.size(); L->nnzB = (int64_t)F.B2.val.size();
+  L->n_entries = (int64_t)F.hoff.size();
   hipError_t e = hipSetDevice(L->dev);
   if (e != hipSuccess) { delete L; return hipfail(ctx, e, "hipSetDevice"); }
   // one arena: uploaded tables first, then the buffers the object owns
-  struct Req { const void* src; size_t bytes; const void** out; };
-  std::vector<Req> reqs;
-  auto add = [&](const auto& v, const auto** o) { reqs.push_back({v.data(), v.size() * sizeof(v[0]), reinterpret_cast<const void**>(o)}); };
+  Arena ar;
   RolloutParams& kp = L->kp;
-  add(F.beta_ptr, &kp.beta_ptr); add(F.u_ptr, &kp.u_ptr); add(F.hoff, &kp.hoff); add(F.perm, &L->d_perm);
-  add(F.A.ptr, &kp.A_ptr); add(F.A.idx, &kp.A_idx); add(F.B1.ptr, &kp.B1_ptr); add(F.B1.idx, &kp.B1_idx); add(F.B1.val, &kp.B1_val);
-  add(F.B2.ptr, &kp.B2_ptr); add(F.B2.idx, &kp.B2_idx); add(F.orphan, &kp.orphan);
-  add(Tb.A_src, &L->d_A_src); add(Tb.B2_src, &L->d_B2_src); add(Tb.b2_owner, &kp.B2_own);
-  std::vector<double> ones((size_t)(F.Nx + F.Nu), 1.0);
-  const double* d_ones = nullptr;
-  add(ones, &d_ones);                                          // q then r
-  auto al = [](size_t b) { return (std::max<size_t>(b, 16) + 255) / 256 * 256; };
-  size_t total = 0;
-  for (auto& r : reqs) total += al(r.bytes);
-  const size_t D = sizeof(double);
-  const size_t b_vals = al((size_t)L->n_entries * D), b_A = al((size_t)(L->nnzA * nscen) * D), b_B = al((size_t)(L->nnzB * nscen) * D);
-  const size_t b_stage = al((size_t)n_gather * D), b_res = al((size_t)(3 * nscen) * D);
-  const size_t b_hist = al((size_t)controller_hist_doubles(F.Nx, F.T, nscen) * D), b_beta = al((size_t)controller_beta_doubles(F.Nx, nscen) * D);
-  const size_t b_x = al((size_t)(2 * F.Nx * nscen) * D), b_acc = al((size_t)((F.Nx + F.Nu) * nscen) * D);
-  const size_t off_vals = total, off_A = off_vals + b_vals, off_B = off_A + b_A, off_stage = off_B + b_B, off_res = off_stage + b_stage;
-  L->state_off = off_res + b_res;
-  L->state_bytes = b_hist + b_beta + b_x + 2 * b_acc;
-  L->plant_bytes = b_A + b_B;
-  e = hipMalloc(&L->arena, L->state_off + L->state_bytes);
-  if (e != hipSuccess) { delete L; return hipfail(ctx, e, "hipMalloc (rollout)"); }
-  unsigned char* base = static_cast<unsigned char*>(L->arena);
-  size_t off = 0;
-  for (auto& r : reqs) {
-    if (r.bytes) {
-      e = hipMemcpy(base + off, r.src, r.bytes, hipMemcpyHostToDevice);
-      if (e != hipSuccess) { (void)hipFree(L->arena); delete L; return hipfail(ctx, e, "hipMemcpy H2D (rollout tables)"); }
-    }
-    *r.out = base + off;
-    off += al(r.bytes);
-  }
-  L->d_q = const_cast<double*>(d_ones); L->d_r = L->d_q + F.Nx;
-  kp.q = L->d_q; kp.r = L->d_r;
-  L->d_vals = reinterpret_cast<double*>(base + off_vals); kp.vals = L->d_vals;
-  L->d_A_val = reinterpret_cast<double*>(base + off_A); kp.A_val = L->d_A_val;
-  L->d_B2_val = reinterpret_cast<double*>(base + off_B); kp.B2_val = L->d_B2_val;
-  L->d_stage = reinterpret_cast<double*>(base + off_stage);
-  L->d_result = reinterpret_cast<double*>(base + off_res);
-  unsigned char* st = base + L->state_off;
-  kp.hist = reinterpret_cast<double*>(st);
-  kp.beta = reinterpret_cast<double*>(st + b_hist);
-  kp.x = reinterpret_cast<double*>(st + b_hist + b_beta);
-  kp.acc_cost = reinterpret_cast<double*>(st + b_hist + b_beta + b_x);
-  kp.acc_peak = reinterpret_cast<double*>(st + b_hist + b_beta + b_x + b_acc);
+  ar.table(F.beta_ptr, &kp.beta_ptr); ar.table(F.u_ptr, &kp.u_ptr); ar.table(F.hoff, &kp.hoff); ar.table(F.perm, &L->d_perm);
+  ar.table(F.A.ptr, &kp.A_ptr); ar.table(F.A.idx, &kp.A_idx); ar.table(F.B1.ptr, &kp.B1_ptr); ar.table(F.B1.idx, &kp.B1_idx);
+  ar.table(F.B1.val, &kp.B1_val); ar.table(F.B2.ptr, &kp.B2_ptr); ar.table(F.B2.idx, &kp.B2_idx); ar.table(F.orphan, &kp.orphan);
+  L->plant.lay_out_tables(ar, Tb.A_src, Tb.B2_src);
+  ar.table(Tb.b2_owner, &kp.B2_own);
+  const std::vector<double> ones((size_t)(F.Nx + F.Nu), 1.0);
+  ar.table(ones, &kp.q);                                       // q then r
+  ar.buffer((size_t)L->n_entries, &L->d_vals);
+  L->plant_bytes = L->plant.lay_out_values(ar, nscen);
+  ar.buffer((size_t)(3 * nscen), &L->d_result);
+  L->state_off = ar.bytes();
+  ar.buffer((size_t)controller_hist_doubles(F.Nx, F.T, nscen), &kp.hist);
+  ar.buffer((size_t)controller_beta_doubles(F.Nx, nscen), &kp.beta);
+  ar.buffer((size_t)(2 * F.Nx * nscen), &kp.x);
+  ar.buffer((size_t)((F.Nx + F.Nu) * nscen), &kp.acc_cost);
+  ar.buffer((size_t)((F.Nx + F.Nu) * nscen), &kp.acc_peak);
+  L->state_bytes = ar.bytes() - L->state_off;
+  rc = ar.commit(ctx, &L->arena, "hipMalloc (rollout)", "hipMemcpy H2D (rollout tables)");
+  if (rc) { delete L; return rc; }
+  L->d_q = const_cast<double*>(kp.q); L->d_r = L->d_q + F.Nx;
+  kp.r = L->d_r;
+  kp.vals = L->d_vals; kp.A_val = L->plant.d_A_val; kp.B2_val = L->plant.d_B2_val;
   kp.Nx = (int32_t)F.Nx; kp.Nu = (int32_t)F.Nu; kp.Nw = (int32_t)F.Nw; kp.T = (int32_t)F.T; kp.R = (int32_t)controller_ring_slots(F.T);
   kp.n_orphan = (int32_t)F.orphan.size();
   kp.nscen = nscen;
-  while (L->scn < 64 && L->scn < nscen) L->scn <<= 1;
-  // every scenario starts from P's values: the broadcast gather from the CSC arrays, staged like a host-path set_plant
-  rc = 0;
-  const double* init[2] = {P->A->nzval, P->B2->nzval};
-  const int64_t nnz[2] = {L->nnzA, L->nnzB};
-  const int32_t* from[2] = {L->d_A_src, L->d_B2_src};
-  double* dst[2] = {L->d_A_val, L->d_B2_val};
-  for (int m = 0; m < 2 && e == hipSuccess && !rc; ++m) {
-    if (!nnz[m]) continue;
-    if (init[m]) e = hipMemcpy(L->d_stage, init[m], (size_t)nnz[m] * D, hipMemcpyHostToDevice);
-    else { std::vector<double> one((size_t)nnz[m], 1.0); e = hipMemcpy(L->d_stage, one.data(), (size_t)nnz[m] * D, hipMemcpyHostToDevice); }
-    if (e == hipSuccess) rc = enqueue_plant_gather(L, nullptr, L->d_stage, from[m], nnz[m], 0, dst[m]);
-    if (e == hipSuccess && !rc) e = hipDeviceSynchronize();
+  L->scn = scenario_slots(nscen);
+  rc = L->plant.init_from(ctx, P, "sls_rollout_plan: upload");
+  if (!rc) {
+    e = hipMemset(static_cast<unsigned char*>(L->arena) + L->state_off, 0, L->state_bytes);   // the state after a reset
+    if (e == hipSuccess) e = hipDeviceSynchronize();           // plan time may wait; the calls below do not
+    if (e != hipSuccess) rc = hipfail(ctx, e, "sls_rollout_plan: upload");
   }
-  if (e == hipSuccess && !rc) e = hipMemset(base + L->state_off, 0, L->state_bytes);      // the state after a reset
-  if (e == hipSuccess && !rc) e = hipDeviceSynchronize();                                   // plan time may wait; the calls below do not
-  if (e != hipSuccess || rc) { (void)hipFree(L->arena); delete L; return rc ? rc : hipfail(ctx, e, "sls_rollout_plan: upload"); }
+  if (rc) { (void)hipFree(L->arena); delete L; return rc; }
   *out = L;
   return 0;
 }
@@ -338,38 +268,16 @@ int sls_rollout_load(sls_rollout* L, void* hip_stream, const double* d_values) {
   if (!L) return fail(nullptr, SLS_EINVAL, "sls_rollout_load: null rollout");
   if (!d_values && L->n_entries > 0) return fail(L->ctx, SLS_EINVAL, "sls_rollout_load: null device pointer");
   HIPCHK(L->ctx, hipSetDevice(L->dev));
-  if (L->n_entries > 0) {                                      // Φ: mask order → row order
-    const int bs = 256;
-    hipLaunchKernelGGL(rollout_gather_phi_kernel, dim3((unsigned)((L->n_entries + bs - 1) / bs)), dim3(bs), 0,
-                       static_cast<hipStream_t>(hip_stream), d_values, L->d_perm, (long long)L->n_entries, L->d_vals);
-    HIPCHK(L->ctx, hipGetLastError());
-  }
+  // Φ: mask order → row order
+  if (int rc = launch_gather_phi(L->ctx, d_values, L->d_perm, L->n_entries, L->d_vals, static_cast<hipStream_t>(hip_stream))) return rc;
   L->loaded = true;
   return 0;
 }
 
 int sls_rollout_set_plant(sls_rollout* L, void* hip_stream, const double* A_nzval, const double* B2_nzval, int on_device, int per_scenario) {
   if (!L) return fail(nullptr, SLS_EINVAL, "sls_rollout_set_plant: null rollout");
-  sls_ctx* ctx = L->ctx;
-  HIPCHK(ctx, hipSetDevice(L->dev));
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  const double* src[2] = {A_nzval, B2_nzval};
-  const int64_t nnz[2] = {L->nnzA, L->nnzB};
-  const int32_t* from[2] = {L->d_A_src, L->d_B2_src};
-  double* dst[2] = {L->d_A_val, L->d_B2_val};
-  for (int m = 0; m < 2; ++m) {
-    if (!src[m] || !nnz[m]) continue;
-    const double* d_src = src[m];
-    if (!on_device) {                                          // host arrays land in the staging buffer; the caller's array is free on return
-      const size_t bytes = (size_t)nnz[m] * (per_scenario ? (size_t)L->kp.nscen : 1) * sizeof(double);
-      HIPCHK(ctx, hipMemcpyAsync(L->d_stage, src[m], bytes, hipMemcpyHostToDevice, st));
-      HIPCHK(ctx, hipStreamSynchronize(st));
-      d_src = L->d_stage;
-    }
-    int rc = enqueue_plant_gather(L, st, d_src, from[m], nnz[m], per_scenario ? 1 : 0, dst[m]);
-    if (rc) return rc;
-  }
-  return 0;
+  HIPCHK(L->ctx, hipSetDevice(L->dev));
+  return L->plant.set(L->ctx, static_cast<hipStream_t>(hip_stream), A_nzval, B2_nzval, on_device, per_scenario);
 }
 
 int sls_rollout_set_weights(sls_rollout* L, void* hip_stream, const double* q, const double* rr, int on_device) {

@@ -47,6 +47,15 @@ __device__ __forceinline__ int wave_max_i32(int v) {
   for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
   return v;
 }
+// sum over the lanes that share `lane % G` (G = 1: the whole wave, G = 64: nothing to add): the xor butterfly 32, 16, … G.
+// a + b == b + a bit for bit, so every lane of a group ends with the same double.  The evaluation passes over a written Φ use
+// this one; their documented summation orders end in exactly this sequence.
+template <int G>
+__device__ __forceinline__ double lane_group_sum(double v) {
+#pragma unroll
+  for (int off = 32; off >= G; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
 
 // 1/a to ~1 ulp: v_rcp_f64 seed + two Newton steps (the result only feeds a preconditioner)
 __device__ __forceinline__ double fast_rcp(double a) {

@@ -15,13 +15,13 @@ twin the tests compare against, not a second backend.
 from __future__ import annotations
 
 import ctypes as C
-import sys
 
 import numpy as np
 import scipy.sparse as sp
 
 from . import _capi
-from .controller import _dims_of, _ptr
+from ._capi import _dev_ptr, _is_tensor
+from .controller import _dims_of
 
 _DP = C.POINTER(C.c_double)
 
@@ -111,8 +111,7 @@ class ClosedLoopNorms:
 
     def load(self, d_values, stream=None):
         """Φ from the mask-order device array `Plan.execute(packed=False)` fills (tensor or pointer).  Returns self."""
-        t = sys.modules.get("torch")
-        if t is not None and isinstance(d_values, t.Tensor):
+        if _is_tensor(d_values):
             d_values = d_values.data_ptr()
         _capi.check(self._lib.sls_norms_load(self.handle, stream, d_values), self.ctx.handle)
         return self
@@ -126,8 +125,8 @@ class ClosedLoopNorms:
 
     def l1_async(self, row_l1=None, col_l1=None, totals=None, stream=None):
         """the same pass into device tensors / pointers (each may be None); nothing waits"""
-        _capi.check(self._lib.sls_norms_l1(self.handle, stream, _ptr(row_l1, self.N, "row_l1"), _ptr(col_l1, self.Nx, "col_l1"),
-                                           _ptr(totals, 2, "totals")), self.ctx.handle)
+        _capi.check(self._lib.sls_norms_l1(self.handle, stream, _dev_ptr(row_l1, self.N, "row_l1"), _dev_ptr(col_l1, self.Nx, "col_l1"),
+                                           _dev_ptr(totals, 2, "totals")), self.ctx.handle)
 
     def hinf(self, omega, iters=32, stream=None):
         """(sigma [nfreq], peak, argpeak) on the host for the angles `omega` (radians per sample): sigma[f] is a lower bound of
@@ -144,7 +143,7 @@ class ClosedLoopNorms:
         waited for, by the next call that needs the pinned buffer"""
         om = np.ascontiguousarray(np.atleast_1d(omega), dtype=np.float64)
         _capi.check(self._lib.sls_norms_hinf(self.handle, stream, om.ctypes.data_as(_DP), om.size, int(iters),
-                                             _ptr(sigma, om.size, "sigma"), _ptr(peak, 2, "peak")), self.ctx.handle)
+                                             _dev_ptr(sigma, om.size, "sigma"), _dev_ptr(peak, 2, "peak")), self.ctx.handle)
 
     def h2(self, stream=None):
         """(row_h2 [N], col_h2 [Nx], totals [2]) on the host: row_h2[i] = Σ_t Σ_j G[t][i,j]², the variance of z_i under unit white
@@ -157,8 +156,8 @@ class ClosedLoopNorms:
 
     def h2_async(self, row_h2=None, col_h2=None, totals=None, stream=None):
         """the same pass into device tensors / pointers (each may be None); nothing waits"""
-        _capi.check(self._lib.sls_norms_h2(self.handle, stream, _ptr(row_h2, self.N, "row_h2"), _ptr(col_h2, self.Nx, "col_h2"),
-                                           _ptr(totals, 2, "totals")), self.ctx.handle)
+        _capi.check(self._lib.sls_norms_h2(self.handle, stream, _dev_ptr(row_h2, self.N, "row_h2"), _dev_ptr(col_h2, self.Nx, "col_h2"),
+                                           _dev_ptr(totals, 2, "totals")), self.ctx.handle)
 
     def set_covariance_pattern(self, pairs_i, pairs_j):
         """The entries (pairs_i[p], pairs_j[p]) of Σ = Σ_t G[t]·G[t]ᵀ that `covariance` evaluates, in the index base of the
@@ -180,7 +179,7 @@ class ClosedLoopNorms:
 
     def covariance_async(self, out, stream=None):
         """the same pass into a device tensor / pointer of npairs doubles; nothing waits"""
-        _capi.check(self._lib.sls_norms_cov(self.handle, stream, _ptr(out, self.npairs, "out")), self.ctx.handle)
+        _capi.check(self._lib.sls_norms_cov(self.handle, stream, _dev_ptr(out, self.npairs, "out")), self.ctx.handle)
 
     def close(self):
         if getattr(self, "handle", None):

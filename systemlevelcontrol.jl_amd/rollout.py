@@ -16,28 +16,13 @@ libsls_mi355x.so (sls_rollout_*: one HIP kernel per step); this module only mars
 from __future__ import annotations
 
 import ctypes as C
-import sys
 
 import numpy as np
 
 from . import _capi
+from ._capi import _dev_ptr, _is_tensor, plant_value_args
 
 _dp = C.POINTER(C.c_double)
-
-
-def _is_tensor(a):
-    t = sys.modules.get("torch")
-    return t is not None and isinstance(a, t.Tensor)
-
-
-def _dev_ptr(a, n, what):
-    """device pointer of a torch tensor (checked: float64, contiguous, on a GPU, n elements) or a raw pointer / None"""
-    if _is_tensor(a):
-        t = sys.modules["torch"]
-        if not a.is_cuda or a.dtype != t.float64 or not a.is_contiguous() or a.numel() != n:
-            raise ValueError(f"{what} must be a contiguous float64 device tensor of {n} elements")
-        return a.data_ptr()
-    return a
 
 
 class Rollout:
@@ -90,25 +75,11 @@ class Rollout:
         """New plant values in the CSC nzval order of the plan's A / B2 (what `Plan.plant_values()` returns): each None (kept), a
         host array, or a device tensor (both must then be tensors, or one None).  per_scenario=False: nnz values for all
         scenarios; True: [nnz, nscen].  The values are not validated."""
-        given = [(name, v, nnz) for name, v, nnz in (("A", A, self.nnz_A), ("B2", B2, self.nnz_B2)) if v is not None]
-        if not given:
+        args = plant_value_args(A, B2, self.nnz_A, self.nnz_B2, self.nscen, per_scenario)
+        if args is None:
             return
-        dev = [_is_tensor(v) for _, v, _ in given]
-        if any(dev) != all(dev):
-            raise ValueError("set_plant: A and B2 must both be host arrays or both be device tensors")
-        ptrs, keep = {"A": None, "B2": None}, []
-        for name, v, nnz in given:
-            n = nnz * (self.nscen if per_scenario else 1)
-            if dev[0]:
-                ptrs[name] = _dev_ptr(v, n, f"set_plant: {name}")
-            else:
-                a = np.ascontiguousarray(v, dtype=np.float64)
-                if a.size != n:
-                    raise ValueError(f"set_plant: {name} has {a.size} values, expected {n}")
-                keep.append(a)
-                ptrs[name] = a.ctypes.data
-        _capi.check(self._lib.sls_rollout_set_plant(self.handle, stream, ptrs["A"], ptrs["B2"], int(dev[0]), int(bool(per_scenario))),
-                    self.ctx.handle)
+        pA, pB2, on_device, _keep = args
+        _capi.check(self._lib.sls_rollout_set_plant(self.handle, stream, pA, pB2, on_device, int(bool(per_scenario))), self.ctx.handle)
 
     def set_weights(self, q=None, r=None, stream=None):
         """q [Nx], r [Nu]: each None (kept), a host array or a device tensor — `Plan.weights()` can be passed as it is"""
