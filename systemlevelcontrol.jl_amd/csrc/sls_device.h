@@ -1,5 +1,5 @@
 // sls_device.h — host/device shared structures of the batched H2 column solver.
-// Plain structs only; included by both the C-ABI host code (sls_api.cpp and its neighbours) and the
+// Plain structs only; included by both the C-ABI host code (sls_api.cpp, sls_plan_update.cpp, …) and the
 // HIP kernels (sls_kernels.hip).
 #pragma once
 #include <stdint.h>

@@ -34,7 +34,7 @@ struct sls_ctx {
     void* ltab = nullptr; size_t ltab_bytes = 0; bool ltab_in_use = false;         // device-built tables of the localized route (same idea)
     // pinned staging ring of the download (sls_plan_download): kDlLanes lanes, each its own stream and pinned chunk
     void* pinned = nullptr; size_t pinned_bytes = 0;
-    // sls_plan_update_plant leaves an asynchronous H2D copy reading the pinned buffer: the next user waits for this event first.
+    // An update leaves an asynchronous H2D copy reading the pinned buffer (pinned_read_until): the next user waits for this event first.
     // Plain state like the "in use" flags above: it relies on the same rule, one thread at a time per context.
     hipEvent_t pinned_busy = nullptr; bool pinned_pending = false;
     std::vector<hipStream_t> dl_streams;
@@ -49,9 +49,15 @@ int hipfail(sls_ctx* ctx, hipError_t e, const char* what);
 // a plan / loop object may outlive its context (host-language GC order): checked before touching it
 bool ctx_is_live(const sls_ctx* ctx);
 // The context slot's pinned staging memory (created on first use, 8 MiB): nullptr when unavailable or too small.  Waits first
-// for an asynchronous H2D copy that still reads it (Slot::pinned_pending); whoever leaves such a copy behind records
-// Slot::pinned_busy after it and sets pinned_pending.
+// for an asynchronous H2D copy that still reads it (Slot::pinned_pending); whoever has enqueued such a copy on `st` says "the
+// buffer is read until here" with pinned_read_until: nothing else sets Slot::pinned_busy and Slot::pinned_pending.
 unsigned char* slot_pinned(sls_ctx* ctx, int slot, size_t bytes);
+int pinned_read_until(sls_ctx* ctx, int slot, hipStream_t st);
+// Host values to a device staging array on `st`: a → d_stage[0, na), b → d_stage[na, na + nb); a NULL array, or one of length 0,
+// enqueues nothing.  Through the pinned buffer when it takes na + nb doubles; else from the caller's arrays, and `st` is waited for.
+int stage_to_device(sls_ctx* ctx, int slot, hipStream_t st, double* d_stage, const double* a, size_t na, const double* b, size_t nb);
+// Device bytes to the host on `st`, which is waited for: through the pinned buffer when it fits, else straight into `dst`.
+int fetch_to_host(sls_ctx* ctx, int slot, hipStream_t st, void* dst, const void* d_src, size_t bytes);
 // the launchers of the .hip units
 hipError_t launch_general(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool wide);
 hipError_t launch_scatter(const double* src, const int64_t* idx, int64_t n, double* dst, hipStream_t stream);

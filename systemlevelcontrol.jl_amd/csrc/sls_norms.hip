@@ -432,14 +432,8 @@ int enqueue_hinf(sls_norms* L, hipStream_t st, const double* omega, int64_t nfre
   for (int t = 0; t < T; ++t)
     for (int f = 0; f < F; ++f) norms_twiddle(omega[f], t, tw[2 * ((size_t)t * F + f)], tw[2 * ((size_t)t * F + f) + 1]);
   HIPCHK(ctx, hipMemcpyAsync(L->d_tw, tw, tw_bytes, hipMemcpyHostToDevice, st));
-  if (pinned) {
-    sls_ctx::Slot& sl = ctx->slots[L->slot];
-    if (!sl.pinned_busy) HIPCHK(ctx, hipEventCreateWithFlags(&sl.pinned_busy, hipEventDisableTiming));
-    HIPCHK(ctx, hipEventRecord(sl.pinned_busy, st));
-    sl.pinned_pending = true;
-  } else {
-    HIPCHK(ctx, hipStreamSynchronize(st));
-  }
+  if (!pinned) HIPCHK(ctx, hipStreamSynchronize(st));
+  else if (int rc = pinned_read_until(ctx, L->slot, st)) return rc;
   const int scn = scenario_slots(F);
   double* res_sigma = L->d_res + N + Nx + 2;
   const long long nv = (long long)Nx * F;
@@ -468,12 +462,7 @@ int enqueue_hinf(sls_norms* L, hipStream_t st, const double* omega, int64_t nfre
 
 // n doubles of an object-owned device buffer to the host, after waiting for `st`
 int fetch_from(sls_norms* L, hipStream_t st, const double* d_src, size_t n, double* stage_out) {
-  const size_t bytes = n * sizeof(double);
-  double* pin = reinterpret_cast<double*>(slot_pinned(L->ctx, L->slot, bytes));
-  HIPCHK(L->ctx, hipMemcpyAsync(pin ? pin : stage_out, d_src, bytes, hipMemcpyDeviceToHost, st));
-  HIPCHK(L->ctx, hipStreamSynchronize(st));
-  if (pin) std::memcpy(stage_out, pin, bytes);
-  return 0;
+  return fetch_to_host(L->ctx, L->slot, st, stage_out, d_src, n * sizeof(double));
 }
 
 // the plan-owned result buffer [off, off + n) to the host, after waiting for `st`

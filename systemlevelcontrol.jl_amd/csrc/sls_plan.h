@@ -1,5 +1,5 @@
-// sls_plan.h — the resident plan as the units behind the C ABI see it: sls_api.cpp builds, runs and destroys it, sls_dropin.cpp
-// (the one-shot calls) and sls_debug.cpp (include/sls_mi355x_debug.h) are its clients.
+// sls_plan.h — the resident plan as the units behind the C ABI see it: sls_api.cpp builds, runs and destroys it, sls_plan_update.cpp
+// (updates and partial re-solves), sls_dropin.cpp (the one-shot calls) and sls_debug.cpp (include/sls_mi355x_debug.h) are its clients.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -140,7 +140,7 @@ struct PlanOpts {
   int host_tables = -1;                             // mask / destination tables: 1 built on the host, 0 expanded on the device, -1 = SLS_HOST_TABLES decides
 };
 
-// sls_api.cpp
+// sls_api.cpp (what sls_plan_update.cpp needs of it: wait_plan_done, enqueue_launches, launch_twisted4_prepares)
 double now_s();
 int plan_create(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
                 int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, int64_t group_begin, int64_t group_end,
@@ -150,6 +150,19 @@ int plan_create_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dims, cons
 // Host waits for the plan's last execute (and for nothing else on the device: a status read or a download must not stall on
 // a collective or on another plan running on some other stream).
 int wait_plan_done(sls_plan* pl);
+// A run over a subset of the columns (sls_plan_execute_columns): the compacted order of compact_order_kernel, laid out like the
+// plan's own order, with the host's copy of the per-launch counts.
+struct SelectedRun {
+  const int32_t* order;     // device
+  const int32_t* pos;       // device: position of each kept item in its launch (the four-wave records are indexed by it)
+  const int32_t* count;     // host: work items kept per launch
+};
+// The launches of one execute on the caller's stream `st`: launch 0 there, the others on plan-owned streams that fork from /
+// join back into it (event edges only; nothing blocks the host).  sel = NULL: every launch in full.  Otherwise the same kernels,
+// LDS plans, workspaces and launch parameters over the kept items of each launch; a launch that keeps none is skipped.
+int enqueue_launches(sls_plan* plan, const KernelParams& kp, hipStream_t st, const SelectedRun* sel);
+// the prepared records of every four-wave launch of the plan, from the operator values the plan holds now
+hipError_t launch_twisted4_prepares(sls_plan* pl, hipStream_t stream);
 // the plan's own status words, without those of an attached refinement (sls_plan_fetch_status merges the two)
 int fetch_status_raw(sls_plan* plan, int32_t* col_status, double* residual, int32_t* iters);
 // the groups select_refinement_groups (sls_dropin_host.h) names get a second plan on the tile kernel (PlanOpts::force_tile), run

@@ -197,6 +197,22 @@ def test_edges(slc, gpu_ctx, cases):
     nrm.close()
 
 
+def test_hinf_twiddles_without_the_pinned_buffer(slc, gpu_ctx, cases, monkeypatch):
+    """With SLS_PAGEABLE_D2H=1 no pinned buffer is handed out: the twiddles are copied from a pageable array and waited for, and
+    the results come straight into the caller's arrays.  σ, peak and argmax equal bitwise those of the run through the pinned buffer.
+    T2 is the smallest case whose twiddles are not all 1 (T1: t = 0 only)."""
+    monkeypatch.delenv("SLS_PAGEABLE_D2H", raising=False)
+    nrm = _norms(slc, gpu_ctx, cases["T2"])
+    try:
+        s, pk, ar = nrm.hinf(nc.PARITY_OMEGAS, iters=nc.PARITY_ITERS)
+        assert len(set(s)) > 1
+        monkeypatch.setenv("SLS_PAGEABLE_D2H", "1")
+        s2, pk2, ar2 = nrm.hinf(nc.PARITY_OMEGAS, iters=nc.PARITY_ITERS)
+        assert np.array_equal(s2, s) and pk2 == pk and ar2 == ar
+    finally:
+        nrm.close()
+
+
 @pytest.mark.parametrize("name", ["ladder", "Nu0", "HOLES"])
 def test_weights_against_prescaled_values(slc, gpu_ctx, cases, name):
     """cz, b random positive against NULL weights on values pre-scaled on the host: one multiply per entry apart.  Both against

@@ -360,6 +360,67 @@ def test_execute_update_execute_on_one_stream_without_host_waits(slc, gpu_ctx, m
         plan.close()
 
 
+# ---- the staging of host values: through the context's pinned buffer, or (SLS_PAGEABLE_D2H) from the caller's arrays ----
+
+@pytest.mark.parametrize("halves", ["both", "A", "B2"])
+def test_host_update_without_the_pinned_buffer(slc, gpu_ctx, monkeypatch, halves):
+    """With SLS_PAGEABLE_D2H=1 no pinned buffer is handed out: a host-path update copies from the caller's arrays and waits.  Φ
+    after it equals bitwise what the same plan gave for the same update through the pinned buffer, update_result() == 0 and
+    plant_values() returns exactly the arrays passed (the half not passed keeps P's values)."""
+    P, S, groups, knobs, route, _ = uc.case(slc, "t4")
+    uc.set_knobs(monkeypatch, knobs)
+    monkeypatch.delenv("SLS_PAGEABLE_D2H", raising=False)
+    Q = uc.perturb(P)
+    new = {k: v for k, v in (("A", _nz(Q.A)), ("B2", _nz(Q.B2))) if halves in ("both", k)}
+    held = (new.get("A", _nz(P.A)), new.get("B2", _nz(P.B2)))
+    plan = slc.Plan(gpu_ctx, P, S, groups)
+    try:
+        assert route in plan.describe()
+        dv = plan.alloc_values()
+        phi0 = _phi(plan, dv)
+        plan.update_plant(**new)
+        want = _phi(plan, dv)                                             # through the pinned buffer
+        assert not np.array_equal(want, phi0)
+        plan.update_plant(A=_nz(P.A), B2=_nz(P.B2))
+        assert np.array_equal(_phi(plan, dv), phi0)
+        monkeypatch.setenv("SLS_PAGEABLE_D2H", "1")
+        plan.update_plant(**new)
+        got = _phi(plan, dv)
+        assert plan.update_result() == 0
+        assert all(np.array_equal(g, w) for g, w in zip(plan.plant_values(), held))
+        assert np.array_equal(got, want), np.abs(got - want).max()
+    finally:
+        plan.close()
+
+
+def test_pinned_buffer_is_not_reused_under_an_update_in_flight(slc, gpu_ctx, monkeypatch):
+    """A host-path update leaves an asynchronous copy reading the context's pinned buffer.  The caller's array is overwritten as
+    soon as the call returns, and fetch_status(), which stages through the same buffer, follows at once: the plan still holds the
+    values passed, and its Φ is a fresh plan's on them."""
+    P, S, groups, knobs, route, _ = uc.case(slc, "t4")
+    uc.set_knobs(monkeypatch, knobs)
+    monkeypatch.delenv("SLS_PAGEABLE_D2H", raising=False)
+    Q = uc.perturb(P)
+    plan = slc.Plan(gpu_ctx, P, S, groups)
+    try:
+        dv = plan.alloc_values()
+        _phi(plan, dv)
+        a, b = _nz(Q.A).copy(), _nz(Q.B2).copy()
+        plan.update_plant(A=a, B2=b)
+        a[:] = 7.0; b[:] = -7.0
+        st = plan.fetch_status()[0]
+        hA, hB = plan.plant_values()
+        assert np.all(st == 0)
+        assert np.array_equal(hA, _nz(Q.A)) and np.array_equal(hB, _nz(Q.B2))
+        got = _phi(plan, dv)
+        assert np.abs(got - _oracle(slc, "t4", "pert")).max() < TOL
+        f, repeats = _fresh_phi(slc, gpu_ctx, Q, S, groups)
+        if repeats:
+            assert np.array_equal(got, f), np.abs(got - f).max()
+    finally:
+        plan.close()
+
+
 # ---- an update detaches an attached refinement ----
 
 def test_update_detaches_the_refinement(slc, oracle, gpu_ctx, monkeypatch):

@@ -306,6 +306,72 @@ def test_execute_update_execute_on_one_stream_without_host_waits(slc, gpu_ctx, m
         plan.close()
 
 
+# ---- the staging of host values: through the context's pinned buffer, or (SLS_PAGEABLE_D2H) from the caller's arrays ----
+
+@pytest.mark.parametrize("halves", ["both", "C1", "D12"])
+def test_host_update_without_the_pinned_buffer(slc, gpu_ctx, monkeypatch, halves):
+    """With SLS_PAGEABLE_D2H=1 no pinned buffer is handed out: a host-path update copies from the caller's arrays and waits.  Φ
+    after it equals bitwise what the same plan gave for the same update through the pinned buffer, update_weights_result() == 0
+    and weights() returns exactly the arrays passed (the half not passed keeps seed 11's values)."""
+    P, S, groups, knobs, route, _ = uc.case(slc, "t4")
+    uc.set_knobs(monkeypatch, knobs)
+    monkeypatch.delenv("SLS_PAGEABLE_D2H", raising=False)
+    (cA, dA), (cB, dB) = wc.diagonals(P, A), wc.diagonals(P, B)
+    new = {k: v for k, v in (("C1", cB), ("D12", dB)) if halves in ("both", k)}
+    held = (new.get("C1", cA), new.get("D12", dA))
+    plan = slc.Plan(gpu_ctx, wc.weighted(P, A), S, groups, updatable_weights=True)
+    try:
+        assert route in plan.describe()
+        dv = plan.alloc_values()
+        phi0 = _phi(plan, dv)
+        plan.update_weights(**new)
+        want = _phi(plan, dv)                                             # through the pinned buffer
+        assert not np.array_equal(want, phi0)
+        plan.update_weights(C1=cA, D12=dA)
+        assert np.array_equal(_phi(plan, dv), phi0)
+        monkeypatch.setenv("SLS_PAGEABLE_D2H", "1")
+        plan.update_weights(**new)
+        got = _phi(plan, dv)
+        assert plan.update_weights_result() == 0
+        assert all(np.array_equal(g, w) for g, w in zip(plan.weights(), held))
+        assert np.array_equal(got, want), np.abs(got - want).max()
+    finally:
+        plan.close()
+
+
+def test_pinned_buffer_is_not_reused_under_an_update_in_flight(slc, gpu_ctx, monkeypatch):
+    """A host-path update leaves an asynchronous copy reading the context's pinned buffer.  The caller's arrays are overwritten as
+    soon as the call returns, and fetch_status(), which stages through the same buffer, follows at once: the plan still holds the
+    values passed, and its Φ is a fresh plan's on them."""
+    P, S, groups, knobs, route, _ = uc.case(slc, "t4")
+    uc.set_knobs(monkeypatch, knobs)
+    monkeypatch.delenv("SLS_PAGEABLE_D2H", raising=False)
+    cB, dB = wc.diagonals(P, B)
+    plan = fresh = None
+    try:
+        plan = slc.Plan(gpu_ctx, wc.weighted(P, A), S, groups, updatable_weights=True)
+        dv = plan.alloc_values()
+        _phi(plan, dv)
+        c, d = np.array(cB, dtype=np.float64), np.array(dB, dtype=np.float64)
+        plan.update_weights(C1=c, D12=d)
+        c[:] = 7.0; d[:] = 9.0
+        st = plan.fetch_status()[0]
+        hc, hd = plan.weights()
+        assert np.all(st == 0)
+        assert np.array_equal(hc, cB) and np.array_equal(hd, dB)
+        got = _phi(plan, dv)
+        assert np.abs(got - wc.oracle_flat(slc, "t4", B)).max() < TOL
+        fresh = slc.Plan(gpu_ctx, wc.weighted(P, B), S, groups, updatable_weights=True)
+        fv = fresh.alloc_values()
+        f1 = _phi(fresh, fv); f2 = _phi(fresh, fv)
+        if np.array_equal(f1, f2):
+            assert np.array_equal(got, f1), np.abs(got - f1).max()
+    finally:
+        for p in (plan, fresh):
+            if p is not None:
+                p.close()
+
+
 # ---- an update detaches an attached refinement ----
 
 def test_weights_update_detaches_the_refinement(slc, oracle, gpu_ctx, monkeypatch):
