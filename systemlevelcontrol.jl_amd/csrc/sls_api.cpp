@@ -1,7 +1,9 @@
 // sls_api.cpp — implementation of include/sls_mi355x.h (the drop-in C ABI): the context, its pinned staging buffer, and the resident
 // plans (build, execute, batch, status, objective, residual, download, destroy).  Plant and weights updates and partial re-solves
 // of a plan are in sls_plan_update.cpp, the one-shot calls built on plans (sls_h2_sf_solve ≙ SLS_𝓗₂(P, 𝓢; 𝓘),
-// src/synthesis.jl:11-32) in sls_dropin.cpp, the exports of include/sls_mi355x_debug.h in sls_debug.cpp.
+// src/synthesis.jl:11-32) in sls_dropin.cpp, the three device symbolic passes (sls_localization_masks_device,
+// sls_index_sets_device, sls_h2_sf_plan_localized) in sls_symbolic_device.cpp, the exports of include/sls_mi355x_debug.h in
+// sls_debug.cpp.
 //
 // Host side of the path that replaces reference src/synthesis.jl:11-72:
 //   sls_h2_sf_plan       ≙ the per-column set-up the reference redoes inside the loop
@@ -31,7 +33,6 @@
 #include "sls_residual.h"
 #include "sls_routing.h"
 #include "sls_symbolic.h"
-#include "sls_weights.h"
 
 namespace {
 std::mutex g_err_mu;
@@ -146,13 +147,9 @@ int sls::fetch_to_host(sls_ctx* ctx, int slot, hipStream_t st, void* dst, const 
   return 0;
 }
 
-namespace {
-
-// Device → host copy of a flat array of 8-byte elements into the caller's pageable slices (slice i = elements
-// [beg[i], beg[i+1]) → ptrs[i]): 1 MiB chunks through kDlLanes lanes, each a host thread with its own stream and pinned chunk —
-// DMA at link speed into pinned memory, then a host copy whose first-touch page faults are spread over the lanes and overlap
-// the other lanes' DMA.  Returns 0, a negative error, or 1 when the pinned ring is not available (the caller falls back).
-int pinned_download(sls_ctx* ctx, int slot, int dev, const void* d_src, const std::vector<int64_t>& beg, const std::vector<void*>& ptrs) {
+// (contract: sls_internal.h)  1 MiB chunks through kDlLanes lanes, each a host thread with its own stream and pinned chunk — DMA at
+// link speed into pinned memory, then a host copy whose first-touch page faults are spread over the lanes and overlap the other DMA.
+int sls::pinned_download(sls_ctx* ctx, int slot, int dev, const void* d_src, const std::vector<int64_t>& beg, const std::vector<void*>& ptrs) {
   constexpr int kDlLanes = 8;
   constexpr int64_t kChunk = (1ll << 20) / 8;          // elements per chunk
   const int64_t nsl = (int64_t)ptrs.size(), n_total = beg[nsl];
@@ -190,6 +187,8 @@ int pinned_download(sls_ctx* ctx, int slot, int dev, const void* d_src, const st
   for (hipError_t e : errs) if (e != hipSuccess) return hipfail(ctx, e, "pinned D2H");
   return 0;
 }
+
+namespace {
 
 int arena_commit(sls_plan* pl) {
   auto al = [](size_t b) { return (std::max<size_t>(b, 16) + 255) / 256 * 256; };
@@ -415,211 +414,6 @@ int sls_localization_masks(const sls_dims* dims, const sls_csc_f64* A, const sls
   return rc ? fail(nullptr, rc, msg) : 0;
 }
 
-int sls_localization_masks_device(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_csc_f64* A, const sls_csc_f64* B2,
-                                  int64_t d, double alpha, int64_t* nnz_x, int64_t* nnz_u, int64_t* const* colptr_x,
-                                  int64_t* const* rowval_x, int64_t* const* colptr_u, int64_t* const* rowval_u) {
-  if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
-  if (!dims || !A || !B2 || !nnz_x || !nnz_u) return fail(ctx, SLS_EINVAL, "null argument");
-  if (dev_slot < 0 || dev_slot >= (int)ctx->devs.size()) return fail(ctx, SLS_EINVAL, "dev_slot out of range");
-  std::vector<int32_t> kx, ku, a_cp, a_ri, b_rp, b_ci;
-  int kmax = 0;
-  std::string msg;
-  int rc = mask_recipe_inputs(dims, A, B2, d, alpha, kx, ku, kmax, a_cp, a_ri, b_rp, b_ci, msg);
-  if (rc) return fail(ctx, rc, msg);
-  const bool fill = rowval_x != nullptr;
-  if (fill && (!colptr_x || !colptr_u || !rowval_u)) return fail(ctx, SLS_EINVAL, "null output arrays");
-  const int64_t Nx = dims->Nx, Nu = dims->Nu, T = dims->T;
-  const int base = dims->index_base;
-  const int K1 = kmax + 1;
-  // LDS plan of one wave: two bitmaps (states, inputs) + three level lists
-  const int64_t bm_bytes = ((Nx + 31) / 32 + (std::max<int64_t>(Nu, 1) + 31) / 32) * 4;
-  if (bm_bytes > 96 * 1024) return fail(ctx, SLS_EUNSUPPORTED, "device mask recipe: the state bitmap does not fit LDS (Nx > ≈7e5); use sls_localization_masks");
-  // level lists: 1024 entries to start with (a level is an index set: tens to hundreds of entries); doubled and the count pass
-  // repeated when a level overflows, up to what LDS holds
-  const int cap_limit = (int)std::min<int64_t>(std::max<int64_t>(Nx, Nu), (kMaxLds - bm_bytes) / 12);
-  int cap = std::min(cap_limit, 1024);
-  size_t lds = (size_t)bm_bytes + 12ull * cap;
-  HIPCHK(ctx, hipSetDevice(ctx->devs[dev_slot]));
-  // one arena for everything on the device
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t sz_acp = al(a_cp.size() * 4), sz_ari = al(std::max<size_t>(a_ri.size(), 1) * 4), sz_brp = al(b_rp.size() * 4),
-               sz_bci = al(std::max<size_t>(b_ci.size(), 1) * 4), sz_k = al((size_t)T * 4), sz_cnt = al((size_t)Nx * K1 * 4);
-  const size_t head = sz_acp + sz_ari + sz_brp + sz_bci + 2 * sz_k + 2 * sz_cnt + 256;
-  unsigned char* dbase = nullptr;
-  HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&dbase), head));
-  auto freeall = [&](void* extra) { (void)hipFree(dbase); if (extra) (void)hipFree(extra); };
-  size_t off = 0;
-  auto put = [&](const void* src, size_t bytes, size_t padded) -> void* {
-    void* dptr = dbase + off; off += padded;
-    if (bytes && hipMemcpy(dptr, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return dptr;
-  };
-  MaskParams mp{};
-  mp.Nx = (int32_t)Nx; mp.Nu = (int32_t)Nu; mp.T = (int32_t)T; mp.kmax = kmax; mp.base = base;
-  mp.A_cp = static_cast<const int32_t*>(put(a_cp.data(), a_cp.size() * 4, sz_acp));
-  mp.A_ri = static_cast<const int32_t*>(put(a_ri.data(), a_ri.size() * 4, sz_ari));
-  mp.B_rp = static_cast<const int32_t*>(put(b_rp.data(), b_rp.size() * 4, sz_brp));
-  mp.B_ci = static_cast<const int32_t*>(put(b_ci.data(), b_ci.size() * 4, sz_bci));
-  mp.kx = static_cast<const int32_t*>(put(kx.data(), (size_t)T * 4, sz_k));
-  mp.ku = static_cast<const int32_t*>(put(ku.data(), (size_t)T * 4, sz_k));
-  if (!mp.A_cp || !mp.A_ri || !mp.B_rp || !mp.B_ci || !mp.kx || !mp.ku) { freeall(nullptr); return fail(ctx, SLS_EHIP, "H2D of the plant pattern failed"); }
-  mp.cntx = reinterpret_cast<int32_t*>(dbase + off); off += sz_cnt;
-  mp.cntu = reinterpret_cast<int32_t*>(dbase + off); off += sz_cnt;
-  mp.overflow = reinterpret_cast<int32_t*>(dbase + off);
-  hipError_t e = hipSuccess;
-  std::vector<int32_t> cntx((size_t)Nx * K1), cntu((size_t)Nx * K1);
-  int grid = 1;
-  for (;;) {
-    mp.cap = cap;
-    lds = (size_t)bm_bytes + 12ull * cap;
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)kMaxLds / std::max<size_t>(lds, 1)));
-    grid = (int)std::min<int64_t>(Nx, (int64_t)ctx->ncu[dev_slot] * per_cu);
-    e = hipMemset(mp.overflow, 0, 4);
-    if (e == hipSuccess) e = launch_mask_levels(mp, false, grid, lds, nullptr);
-    int32_t ovf = 0;
-    if (e == hipSuccess) e = hipMemcpy(&ovf, mp.overflow, 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { freeall(nullptr); return hipfail(ctx, e, "device mask recipe (count pass)"); }
-    if (!ovf) break;
-    if (cap >= cap_limit) { freeall(nullptr); return fail(ctx, SLS_EUNSUPPORTED, "device mask recipe: a level set does not fit the LDS list; use sls_localization_masks"); }
-    cap = std::min(cap_limit, 2 * cap);
-  }
-  e = hipMemcpy(cntx.data(), mp.cntx, cntx.size() * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(cntu.data(), mp.cntu, cntu.size() * 4, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) { freeall(nullptr); return hipfail(ctx, e, "device mask recipe (level sizes)"); }
-  // prefix sums over the columns, per level; sizes per time step
-  std::vector<int64_t> prex((size_t)K1 * Nx), preu((size_t)K1 * Nx), totx(K1, 0), totu(K1, 0);
-  for (int k = 0; k < K1; ++k) {
-    int64_t sx = 0, su = 0;
-    for (int64_t c = 0; c < Nx; ++c) { prex[(size_t)k * Nx + c] = sx; preu[(size_t)k * Nx + c] = su; sx += cntx[(size_t)c * K1 + k]; su += cntu[(size_t)c * K1 + k]; }
-    totx[k] = sx; totu[k] = su;
-  }
-  std::vector<int64_t> offx(T + 1, 0), offu(T + 1, 0);
-  for (int64_t t = 0; t < T; ++t) { nnz_x[t] = totx[kx[t]]; nnz_u[t] = totu[ku[t]]; offx[t + 1] = offx[t] + nnz_x[t]; offu[t + 1] = offu[t] + nnz_u[t]; }
-  if (!fill) { freeall(nullptr); return 0; }
-  for (int64_t t = 0; t < T; ++t) {
-    if (!colptr_x[t] || !colptr_u[t] || (nnz_x[t] && !rowval_x[t]) || (nnz_u[t] && !rowval_u[t])) { freeall(nullptr); return fail(ctx, SLS_EINVAL, "null output array for some t"); }
-    const int64_t* px = prex.data() + (size_t)kx[t] * Nx; const int64_t* pu = preu.data() + (size_t)ku[t] * Nx;
-    for (int64_t c = 0; c < Nx; ++c) { colptr_x[t][c] = px[c] + base; colptr_u[t][c] = pu[c] + base; }
-    colptr_x[t][Nx] = nnz_x[t] + base; colptr_u[t][Nx] = nnz_u[t] + base;
-  }
-  const size_t sz_pre = al((size_t)K1 * Nx * 8), sz_off = al((size_t)(T + 1) * 8);
-  const size_t nrow = (size_t)(offx[T] + offu[T]);
-  unsigned char* d2 = nullptr;
-  e = hipMalloc(reinterpret_cast<void**>(&d2), 2 * sz_pre + 2 * sz_off + al(std::max<size_t>(nrow, 1) * 8));
-  if (e != hipSuccess) { freeall(nullptr); return hipfail(ctx, e, "hipMalloc (mask row indices)"); }
-  size_t o2 = 0;
-  auto put2 = [&](const void* src, size_t bytes, size_t padded) -> void* {
-    void* dptr = d2 + o2; o2 += padded;
-    if (hipMemcpy(dptr, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return dptr;
-  };
-  mp.prex = static_cast<const int64_t*>(put2(prex.data(), prex.size() * 8, sz_pre));
-  mp.preu = static_cast<const int64_t*>(put2(preu.data(), preu.size() * 8, sz_pre));
-  mp.offx = static_cast<const int64_t*>(put2(offx.data(), offx.size() * 8, sz_off));
-  mp.offu = static_cast<const int64_t*>(put2(offu.data(), offu.size() * 8, sz_off));
-  if (!mp.prex || !mp.preu || !mp.offx || !mp.offu) { freeall(d2); return fail(ctx, SLS_EHIP, "H2D of the prefix tables failed"); }
-  mp.rowx = reinterpret_cast<int64_t*>(d2 + o2);
-  mp.rowu = mp.rowx + offx[T];
-  e = launch_mask_levels(mp, true, grid, lds, nullptr);
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  if (e != hipSuccess) { freeall(d2); return hipfail(ctx, e, "device mask recipe (fill pass)"); }
-  // row indices → the caller's 2T arrays
-  std::vector<int64_t> beg(2 * T + 1);
-  std::vector<void*> ptrs(2 * T);
-  for (int64_t t = 0; t < T; ++t) { beg[t] = offx[t]; ptrs[t] = rowval_x[t]; beg[T + t] = offx[T] + offu[t]; ptrs[T + t] = rowval_u[t]; }
-  beg[2 * T] = offx[T] + offu[T];
-  rc = pinned_download(ctx, dev_slot, ctx->devs[dev_slot], mp.rowx, beg, ptrs);
-  if (rc > 0) {
-    rc = 0;
-    for (int64_t s2 = 0; s2 < 2 * T && e == hipSuccess; ++s2)
-      if (beg[s2 + 1] > beg[s2]) e = hipMemcpy(ptrs[s2], mp.rowx + beg[s2], (size_t)(beg[s2 + 1] - beg[s2]) * 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = hipfail(ctx, e, "hipMemcpy D2H (mask row indices)");
-  }
-  freeall(d2);
-  return rc;
-}
-
-int sls_index_sets_device(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_csc_f64* A, const sls_csc_bool* Sx_last,
-                          const sls_csc_bool* Su_last, int64_t* sx_ptr, int64_t* sx_idx, int64_t* su_ptr, int64_t* su_idx) {
-  if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
-  if (!dims || !A || !Sx_last || !Su_last || !sx_ptr || !su_ptr) return fail(ctx, SLS_EINVAL, "null argument");
-  if (dev_slot < 0 || dev_slot >= (int)ctx->devs.size()) return fail(ctx, SLS_EINVAL, "dev_slot out of range");
-  const bool fill = sx_idx != nullptr;
-  if (fill && !su_idx) return fail(ctx, SLS_EINVAL, "null output arrays");
-  std::vector<int32_t> a_cp, a_ri, sx_cp, sx_ri, su_cp, su_ri;
-  std::string msg;
-  int rc = index_set_inputs(dims, A, Sx_last, Su_last, a_cp, a_ri, sx_cp, sx_ri, su_cp, su_ri, msg);
-  if (rc) return fail(ctx, rc, msg);
-  const int64_t Nx = dims->Nx, Nu = dims->Nu;
-  const int base = dims->index_base;
-  const int64_t bm_bytes = ((Nx + 31) / 32 + (std::max<int64_t>(Nu, 1) + 31) / 32) * 4;
-  if (bm_bytes > 96 * 1024) return fail(ctx, SLS_EUNSUPPORTED, "device index sets: the state bitmap does not fit LDS (Nx > ≈7e5); use sls_sparsity_dim_reduction");
-  const int cap_limit = (int)std::min<int64_t>(std::max<int64_t>(Nx, Nu), (kMaxLds - bm_bytes) / 4);
-  int cap = std::min(cap_limit, 1024);
-  HIPCHK(ctx, hipSetDevice(ctx->devs[dev_slot]));
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-  const std::vector<int32_t>* up[6] = {&a_cp, &a_ri, &sx_cp, &sx_ri, &su_cp, &su_ri};
-  size_t head = 2 * al((size_t)Nx * 4) + 256;
-  for (auto* v : up) head += al(std::max<size_t>(v->size(), 1) * 4);
-  unsigned char* dbase = nullptr;
-  HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&dbase), head));
-  auto freeall = [&](void* extra) { (void)hipFree(dbase); if (extra) (void)hipFree(extra); };
-  size_t off = 0;
-  const int32_t* dp[6];
-  for (int i = 0; i < 6; ++i) {
-    dp[i] = reinterpret_cast<const int32_t*>(dbase + off);
-    if (!up[i]->empty() && hipMemcpy(dbase + off, up[i]->data(), up[i]->size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-      freeall(nullptr); return fail(ctx, SLS_EHIP, "H2D of the patterns failed");
-    }
-    off += al(std::max<size_t>(up[i]->size(), 1) * 4);
-  }
-  IndexSetParams ip{};
-  ip.Nx = (int32_t)Nx; ip.Nu = (int32_t)Nu; ip.base = base;
-  ip.A_cp = dp[0]; ip.A_ri = dp[1]; ip.Sx_cp = dp[2]; ip.Sx_ri = dp[3]; ip.Su_cp = dp[4]; ip.Su_ri = dp[5];
-  ip.cntx = reinterpret_cast<int32_t*>(dbase + off); off += al((size_t)Nx * 4);
-  ip.cntu = reinterpret_cast<int32_t*>(dbase + off); off += al((size_t)Nx * 4);
-  ip.overflow = reinterpret_cast<int32_t*>(dbase + off);
-  hipError_t e = hipSuccess;
-  int grid = 1;
-  size_t lds = 0;
-  for (;;) {
-    ip.cap = cap;
-    lds = (size_t)bm_bytes + 4ull * cap;
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)kMaxLds / std::max<size_t>(lds, 1)));
-    grid = (int)std::min<int64_t>(Nx, (int64_t)ctx->ncu[dev_slot] * per_cu);
-    e = hipMemset(ip.overflow, 0, 4);
-    if (e == hipSuccess) e = launch_index_sets(ip, false, grid, lds, nullptr);
-    int32_t ovf = 0;
-    if (e == hipSuccess) e = hipMemcpy(&ovf, ip.overflow, 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { freeall(nullptr); return hipfail(ctx, e, "device index sets (count pass)"); }
-    if (!ovf) break;
-    if (cap >= cap_limit) { freeall(nullptr); return fail(ctx, SLS_EUNSUPPORTED, "device index sets: an index set does not fit the LDS list"); }
-    cap = std::min(cap_limit, 2 * cap);
-  }
-  std::vector<int32_t> cntx(Nx), cntu(Nx);
-  e = hipMemcpy(cntx.data(), ip.cntx, (size_t)Nx * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(cntu.data(), ip.cntu, (size_t)Nx * 4, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) { freeall(nullptr); return hipfail(ctx, e, "device index sets (sizes)"); }
-  std::vector<int64_t> px(Nx + 1, 0), pu(Nx + 1, 0);
-  for (int64_t c = 0; c < Nx; ++c) { px[c + 1] = px[c] + cntx[c]; pu[c + 1] = pu[c] + cntu[c]; }
-  for (int64_t c = 0; c <= Nx; ++c) { sx_ptr[c] = px[c] + base; su_ptr[c] = pu[c] + base; }
-  if (!fill) { freeall(nullptr); return 0; }
-  const size_t sz_p = al((size_t)(Nx + 1) * 8), nout = (size_t)(px[Nx] + pu[Nx]);
-  unsigned char* d2 = nullptr;
-  e = hipMalloc(reinterpret_cast<void**>(&d2), 2 * sz_p + al(std::max<size_t>(nout, 1) * 8));
-  if (e != hipSuccess) { freeall(nullptr); return hipfail(ctx, e, "hipMalloc (index sets)"); }
-  e = hipMemcpy(d2, px.data(), (size_t)(Nx + 1) * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d2 + sz_p, pu.data(), (size_t)(Nx + 1) * 8, hipMemcpyHostToDevice);
-  ip.ptrx = reinterpret_cast<const int64_t*>(d2); ip.ptru = reinterpret_cast<const int64_t*>(d2 + sz_p);
-  ip.outx = reinterpret_cast<int64_t*>(d2 + 2 * sz_p); ip.outu = ip.outx + px[Nx];
-  if (e == hipSuccess) e = launch_index_sets(ip, true, grid, lds, nullptr);
-  if (e == hipSuccess && px[Nx]) e = hipMemcpy(sx_idx, ip.outx, (size_t)px[Nx] * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && pu[Nx]) e = hipMemcpy(su_idx, ip.outu, (size_t)pu[Nx] * 8, hipMemcpyDeviceToHost);
-  freeall(d2);
-  if (e != hipSuccess) return hipfail(ctx, e, "device index sets (fill pass)");
-  return 0;
-}
-
 int sls_shard_groups(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
                      int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, int nshards, int64_t* cuts) {
   if (nshards <= 0 || !cuts) return fail(nullptr, SLS_EINVAL, "nshards must be >= 1");
@@ -658,16 +452,6 @@ int sls_h2_sf_packed_layout(const sls_dims* dims, const sls_plant* P, const sls_
   }
   return 0;
 }
-
-struct DeviceTables {            // device-resident symbolic route: tables built on the device, owned by the plan
-  const int32_t* d_idx = nullptr;
-  const uint64_t* d_cmask = nullptr;
-  const int32_t* d_cbase = nullptr;
-  const int64_t* d_coff = nullptr;
-  double t_symbolic_s = 0.0;     // device + host time of the symbolic route (replaces the host pass's share)
-};
-static int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_plan* pl, double t0, bool want_packed, const PlanOpts& opt,
-                       const DeviceTables* dt, sls_plan** plan_out);
 
 int sls_h2_sf_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx,
                    const sls_csc_bool* Su, int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols,
@@ -713,11 +497,9 @@ extern "C++" int sls::plan_create(sls_ctx* ctx, int dev_slot, const sls_dims* di
   return plan_finish(ctx, dev_slot, dims, pl, t0, want_packed, opt, nullptr, plan_out);
 }
 
-// Second half of plan creation, shared by the mask-based route (host symbolic pass above) and the device-resident route
-// (plan_create_localized below): kernel selection, launch list, uploads, workspaces.  `dt` != NULL: the per-column index sets
-// and compact tables already sit in device memory (built by column_tables_kernel) and are used where they are.
-static int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_plan* pl, double t0, bool want_packed, const PlanOpts& opt,
-                       const DeviceTables* dt, sls_plan** plan_out) {
+// second half of plan creation (contract: sls_plan.h)
+extern "C++" int sls::plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_plan* pl, double t0, bool want_packed,
+                                  const PlanOpts& opt, const DeviceTables* dt, sls_plan** plan_out) {
   int rc = 0;
   const double t1 = now_s();
   Symbolic& S = pl->sym;
@@ -959,259 +741,6 @@ static int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_pla
   pool_vec<uint64_t>().swap(S.cmask); pool_vec<int32_t>().swap(S.cbase); pool_vec<int64_t>().swap(S.coff);
   *plan_out = pl;
   return 0;
-}
-
-// ---- device-resident symbolic route (SURVEY §8 row f1 on the solve path; reference README.md:52-54 + src/reduction.jl:14) ----
-// The README's masks are a function of (A, B2, d, α, T).  Instead of receiving them as 2T host arrays (8 B per entry over
-// PCIe, read once by the host pass), this route derives everything a plan needs from the plant pattern ON THE DEVICE: level
-// sets per column (count pass), exclusive prefixes over the columns (the CSC positions), then index sets, compact bit masks
-// and first destinations (fill pass), expanded into the kernels' tables by the same expand_tables_kernel as the host route.
-// Over PCIe: the plant (KBs), 24 B per column of sizes coming back, 64 B per column of descriptors going up.
-extern "C++" int sls::plan_create_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, int64_t d, double alpha,
-                                            sls_plan** plan_out) {
-  if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
-  if (!plan_out) return fail(ctx, SLS_EINVAL, "null plan_out");
-  *plan_out = nullptr;
-  if (dev_slot < 0 || dev_slot >= (int)ctx->devs.size()) return fail(ctx, SLS_EINVAL, "dev_slot out of range");
-  if (!ctx->ridge_x.empty() || !ctx->ridge_u.empty())
-    return fail(ctx, SLS_EUNSUPPORTED, "the device-resident symbolic route does not carry the ridge term of sls_set_ridge; pass the masks to sls_h2_sf_plan");
-  sls_plan* pl = new (std::nothrow) sls_plan();
-  if (!pl) return fail(ctx, SLS_ENOMEM, "out of memory");
-  pl->ctx = ctx; pl->dev = ctx->devs[dev_slot]; pl->slot = dev_slot;
-  const double t0 = now_s();
-  Symbolic& S = pl->sym;
-  S.want_packed = false; S.compact = true;
-  LocalizedHost L;
-  std::string msg;
-  int rc = localized_prepare(dims, P, d, alpha, S, L, msg);
-  if (rc) { delete pl; return fail(ctx, rc, msg); }
-  const int64_t Nx = dims->Nx, Nu = dims->Nu, T = dims->T;
-  pl->gbeg = 0; pl->gend = Nx; pl->ngroups_in = 0;
-  const bool dbg_t = sls_knob("SLS_DEBUG_TIMING") != nullptr;
-  double tdbg = now_s();
-  auto tick = [&](const char* what) { if (dbg_t) { const double n = now_s(); std::fprintf(stderr, "[sls localized] %-34s %8.3f ms\n", what, 1e3 * (n - tdbg)); tdbg = n; } };
-  tick("host: checks, pattern, operator CSR");
-  hipError_t e = hipSetDevice(pl->dev);
-  if (e != hipSuccess) { delete pl; return hipfail(ctx, e, "hipSetDevice"); }
-
-  const int K1 = L.kmax + 1;
-  ColumnTableParams cp{};
-  cp.Nx = (int32_t)Nx; cp.Nu = (int32_t)Nu; cp.T = (int32_t)T; cp.kmax = L.kmax;
-  cp.qx1 = L.kx[T - 1] + 1; cp.qu1 = L.ku[T - 1] + 1;
-  cp.KL = std::max(L.kmax, std::max(cp.qx1, cp.qu1));
-  auto al = [](size_t b) { return (std::max<size_t>(b, 16) + 255) / 256 * 256; };
-  // ---- arena 1 (temporary): patterns, schedule, operator rows for the nnz counts, count-pass outputs, prefixes ----
-  struct Up { const void* src; size_t bytes; void** dst; };
-  const int32_t *d_acp, *d_ari, *d_brp, *d_bci, *d_arp, *d_aci, *d_Brp, *d_Bci, *d_kx, *d_ku;
-  const double *d_av, *d_Bv;
-  std::vector<Up> ups = {
-    {L.a_cp.data(), L.a_cp.size() * 4, (void**)&d_acp}, {L.a_ri.data(), L.a_ri.size() * 4, (void**)&d_ari},
-    {L.b_rp.data(), L.b_rp.size() * 4, (void**)&d_brp}, {L.b_ci.data(), L.b_ci.size() * 4, (void**)&d_bci},
-    {S.A_csr.ptr.data(), S.A_csr.ptr.size() * 4, (void**)&d_arp}, {S.A_csr.idx.data(), S.A_csr.idx.size() * 4, (void**)&d_aci},
-    {S.A_csr.val.data(), S.A_csr.val.size() * 8, (void**)&d_av},
-    {S.B_csr.ptr.data(), S.B_csr.ptr.size() * 4, (void**)&d_Brp}, {S.B_csr.idx.data(), S.B_csr.idx.size() * 4, (void**)&d_Bci},
-    {S.B_csr.val.data(), S.B_csr.val.size() * 8, (void**)&d_Bv},
-    {L.kx.data(), (size_t)T * 4, (void**)&d_kx}, {L.ku.data(), (size_t)T * 4, (void**)&d_ku}};
-  size_t up_bytes = 0;
-  for (auto& u : ups) up_bytes += al(u.bytes);
-  const size_t sz_cnt = al((size_t)Nx * K1 * 4), sz_info = al((size_t)Nx * 6 * 4), sz_pre = al((size_t)K1 * Nx * 8), sz_tot = al((size_t)K1 * 8);
-  const size_t a1_bytes = up_bytes + 2 * sz_cnt + sz_info + 256 + 2 * sz_pre + 2 * sz_tot;
-  // the temporary arena comes from the slot's cached scratch workspace when that is free and large enough (a hipMalloc +
-  // hipFree pair per call costs ≈0.3 ms); the plan borrows the same scratch only after this arena is done with
-  unsigned char* a1 = nullptr;
-  bool a1_borrowed = false;
-  {
-    sls_ctx::Slot& sl = ctx->slots[dev_slot];
-    if (!sl.scratch_in_use && sl.scratch && sl.scratch_bytes >= a1_bytes) { a1 = static_cast<unsigned char*>(sl.scratch); a1_borrowed = true; }
-  }
-  if (!a1) {
-    e = hipMalloc(reinterpret_cast<void**>(&a1), a1_bytes);
-    if (e != hipSuccess) { delete pl; return hipfail(ctx, e, "hipMalloc (symbolic arena)"); }
-  }
-  unsigned char* a2 = nullptr;
-  bool a2_owned = false;        // a2 came from hipMalloc (not the slot's cache) and is not yet the plan's
-  auto bail = [&](int code) { if (a1 && !a1_borrowed) (void)hipFree(a1); if (a2 && a2_owned) (void)hipFree(a2); delete pl; return code; };
-  {
-    std::vector<unsigned char> stage(up_bytes);
-    size_t off = 0;
-    for (auto& u : ups) { if (u.bytes) std::memcpy(stage.data() + off, u.src, u.bytes); *u.dst = a1 + off; off += al(u.bytes); }
-    e = hipMemcpy(a1, stage.data(), up_bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return bail(hipfail(ctx, e, "hipMemcpy H2D (plant pattern)"));
-  }
-  size_t off = up_bytes;
-  cp.A_cp = d_acp; cp.A_ri = d_ari; cp.B_rp = d_brp; cp.B_ci = d_bci;
-  cp.A_rowptr = d_arp; cp.A_colidx = d_aci; cp.A_val = d_av; cp.B_rowptr = d_Brp; cp.B_colidx = d_Bci; cp.B_val = d_Bv;
-  cp.kx = d_kx; cp.ku = d_ku;
-  cp.cntx = reinterpret_cast<int32_t*>(a1 + off); off += sz_cnt;
-  cp.cntu = reinterpret_cast<int32_t*>(a1 + off); off += sz_cnt;
-  int64_t* d_prex = reinterpret_cast<int64_t*>(a1 + off); off += sz_pre;
-  int64_t* d_preu = reinterpret_cast<int64_t*>(a1 + off); off += sz_pre;
-  // what comes back to the host in ONE copy: flags, level totals, per-column sizes
-  unsigned char* d_back = a1 + off;
-  cp.flags = reinterpret_cast<int32_t*>(a1 + off); off += 256;
-  int64_t* d_totx = reinterpret_cast<int64_t*>(a1 + off); off += sz_tot;
-  int64_t* d_totu = reinterpret_cast<int64_t*>(a1 + off); off += sz_tot;
-  cp.col_info = reinterpret_cast<int32_t*>(a1 + off); off += sz_info;
-  const size_t back_bytes = 256 + 2 * sz_tot + (size_t)Nx * 6 * 4;
-  std::vector<unsigned char> back(back_bytes);
-  // LDS plan of one wave: two bitmaps, level starts, regularity counters, two level pools of `cap` entries
-  const int64_t fixed_bytes = ((Nx + 31) / 32 + (std::max<int64_t>(Nu, 1) + 31) / 32) * 4 + 2 * 68 * 4 + 4 * T * 4;
-  if (fixed_bytes > 96 * 1024) return bail(fail(ctx, SLS_EUNSUPPORTED, "device symbolic route: the state bitmap does not fit LDS (Nx > ≈7e5); pass the masks to sls_h2_sf_plan"));
-  const int cap_limit = (int)((kMaxLds - fixed_bytes) / 8);
-  int cap = std::min(cap_limit, 2048);
-  int grid = 1; size_t lds = 0;
-  for (;;) {
-    cp.cap = cap;
-    lds = (size_t)fixed_bytes + 8ull * cap;
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)kMaxLds / std::max<size_t>(lds, 1)));
-    grid = (int)std::min<int64_t>(Nx, (int64_t)ctx->ncu[dev_slot] * per_cu);
-    e = hipMemsetAsync(cp.flags, 0, 8, nullptr);
-    if (e == hipSuccess) e = launch_column_tables(cp, false, grid, lds, nullptr);
-    if (e == hipSuccess) e = launch_level_prefix(cp.cntx, cp.cntu, (int)Nx, K1, d_prex, d_preu, d_totx, d_totu, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(back.data(), d_back, back_bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return bail(hipfail(ctx, e, "device symbolic route (count pass)"));
-    if (!reinterpret_cast<const int32_t*>(back.data())[0]) break;
-    if (cap >= cap_limit) return bail(fail(ctx, SLS_EUNSUPPORTED, "device symbolic route: a column's level sets do not fit LDS; pass the masks to sls_h2_sf_plan"));
-    cap = std::min(cap_limit, 2 * cap);
-  }
-  tick("device: count pass + prefixes + D2H");
-  const int64_t* totx = reinterpret_cast<const int64_t*>(back.data() + 256);
-  const int64_t* totu = reinterpret_cast<const int64_t*>(back.data() + 256 + sz_tot);
-  const int32_t* info = reinterpret_cast<const int32_t*>(back.data() + 256 + 2 * sz_tot);
-
-  // ---- host: value-array offsets, per-column placement, descriptors ----
-  S.off_x.assign(T + 1, 0); S.off_u.assign(T + 1, 0);
-  for (int64_t t = 0; t < T; ++t) S.off_x[t + 1] = S.off_x[t] + totx[L.kx[t]];
-  S.off_u[0] = S.off_x[T];
-  for (int64_t t = 0; t < T; ++t) S.off_u[t + 1] = S.off_u[t] + totu[L.ku[t]];
-  S.n_values = S.off_u[T];
-  if (S.n_values > 0x7fffffffLL) return bail(fail(ctx, SLS_EUNSUPPORTED, "more than 2^31 values in Φ: not supported by this build"));
-  S.n_total_subproblems = Nx; S.first_sub_index = 0;
-  S.subs.resize((size_t)Nx); S.sub_col.resize((size_t)Nx);
-  std::vector<int64_t> idx_off((size_t)Nx), cw_off((size_t)Nx);
-  S.pk_base.assign((size_t)Nx + 1, 0);
-  int64_t idx_tot = 0, cw_tot = 0, md_tot = 0;
-  for (int64_t c = 0; c < Nx; ++c) {
-    const int32_t* ci = info + 6 * c;
-    const int32_t n = ci[0], m = ci[1], nm = n + m;
-    SubDesc sd{};
-    sd.n = n; sd.m = m; sd.pos = ci[2]; sd.nnzA = ci[3]; sd.nnzB = ci[4]; sd.has_w = 0;
-    sd.cls = wave_class_of(n, m);
-    sd.off_sx = idx_tot; sd.off_su = idx_tot + n; sd.off_mask = sd.off_dest = md_tot; sd.off_w = 0; sd.out_index = c;
-    S.subs[(size_t)c] = sd; S.sub_col[(size_t)c] = (int32_t)c;
-    idx_off[(size_t)c] = idx_tot; cw_off[(size_t)c] = cw_tot;
-    idx_tot += nm; cw_tot += T * ((nm + 63) / 64); md_tot += T * nm;
-    S.pk_base[(size_t)c + 1] = S.pk_base[(size_t)c] + ci[5];
-    S.max_n = std::max(S.max_n, n); S.max_m = std::max(S.max_m, m); S.max_nm = std::max(S.max_nm, nm);
-    S.max_nnzA = std::max(S.max_nnzA, ci[3]); S.max_nnzB = std::max(S.max_nnzB, ci[4]);
-    const double dn = n, dnf = ci[5], dT = (double)T;
-    S.flops_alg += dn * dn * dnf + (7.0 / 3.0) * (dT + 1) * dn * dn * dn + 6.0 * (dT + 1) * dn * dn + 2.0 * dn * dnf;
-    S.bytes_alg += 12.0 * (ci[3] + ci[4]) + 4.0 * (n + m) + dT * (n + m) / 8.0 + 8.0 * dnf;
-  }
-  S.md_total = md_tot; S.n_packed = S.pk_base[(size_t)Nx];
-  // objective records: this route only takes the default cost, so the constant is 0 and the scale is B1[c,c]² (1 for the
-  // minimum-norm point of a b = 0 column), as the host pass leaves them
-  S.obj_pool.resize(2 * (size_t)Nx);
-  const int64_t b1 = dims->index_base;
-  for (int64_t c = 0; c < Nx; ++c) {
-    double bd = 0.0;
-    for (int64_t k = P->B1->colptr[c] - b1; k < P->B1->colptr[c + 1] - b1; ++k)
-      if (P->B1->rowval[k] - b1 == c) bd = P->B1->nzval ? P->B1->nzval[k] : 1.0;
-    S.obj_pool[2 * (size_t)c] = bd != 0.0 ? bd * bd : 1.0; S.obj_pool[2 * (size_t)c + 1] = 0.0;
-  }
-  tick("host: offsets + descriptors");
-  S.order.resize((size_t)Nx);
-  for (int64_t c = 0; c < Nx; ++c) S.order[(size_t)c] = (int32_t)c;
-  std::stable_sort(S.order.begin(), S.order.end(), [&](int32_t a, int32_t b2) { return S.subs[a].n > S.subs[b2].n; });
-
-  // ---- arena 2 (kept by the plan): index sets, compact masks, bases; + the fill pass's own inputs ----
-  const size_t sz_idx = al((size_t)std::max<int64_t>(idx_tot, 1) * 4), sz_cm = al((size_t)std::max<int64_t>(cw_tot, 1) * 8),
-               sz_cb = al((size_t)2 * T * Nx * 4), sz_off = al((size_t)Nx * 8), sz_t = al((size_t)T * 8);
-  const size_t a2_bytes = sz_idx + sz_cm + sz_cb + 2 * sz_off + 2 * sz_t;
-  bool a2_borrowed = false;
-  {
-    // kept by the plan; a one-shot call builds and drops a plan per call, so the slot caches one such buffer (as for the arena)
-    sls_ctx::Slot& sl = ctx->slots[dev_slot];
-    if (!sl.ltab_in_use) {
-      if (sl.ltab_bytes < a2_bytes || sl.ltab_bytes > 4 * a2_bytes + (64u << 20)) {
-        if (sl.ltab) (void)hipFree(sl.ltab);
-        sl.ltab = nullptr; sl.ltab_bytes = 0;
-        e = hipMalloc(&sl.ltab, a2_bytes);
-        if (e != hipSuccess) return bail(hipfail(ctx, e, "hipMalloc (device tables)"));
-        sl.ltab_bytes = a2_bytes;
-      }
-      a2 = static_cast<unsigned char*>(sl.ltab); a2_borrowed = true;
-    }
-  }
-  if (!a2) {
-    e = hipMalloc(reinterpret_cast<void**>(&a2), a2_bytes);
-    if (e != hipSuccess) return bail(hipfail(ctx, e, "hipMalloc (device tables)"));
-    a2_owned = true;
-  }
-  size_t o2 = 0;
-  cp.idx_pool = reinterpret_cast<int32_t*>(a2 + o2); o2 += sz_idx;
-  cp.cmask = reinterpret_cast<uint64_t*>(a2 + o2); o2 += sz_cm;
-  cp.cbase = reinterpret_cast<int32_t*>(a2 + o2); o2 += sz_cb;
-  int64_t* d_cw = reinterpret_cast<int64_t*>(a2 + o2); o2 += sz_off;
-  int64_t* d_io = reinterpret_cast<int64_t*>(a2 + o2); o2 += sz_off;
-  int64_t* d_ox = reinterpret_cast<int64_t*>(a2 + o2); o2 += sz_t;
-  int64_t* d_ou = reinterpret_cast<int64_t*>(a2 + o2); o2 += sz_t;
-  {
-    // cw_off | idx_off | off_x | off_u are adjacent in the arena: one staged copy
-    std::vector<unsigned char> st2(2 * sz_off + 2 * sz_t, 0);
-    std::memcpy(st2.data(), cw_off.data(), (size_t)Nx * 8);
-    std::memcpy(st2.data() + sz_off, idx_off.data(), (size_t)Nx * 8);
-    std::memcpy(st2.data() + 2 * sz_off, S.off_x.data(), (size_t)T * 8);
-    std::memcpy(st2.data() + 2 * sz_off + sz_t, S.off_u.data(), (size_t)T * 8);
-    e = hipMemcpy(d_cw, st2.data(), st2.size(), hipMemcpyHostToDevice);
-  }
-  cp.prex = d_prex; cp.preu = d_preu; cp.offx = d_ox; cp.offu = d_ou; cp.idx_off = d_io; cp.cw_off = d_cw;
-  if (e == hipSuccess) e = launch_column_tables(cp, true, grid, lds, nullptr);
-  int32_t fl[2] = {0, 0};
-  if (e == hipSuccess) e = hipMemcpy(fl, cp.flags, 8, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return bail(hipfail(ctx, e, "device symbolic route (fill pass)"));
-  if (fl[1]) return bail(fail(ctx, SLS_EUNSUPPORTED, "device symbolic route: a mask row lies outside its column's index set (A without a full diagonal); pass the masks to sls_h2_sf_plan"));
-  tick("device: fill pass");
-  if (S.wu.updatable) {
-    // updatable weights on this route: a record for every column with B1[c,c] ≠ 0, filled on the host by the update's own twin
-    // from the plan-time diagonals.  The index sets exist on the device only, so they come back once (4 B per local variable,
-    // flagged plans only); plan_finish drops the host copy again.
-    S.idx_pool.resize((size_t)idx_tot);
-    if (idx_tot) {
-      e = hipMemcpy(S.idx_pool.data(), cp.idx_pool, (size_t)idx_tot * sizeof(int32_t), hipMemcpyDeviceToHost);
-      if (e != hipSuccess) return bail(hipfail(ctx, e, "hipMemcpy D2H (index sets)"));
-    }
-    S.wu.b2.assign((size_t)Nx, 0.0);
-    for (int64_t c = 0; c < Nx; ++c) {
-      double bd = 0.0;
-      for (int64_t k = P->B1->colptr[c] - b1; k < P->B1->colptr[c + 1] - b1; ++k)
-        if (P->B1->rowval[k] - b1 == c) bd = P->B1->nzval ? P->B1->nzval[k] : 1.0;
-      if (bd == 0.0) continue;                                  // a b = 0 column keeps no record: its minimiser ignores the weights
-      SubDesc& sd = S.subs[(size_t)c];
-      sd.has_w = 1; sd.off_w = 2 * idx_off[(size_t)c];
-      S.wu.b2[(size_t)c] = bd * bd;
-      S.obj_pool[2 * (size_t)c] = 1.0;                          // the scale belongs to has_w = 0 columns
-    }
-    weights_owner_scale(S);
-    std::string wmsg;
-    const double* dg = S.wu.diag.data();
-    if (check_weights_update(S.wu, Nx, Nu, dg, dg + Nx, wmsg)) return bail(fail(ctx, SLS_EUNSUPPORTED, wmsg + " (plan-time weights)"));
-    S.w_pool.assign((size_t)(2 * idx_tot), 0.0);
-    if ((rc = weight_records_host(S, dg, dg + Nx, S.w_pool.data(), nullptr, nullptr, nullptr, wmsg))) return bail(fail(ctx, rc, wmsg));
-  }
-  if (!a1_borrowed) (void)hipFree(a1);
-  a1 = nullptr;
-  if (a2_borrowed) { ctx->slots[dev_slot].ltab_in_use = true; pl->ltab_borrowed = true; }
-  else pl->dev_allocs.push_back(a2);
-  DeviceTables dt;
-  dt.d_idx = cp.idx_pool; dt.d_cmask = cp.cmask; dt.d_cbase = cp.cbase; dt.d_coff = d_cw;
-  a2 = nullptr;                                      // owned by the plan from here on (plan_finish destroys the plan on failure)
-  return plan_finish(ctx, dev_slot, dims, pl, t0, false, PlanOpts{}, &dt, plan_out);
-}
-
-int sls_h2_sf_plan_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, int64_t d, double alpha,
-                             sls_plan** plan_out) {
-  return plan_create_localized(ctx, dev_slot, dims, P, d, alpha, plan_out);
 }
 
 int sls_plan_get_info(const sls_plan* plan, sls_plan_info* info) {

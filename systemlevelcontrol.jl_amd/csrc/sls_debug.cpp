@@ -32,7 +32,7 @@ int sls_debug_plan_tables_localized(sls_ctx* ctx, int dev_slot, const sls_dims* 
                                     int64_t* md_total, uint8_t* mask_out, int32_t* dest_out, int64_t* n_idx, int32_t* idx_out) {
   if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
   sls_plan* pl = nullptr;
-  int rc = plan_create_localized(ctx, dev_slot, dims, P, d, alpha, &pl);
+  int rc = sls_h2_sf_plan_localized(ctx, dev_slot, dims, P, d, alpha, &pl);
   if (rc) return rc;
   const int64_t n = pl->sym.md_total;
   int64_t ni = 0;

@@ -203,7 +203,7 @@ int sls_h2_sf_solve_localized(sls_ctx* ctx, const sls_dims* dims, const sls_plan
   if (!phix_vals || !phiu_vals) return fail(ctx, SLS_EINVAL, "null output arrays");
   std::vector<sls_plan*> plans(1, nullptr);
   std::vector<double*> dvals(1, nullptr);
-  int rc = plan_create_localized(ctx, 0, dims, P, d, alpha, &plans[0]);
+  int rc = sls_h2_sf_plan_localized(ctx, 0, dims, P, d, alpha, &plans[0]);
   if (rc) return rc;
   sls_stats st{};
   st.n_devices = 1;

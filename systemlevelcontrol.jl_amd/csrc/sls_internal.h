@@ -1,4 +1,5 @@
-// sls_internal.h — what the translation units behind include/sls_mi355x.h share (context object, error plumbing).
+// sls_internal.h — what the translation units behind include/sls_mi355x.h share: the context object, error plumbing, the slot's
+// pinned staging paths (host → device, device → host, the download ring) and the launchers of the .hip units.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -58,6 +59,9 @@ int pinned_read_until(sls_ctx* ctx, int slot, hipStream_t st);
 int stage_to_device(sls_ctx* ctx, int slot, hipStream_t st, double* d_stage, const double* a, size_t na, const double* b, size_t nb);
 // Device bytes to the host on `st`, which is waited for: through the pinned buffer when it fits, else straight into `dst`.
 int fetch_to_host(sls_ctx* ctx, int slot, hipStream_t st, void* dst, const void* d_src, size_t bytes);
+// Device → host copy of a flat array of 8-byte elements into the caller's pageable slices (slice i = elements [beg[i], beg[i+1]) →
+// ptrs[i]) through the slot's pinned ring.  0, a negative error, or 1 when the ring is not available (the caller falls back).
+int pinned_download(sls_ctx* ctx, int slot, int dev, const void* d_src, const std::vector<int64_t>& beg, const std::vector<void*>& ptrs);
 // the launchers of the .hip units
 hipError_t launch_general(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool wide);
 hipError_t launch_scatter(const double* src, const int64_t* idx, int64_t n, double* dst, hipStream_t stream);

@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "sls_device.h"
+#include "sls_symbolic_device.h"
 
 namespace sls {
 
@@ -206,8 +207,8 @@ __global__ __launch_bounds__(64) void column_tables_kernel(const ColumnTablePara
   uint32_t* bmx = lds_u32;
   uint32_t* bmu = bmx + nwx;
   int32_t* px = reinterpret_cast<int32_t*>(bmu + nwu);        // level starts in lx (KL + 2 entries)
-  int32_t* pu = px + 68;
-  int32_t* chk = pu + 68;                                      // [2][T] regularity counters (fill pass)
+  int32_t* pu = px + kLevelStarts;
+  int32_t* chk = pu + kLevelStarts;                            // [2][T] regularity counters (fill pass)
   int32_t* kxs = chk + 2 * p.T;                                // level schedule, staged once (a global load per time step and
   int32_t* kus = kxs + p.T;                                    //  column was most of the fill pass)
   int32_t* lx = kus + p.T;

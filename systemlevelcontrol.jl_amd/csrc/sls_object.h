@@ -29,6 +29,9 @@ class Arena {
   // hipMalloc on the current device, the uploads (synchronous), the pointers.  On a failure nothing stays allocated, *arena is
   // NULL and the result is hipfail's, with `what_malloc` or `what_upload`.
   int commit(sls_ctx* ctx, void** arena, const char* what_malloc, const char* what_upload);
+  // The same layout inside bytes() of device memory the caller owns: the tables, declared first, are staged on the host and go
+  // up in ONE synchronous copy.  A failure is hipfail's with `what_upload`.
+  int commit_in(sls_ctx* ctx, void* base, const char* what_upload);
 
  private:
   struct Req { const void* src; size_t bytes; const void** out; };

@@ -1,6 +1,8 @@
 // sls_object.hip — the arena, the Φ gather and the plant ensemble of the objects that evaluate a resident Φ (sls_object.h).
 #include "sls_object.h"
 
+#include <cstring>
+
 namespace {
 
 __global__ void gather_phi_kernel(const double* __restrict__ values, const int32_t* __restrict__ perm, long long n,
@@ -51,6 +53,16 @@ int Arena::commit(sls_ctx* ctx, void** arena, const char* what_malloc, const cha
   }
   *arena = a;
   return 0;
+}
+
+int Arena::commit_in(sls_ctx* ctx, void* base, const char* what_upload) {
+  size_t off = 0, up_end = 0;
+  for (const Req& r : reqs_) { *r.out = static_cast<unsigned char*>(base) + off; off += al(r.bytes); if (r.src) up_end = off; }
+  std::vector<unsigned char> stage(up_end);
+  off = 0;
+  for (const Req& r : reqs_) { if (r.src && r.bytes) std::memcpy(stage.data() + off, r.src, r.bytes); off += al(r.bytes); }
+  const hipError_t e = up_end ? hipMemcpy(base, stage.data(), up_end, hipMemcpyHostToDevice) : hipSuccess;
+  return e == hipSuccess ? 0 : hipfail(ctx, e, what_upload);
 }
 
 int launch_gather_phi(sls_ctx* ctx, const double* d_values, const int32_t* d_perm, int64_t n, double* d_vals, hipStream_t stream) {

@@ -1,5 +1,6 @@
 // sls_plan.h — the resident plan as the units behind the C ABI see it: sls_api.cpp builds, runs and destroys it, sls_plan_update.cpp
-// (updates and partial re-solves), sls_dropin.cpp (the one-shot calls) and sls_debug.cpp (include/sls_mi355x_debug.h) are its clients.
+// (updates and partial re-solves), sls_dropin.cpp (the one-shot calls), sls_symbolic_device.cpp (the device-resident symbolic
+// route, which ends in plan_finish) and sls_debug.cpp (include/sls_mi355x_debug.h) are its clients.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -145,8 +146,14 @@ double now_s();
 int plan_create(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
                 int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, int64_t group_begin, int64_t group_end,
                 bool want_packed, const PlanOpts& opt, sls_plan** plan_out);
-int plan_create_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, int64_t d, double alpha,
-                          sls_plan** plan_out);
+struct DeviceTables {            // sls_h2_sf_plan_localized (sls_symbolic_device.cpp): tables built on the device, owned by the plan
+  const int32_t* d_idx = nullptr; const uint64_t* d_cmask = nullptr;
+  const int32_t* d_cbase = nullptr; const int64_t* d_coff = nullptr;
+};
+// Second half of plan creation, shared by plan_create (host symbolic pass) and sls_h2_sf_plan_localized: kernel selection, launch list,
+// uploads, workspaces.  `dt` != NULL: index sets and compact tables are used where they sit on the device.  Owns `pl`: a failure destroys it.
+int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_plan* pl, double t0, bool want_packed, const PlanOpts& opt,
+                const DeviceTables* dt, sls_plan** plan_out);
 // Host waits for the plan's last execute (and for nothing else on the device: a status read or a download must not stall on
 // a collective or on another plan running on some other stream).
 int wait_plan_done(sls_plan* pl);

@@ -529,6 +529,50 @@ int localized_prepare(const sls_dims* dims, const sls_plant* P, int64_t d, doubl
   return 0;
 }
 
+int localized_layout(const sls_dims* dims, const sls_csc_f64* B1, const LocalizedHost& L, const int64_t* totx, const int64_t* totu,
+                     const int32_t* col_info, Symbolic& S, LocalizedLayout& lay, std::string& msg) {
+  const int64_t Nx = dims->Nx, T = dims->T;
+  // value-array offsets: time step t holds the levels kx[t] / ku[t] of every column
+  S.off_x.assign(T + 1, 0); S.off_u.assign(T + 1, 0);
+  for (int64_t t = 0; t < T; ++t) S.off_x[t + 1] = S.off_x[t] + totx[L.kx[t]];
+  S.off_u[0] = S.off_x[T];
+  for (int64_t t = 0; t < T; ++t) S.off_u[t + 1] = S.off_u[t] + totu[L.ku[t]];
+  S.n_values = S.off_u[T];
+  if (S.n_values > 0x7fffffffLL) { msg = "more than 2^31 values in Φ: not supported by this build"; return SLS_EUNSUPPORTED; }
+  // per-column placement and descriptors
+  S.n_total_subproblems = Nx; S.first_sub_index = 0;
+  S.subs.resize((size_t)Nx); S.sub_col.resize((size_t)Nx);
+  lay.idx_off.resize((size_t)Nx); lay.cw_off.resize((size_t)Nx);
+  S.pk_base.assign((size_t)Nx + 1, 0);
+  // objective records: this route only takes the default cost, so the constant is 0 and the scale is B1[c,c]² (1 for the
+  // minimum-norm point of a b = 0 column), as the host pass leaves them
+  S.obj_pool.resize(2 * (size_t)Nx);
+  int64_t& idx_tot = lay.idx_total = 0; int64_t& cw_tot = lay.cw_total = 0; int64_t md_tot = 0;
+  for (int64_t c = 0; c < Nx; ++c) {
+    const int32_t* ci = col_info + 6 * c;
+    const int32_t n = ci[0], m = ci[1], nm = n + m;
+    SubDesc sd{};
+    sd.n = n; sd.m = m; sd.pos = ci[2]; sd.nnzA = ci[3]; sd.nnzB = ci[4]; sd.has_w = 0;
+    sd.cls = wave_class_of(n, m);
+    sd.off_sx = idx_tot; sd.off_su = idx_tot + n; sd.off_mask = sd.off_dest = md_tot; sd.off_w = 0; sd.out_index = c;
+    S.subs[(size_t)c] = sd; S.sub_col[(size_t)c] = (int32_t)c;
+    lay.idx_off[(size_t)c] = idx_tot; lay.cw_off[(size_t)c] = cw_tot;
+    idx_tot += nm; cw_tot += T * ((nm + 63) / 64); md_tot += T * nm;
+    S.pk_base[(size_t)c + 1] = S.pk_base[(size_t)c] + ci[5];
+    S.max_n = std::max(S.max_n, n); S.max_m = std::max(S.max_m, m); S.max_nm = std::max(S.max_nm, nm);
+    S.max_nnzA = std::max(S.max_nnzA, ci[3]); S.max_nnzB = std::max(S.max_nnzB, ci[4]);
+    add_column_cost(n, m, ci[3], ci[4], T, ci[5], S.flops_alg, S.bytes_alg);
+    const double bd = b1_diagonal(B1, dims->index_base, c);
+    S.obj_pool[2 * (size_t)c] = bd != 0.0 ? bd * bd : 1.0; S.obj_pool[2 * (size_t)c + 1] = 0.0;
+  }
+  S.md_total = md_tot; S.n_packed = S.pk_base[(size_t)Nx];
+  // processing order, as build_symbolic: descending ñx, stable — it is the plan's launch order
+  S.order.resize((size_t)Nx);
+  std::iota(S.order.begin(), S.order.end(), 0);
+  std::stable_sort(S.order.begin(), S.order.end(), [&](int32_t a, int32_t b) { return S.subs[a].n > S.subs[b].n; });
+  return 0;
+}
+
 int index_set_inputs(const sls_dims* dims, const sls_csc_f64* A, const sls_csc_bool* Sx_last, const sls_csc_bool* Su_last,
                      std::vector<int32_t>& a_cp, std::vector<int32_t>& a_ri, std::vector<int32_t>& sx_cp, std::vector<int32_t>& sx_ri,
                      std::vector<int32_t>& su_cp, std::vector<int32_t>& su_ri, std::string& msg) {
@@ -982,10 +1026,7 @@ static int fill_range(const Inputs& in, const std::vector<int64_t>& gptr, const 
       }
       S.subs[sd.out_index] = sd;
       S.sub_col[sd.out_index] = (int32_t)c;
-      // algorithmic work, SURVEY §8d
-      const double dn = n, dT = (double)T, dnf = (double)nfree;
-      part.flops_alg += dn * dn * dnf + (7.0 / 3.0) * (dT + 1) * dn * dn * dn + 6.0 * (dT + 1) * dn * dn + 2.0 * dn * dnf;
-      part.bytes_alg += 12.0 * (nnzA + nnzB) + 4.0 * (n + m) + dT * (n + m) / 8.0 + 8.0 * dnf;
+      add_column_cost(n, m, nnzA, nnzB, T, nfree, part.flops_alg, part.bytes_alg);
     }
     part.max_n = std::max(part.max_n, n); part.max_m = std::max(part.max_m, m);
     part.max_nnzA = std::max(part.max_nnzA, nnzA); part.max_nnzB = std::max(part.max_nnzB, nnzB);

@@ -169,6 +169,29 @@ struct LocalizedHost {
 };
 int localized_prepare(const sls_dims* dims, const sls_plant* P, int64_t d, double alpha, Symbolic& S, LocalizedHost& L, std::string& msg);
 
+// The same route's host arithmetic between its count pass and its fill pass, from the count pass's outputs: the level totals totx /
+// totu [kmax + 1] and col_info [Nx][6] = (ñx, ñu, position of c in s_x, nnz Ã, nnz B̃2, free variables) per column.  Fills S as
+// build_symbolic does in the compact, mask-order layout with default groups, except what only the device holds (idx_pool, cmask, cbase,
+// coff); `lay`: per column the first entry of its index sets in idx_pool and its first word in cmask, and the totals.  SLS_EUNSUPPORTED beyond 2^31 values.
+struct LocalizedLayout { std::vector<int64_t> idx_off, cw_off; int64_t idx_total = 0, cw_total = 0; };
+int localized_layout(const sls_dims* dims, const sls_csc_f64* B1, const LocalizedHost& L, const int64_t* totx, const int64_t* totu,
+                     const int32_t* col_info, Symbolic& S, LocalizedLayout& lay, std::string& msg);
+
+// B1[c, c]: 0 when the entry is not stored, 1 for a stored entry of a B1 without values
+inline double b1_diagonal(const sls_csc_f64* B1, int base, int64_t c) {
+  double bd = 0.0;
+  for (int64_t k = B1->colptr[c] - base; k < B1->colptr[c + 1] - base; ++k)
+    if (B1->rowval[k] - base == c) bd = B1->nzval ? B1->nzval[k] : 1.0;
+  return bd;
+}
+
+// algorithmic work of one column, added to flops / bytes: ñx, ñu, local nnz of Ã and B̃2, free variables
+inline void add_column_cost(int32_t n, int32_t m, int32_t nnzA, int32_t nnzB, int64_t T, int64_t nfree, double& flops, double& bytes) {
+  const double dn = n, dT = (double)T, dnf = (double)nfree;
+  flops += dn * dn * dnf + (7.0 / 3.0) * (dT + 1) * dn * dn * dn + 6.0 * (dT + 1) * dn * dn + 2.0 * dn * dnf;
+  bytes += 12.0 * (nnzA + nnzB) + 4.0 * (n + m) + dT * (n + m) / 8.0 + 8.0 * dnf;
+}
+
 // The shared operator of a plan: A and B2 in row order (A_csr, B_csr) and their CSC storage read as CSR of the transposes
 // (At_csr, Bt_csr), with the longest rows.  build_symbolic and localized_prepare both come through here; matrices already checked.
 void fill_operator_csr(const sls_csc_f64* A, const sls_csc_f64* B2, int base, Symbolic& S);

@@ -76,4 +76,22 @@ int weight_records_host(const Symbolic& S, const double* c1_diag, const double* 
   return 0;
 }
 
+int localized_weight_records(const sls_dims* dims, const sls_csc_f64* B1, const LocalizedLayout& lay, Symbolic& S, std::string& msg) {
+  const int64_t Nx = S.Nx, Nu = S.Nu;
+  S.wu.b2.assign((size_t)Nx, 0.0);
+  for (int64_t c = 0; c < Nx; ++c) {
+    const double bd = b1_diagonal(B1, dims->index_base, c);
+    if (bd == 0.0) continue;                                  // a b = 0 column keeps no record: its minimiser ignores the weights
+    SubDesc& sd = S.subs[(size_t)c];
+    sd.has_w = 1; sd.off_w = 2 * lay.idx_off[(size_t)c];
+    S.wu.b2[(size_t)c] = bd * bd;
+    S.obj_pool[2 * (size_t)c] = 1.0;                          // the scale belongs to has_w = 0 columns
+  }
+  weights_owner_scale(S);
+  const double* dg = S.wu.diag.data();
+  if (check_weights_update(S.wu, Nx, Nu, dg, dg + Nx, msg)) { msg += " (plan-time weights)"; return SLS_EUNSUPPORTED; }
+  S.w_pool.assign((size_t)(2 * lay.idx_total), 0.0);
+  return weight_records_host(S, dg, dg + Nx, S.w_pool.data(), nullptr, nullptr, nullptr, msg);
+}
+
 }  // namespace sls

@@ -133,4 +133,8 @@ int check_weights_update(const Symbolic::UpdatableWeights& W, int64_t Nx, int64_
 int weight_records_host(const Symbolic& S, const double* c1_diag, const double* d12_diag, double* w_pool, double* diag, uint8_t* dirty,
                         int64_t* rejected, std::string& msg);
 
+// The device-resident symbolic route's records, behind its fill pass (S as localized_layout left it, plus idx_pool and wu.diag): a
+// has_w = 1 record at 2·idx_off[c] for every column with B1[c,c] ≠ 0, b², the value rule's scale; SLS_EUNSUPPORTED on a bad weight.
+int localized_weight_records(const sls_dims* dims, const sls_csc_f64* B1, const LocalizedLayout& lay, Symbolic& S, std::string& msg);
+
 }  // namespace sls

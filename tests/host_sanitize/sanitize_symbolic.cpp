@@ -2,10 +2,12 @@
 // built and run by tests/test_host.py::test_symbolic_pass_under_sanitizers with g++ -fsanitize=address,undefined.  Drives every
 // host-only entry the C ABI forwards to — mask recipe, validation, index sets, the full symbolic pass in its four table layouts
 // (explicit / compact × packed / mask order), shard ranges, caller groups (decoupled and coupled), cost model, the inputs of
-// the two device passes (also on the hub, long-range, dense and stored-zero plants of tests/symbolic_cases.py), the closed-loop FIR operator (restated exactly from the masks: check_fir), kernel selection (csrc/sls_routing.cpp: the launch list of every shard for
+// the two device passes (also on the hub, long-range, dense and stored-zero plants of tests/symbolic_cases.py), their LDS list plans
+// (csrc/sls_symbolic_device.h) and the host arithmetic of the device-resident route (localized_layout, against the host pass), the closed-loop FIR operator (restated exactly from the masks: check_fir), kernel selection (csrc/sls_routing.cpp: the launch list of every shard for
 // 1, 8 and 256 CUs, both objectives, with and without force_tile) — on a chain, a 2-D grid and a random plant, in both index bases, plus
 // malformed inputs that must be refused without touching memory out of bounds.  Exit code 0 = clean.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -14,6 +16,7 @@
 
 #include "../../systemlevelcontrol.jl_amd/csrc/sls_routing.h"
 #include "../../systemlevelcontrol.jl_amd/csrc/sls_symbolic.h"
+#include "../../systemlevelcontrol.jl_amd/csrc/sls_symbolic_device.h"
 
 namespace {
 
@@ -454,9 +457,147 @@ void exercise_device_inputs(const Plant& P, int64_t d, int64_t T, double alpha, 
   std::printf("%s base=%d: largest mask column %lld: done\n", name, base, (long long)biggest);
 }
 
+// ---- LDS list plans of the device passes (csrc/sls_symbolic_device.h) ----
+// cap_limit against the numbers tests/test_symbolic_cases_host.py derives from the reference; the launch of a capacity at 1, 8 and
+// 256 CUs; the bitmap refusal on both sides of 96 KiB.
+void check_list_plans() {
+  using namespace sls;
+  EXPECT(kMaxLds == 160 * 1024 && kBitmapLimit == 96 * 1024, "LDS limits");
+  EXPECT(mask_list_plan(1100, 1100).cap_limit == 1100 && mask_list_plan(1100, 1100).cap0 == kMaskCap0, "hub1024: mask lists");
+  EXPECT(mask_list_plan(40, 1300).cap_limit == 1300 && index_list_plan(40, 1300).cap_limit == 1300, "hub_wideB: the actuator list sets cap_limit");
+  EXPECT(mask_list_plan(40, 20).cap_limit == 40 && index_list_plan(40, 20).cap_limit == 40, "dense40: cap_limit = Nx");
+  EXPECT(mask_list_plan(40, 20).cap0 == 40 && index_list_plan(40, 20).cap0 == 40, "dense40: first capacity = cap_limit");
+  EXPECT(mask_list_plan(14000, 14000).cap_limit == (kMaxLds - 2 * 438 * 4) / 12, "too_big_mask: what LDS holds");
+  // cap_limit_tables of tests/symbolic_cases.py restated with literals: an independent twin of the header's arithmetic (the Python
+  // value itself is held against the reference by tests/test_symbolic_cases_host.py)
+  auto tables_limit = [](int64_t Nx, int64_t Nu, int64_t T) {
+    const int64_t bitmap = ((Nx + 31) / 32 + (std::max<int64_t>(Nu, 1) + 31) / 32) * 4;
+    return (int)((160 * 1024 - (bitmap + 2 * 68 * 4 + 4 * T * 4)) / 8);
+  };
+  EXPECT(tables_list_plan(4200, 1400, 4).cap_limit == tables_limit(4200, 1400, 4), "far4200: tables pools");
+  EXPECT(tables_list_plan(23, 9, 130).cap_limit == tables_limit(23, 9, 130), "T = 130: tables pools");
+  EXPECT(tables_list_plan(335, 335, 3).cap_limit == 20395, "fits_pool: 20395 entries are what 160 KiB hold");
+  EXPECT(tables_list_plan(4200, 1400, 4).cap0 == kTablesCap0 && tables_list_plan(4200, 1400, 4).entry_bytes == 8, "tables: first capacity");
+  const ListPlan plans[3] = {mask_list_plan(4200, 1400), index_list_plan(4200, 1400), tables_list_plan(4200, 1400, 4)};
+  for (const ListPlan& p : plans)
+    for (int ncu : {1, 8, 256})
+      for (int64_t Nx : {(int64_t)1, (int64_t)7, (int64_t)4200})
+        for (int cap = p.cap0; cap <= p.cap_limit; cap = cap < p.cap_limit ? std::min(p.cap_limit, 2 * cap) : cap + 1) {
+          const ListLaunch l = list_launch(p, cap, ncu, Nx);
+          EXPECT(l.cap == cap && l.lds == (size_t)(p.fixed_bytes + (int64_t)p.entry_bytes * cap) && l.lds <= (size_t)kMaxLds, "list launch: LDS");
+          EXPECT(l.per_cu >= 1 && l.per_cu <= 8 && (l.per_cu == 8 || (size_t)(l.per_cu + 1) * l.lds > (size_t)kMaxLds), "list launch: waves per CU");
+          EXPECT(l.per_cu == 1 || (size_t)l.per_cu * l.lds <= (size_t)kMaxLds, "list launch: the waves of a CU fit its LDS");
+          EXPECT(l.grid == (int)std::min<int64_t>(Nx, (int64_t)ncu * l.per_cu), "list launch: grid = min(Nx, ncu * per_cu)");
+        }
+  // bitmap of 96 KiB exactly: 24576 words, e.g. 24575 state words + 1 input word
+  const int64_t Nx_fit = 24575 * 32, Nx_over = Nx_fit + 1;
+  EXPECT(mask_list_plan(Nx_fit, 1).fixed_bytes == 96 * 1024 && mask_list_plan(Nx_fit, 1).fits() && index_list_plan(Nx_fit, 0).fits(), "bitmap of 96 KiB accepted");
+  EXPECT(!mask_list_plan(Nx_over, 1).fits() && !index_list_plan(Nx_over, 1).fits(), "bitmap over 96 KiB refused");
+  EXPECT(tables_list_plan(Nx_fit, 1, 1).fixed_bytes == 96 * 1024 + 2 * 68 * 4 + 16 && !tables_list_plan(Nx_fit, 1, 1).fits(), "tables: the fixed words count");
+  EXPECT(tables_list_plan(Nx_fit - 32 * 140, 1, 1).fits() && !tables_list_plan(Nx_fit - 32 * 139, 1, 1).fits(), "tables: both sides of 96 KiB");
+  std::printf("list plans: done\n");
+}
+
+// ---- host arithmetic of the device-resident symbolic route (localized_layout) against the host pass ----
+// build_symbolic in the compact, mask-order layout on the recipe's own masks gives what column_tables_kernel's count pass
+// reports (col_info from its SubDescs, level totals from the masks' sizes); localized_layout must then place everything where
+// build_symbolic did.
+int levels_beyond_kmax = 0, levels_within_kmax = 0;      // cases with kx[T−1] + 1 > kmax (the index sets need a level no mask uses) / ≤ kmax
+
+void check_localized_layout(const Plant& P, int64_t d, int64_t T, double alpha, int base, const char* name) {
+  Masks M = make_masks(P, d, T, alpha, base);
+  sls_dims dims{P.Nx, P.Nu, P.Nx + P.Nu, P.Nx, T, base, 0};
+  sls_csc_f64 A = P.A.f64(), B1 = P.B1.f64(), B2 = P.B2.f64();
+  sls_plant plant{&A, &B1, &B2, nullptr, nullptr, nullptr};
+  std::string msg;
+  sls::Inputs in{&dims, &plant, M.bx.data(), M.bu.data(), 0, nullptr, nullptr};
+  sls::Symbolic H; H.want_packed = false; H.compact = true;
+  int rc = sls::build_symbolic(in, 0, P.Nx, H, msg);
+  EXPECT(rc == 0 && H.compact, "host pass, compact mask-order layout");
+  if (rc || !H.compact) { std::fprintf(stderr, "  %s: %s\n", name, msg.c_str()); return; }
+  sls::Symbolic Hp; Hp.want_packed = true;                      // the packed pass of the same inputs: n_packed, pk_base
+  EXPECT(sls::build_symbolic(in, 0, P.Nx, Hp, msg) == 0, "host pass, packed layout");
+  sls::Symbolic S;
+  sls::LocalizedHost L;
+  rc = sls::localized_prepare(&dims, &plant, d, alpha, S, L, msg);
+  EXPECT(rc == 0, "localized_prepare");
+  if (rc) return;
+  ++(L.kx[T - 1] + 1 > L.kmax ? levels_beyond_kmax : levels_within_kmax);
+  // the count pass's outputs
+  const int K1 = L.kmax + 1;
+  std::vector<int64_t> totx((size_t)K1, -1), totu((size_t)K1, -1);
+  for (int64_t t = 0; t < T; ++t) { totx[(size_t)L.kx[t]] = (int64_t)M.x[t].ri.size(); totu[(size_t)L.ku[t]] = (int64_t)M.u[t].ri.size(); }
+  std::vector<int32_t> info((size_t)P.Nx * 6);
+  for (int64_t c = 0; c < P.Nx; ++c) {
+    const sls::SubDesc& sd = H.subs[(size_t)c];
+    const int32_t ci[6] = {sd.n, sd.m, sd.pos, sd.nnzA, sd.nnzB, (int32_t)(Hp.pk_base[(size_t)c + 1] - Hp.pk_base[(size_t)c])};
+    std::copy(ci, ci + 6, info.begin() + 6 * c);
+  }
+  sls::LocalizedLayout lay;
+  rc = sls::localized_layout(&dims, &B1, L, totx.data(), totu.data(), info.data(), S, lay, msg);
+  EXPECT(rc == 0, "localized_layout");
+  if (rc) return;
+  EXPECT(S.off_x == H.off_x && S.off_u == H.off_u && S.n_values == H.n_values, "value-array offsets");
+  EXPECT(S.n_total_subproblems == H.n_total_subproblems && S.first_sub_index == H.first_sub_index, "subproblem numbering");
+  EXPECT(S.subs.size() == H.subs.size() && S.sub_col.size() == H.sub_col.size(), "one subproblem per column");
+  if (S.subs.size() != H.subs.size()) return;
+  for (size_t c = 0; c < H.subs.size(); ++c) {
+    const sls::SubDesc &a = S.subs[c], &b = H.subs[c];
+    EXPECT(a.n == b.n && a.m == b.m && a.pos == b.pos && a.nnzA == b.nnzA && a.nnzB == b.nnzB && a.cls == b.cls, "SubDesc sizes, position, class");
+    EXPECT(a.off_sx == b.off_sx && a.off_su == b.off_su && a.off_mask == b.off_mask && a.off_dest == b.off_dest, "SubDesc offsets");
+    EXPECT(a.out_index == b.out_index && a.has_w == b.has_w && a.off_w == b.off_w && S.sub_col[c] == H.sub_col[c], "SubDesc output index, weights, column");
+    EXPECT(lay.cw_off[c] == H.coff[c] && lay.idx_off[c] == b.off_sx, "first mask word / first index of the column");
+  }
+  EXPECT(lay.idx_total == (int64_t)H.idx_pool.size() && lay.cw_total == (int64_t)H.cmask.size(), "pool totals");
+  EXPECT(S.md_total == H.md_total && S.max_n == H.max_n && S.max_m == H.max_m && S.max_nm == H.max_nm, "md_total, max sizes");
+  EXPECT(S.max_nnzA == H.max_nnzA && S.max_nnzB == H.max_nnzB, "max nnz");
+  EXPECT(S.n_packed == Hp.n_packed && S.n_packed == H.n_packed && S.pk_base == Hp.pk_base, "packed bases");
+  EXPECT(S.obj_pool.size() == H.obj_pool.size() && std::equal(S.obj_pool.begin(), S.obj_pool.end(), H.obj_pool.begin()), "objective records");
+  // sums of positive terms taken in another order (the host pass sums per thread range): Nx roundings at most
+  const double tol = (double)P.Nx * 0x1p-52;
+  EXPECT(std::abs(S.flops_alg - H.flops_alg) <= tol * H.flops_alg && std::abs(S.bytes_alg - H.bytes_alg) <= tol * H.bytes_alg, "cost model");
+  // the order is the plan's launch order: a permutation, ñx non-increasing, stable among equal ñx — and then the host pass's
+  std::vector<int32_t> seen(S.order);
+  std::sort(seen.begin(), seen.end());
+  bool perm = (int64_t)seen.size() == P.Nx;
+  for (size_t q = 0; perm && q < seen.size(); ++q) perm = seen[q] == (int32_t)q;
+  EXPECT(perm, "order is a permutation of the columns");
+  for (size_t q = 0; perm && q + 1 < S.order.size(); ++q) {
+    const int32_t a = S.order[q], b = S.order[q + 1];
+    EXPECT(S.subs[(size_t)a].n > S.subs[(size_t)b].n || (S.subs[(size_t)a].n == S.subs[(size_t)b].n && a < b), "order: descending n, stable");
+  }
+  EXPECT(S.order == H.order, "order equals the host pass's");
+  // fabricated totals past 2^31 values: refused, nothing else asked of S
+  std::vector<int64_t> big((size_t)K1, (int64_t)1 << 31);
+  sls::Symbolic S2; sls::LocalizedHost L2; sls::LocalizedLayout lay2;
+  EXPECT(sls::localized_prepare(&dims, &plant, d, alpha, S2, L2, msg) == 0, "localized_prepare");
+  EXPECT(sls::localized_layout(&dims, &B1, L2, big.data(), totu.data(), info.data(), S2, lay2, msg) == SLS_EUNSUPPORTED && msg.find("2^31") != std::string::npos,
+         "more than 2^31 values accepted");
+  std::printf("localized layout %s base=%d T=%lld d=%lld alpha=%g (kx[T-1]+1 %s kmax): done\n", name, base, (long long)T, (long long)d, alpha,
+              L.kx[T - 1] + 1 > L.kmax ? ">" : "<=");
+}
+
 }  // namespace
 
 int main() {
+  check_list_plans();
+  for (int base = 0; base < 2; ++base)
+    for (int64_t T : {(int64_t)1, (int64_t)4})
+      for (int pair = 0; pair < 2; ++pair) {
+        // (d, α) = (1, 1.5): at T = 4 ku reaches d + 1 = kmax, kx[T−1] + 1 = kmax;  (3, 0.5): kx[T−1] = ku[T−1] = kmax, so the
+        // index sets need level kx[T−1] + 1 > kmax
+        const int64_t d = pair ? 3 : 1;
+        const double alpha = pair ? 0.5 : 1.5;
+        check_localized_layout(chain(5, base, false), d, T, alpha, base, "chain5");
+        check_localized_layout(grid(3, base), d, T, alpha, base, "grid3");
+        // the route needs a full diagonal of A (else a mask row lies outside its column's index set): random_plant's stored
+        // zeros stay off the diagonal here
+        Plant R = random_plant(12, base, 3u);
+        for (int64_t c = 0; c < R.Nx; ++c)
+          for (int64_t k = R.A.cp[c] - base; k < R.A.cp[c + 1] - base; ++k) if (R.A.ri[k] - base == c) R.A.v[k] = 1.0;
+        check_localized_layout(R, d, T, alpha, base, "random12");
+      }
+  EXPECT(levels_beyond_kmax > 0 && levels_within_kmax > 0, "localized layout: both kx[T-1] + 1 > kmax and <= kmax must be covered");
   for (int base = 0; base < 2; ++base) {
     exercise(chain(59, base, false), 9, 29, base, false, "chain59");
     exercise(chain(40, base, true), 4, 10, base, false, "chain40_coupled_B1");

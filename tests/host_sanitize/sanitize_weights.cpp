@@ -4,7 +4,8 @@
 // symbolic pass (SLS_PLAN_WEIGHTS_UPDATABLE), weights_shape_check, check_weights_update and weight_records_host over a chain plant
 // with band masks in both index bases, with and without a ridge term: an update must leave exactly the weight pool a fresh pass on
 // the re-weighted plant gives; refused values (NaN, inf, a zero weight without a ridge) keep their old records and are counted;
-// shapes that are not updatable, an unflagged pass and passes of another size are refused.  Exit code 0 = clean.
+// shapes that are not updatable, an unflagged pass and passes of another size are refused; the records of the device-resident
+// symbolic route (localized_weight_records) equal the flagged pass's.  Exit code 0 = clean.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -175,6 +176,37 @@ void run(int base, bool ridge) {
     const int64_t gptr[2] = {0, 2}, gcols[2] = {8 + base, 9 + base};
     EXPECT(pass(p, SLS_PLAN_WEIGHTS_UPDATABLE, nullptr, nullptr, Sx, msg, nullptr, nullptr, &B, 1, gptr, gcols) == SLS_EUNSUPPORTED &&
            msg.find("coupled") != std::string::npos, "coupled group"); }
+  if (!ridge) {
+    // The records of the device-resident symbolic route (localized_weight_records) from what that route holds behind its fill
+    // pass — descriptors without records, the index sets, the plan-time diagonals — against the flagged host pass: b², the value
+    // rule's scale, which columns have a record, every record's content and the objective scales.  off_w legitimately differs:
+    // the host pass packs the records back to back (none for the b = 0 column 5), the device route puts column c's at 2·idx_off[c].
+    sls_dims dims{p.Nx, p.Nu, p.Nx + p.Nu, p.Nx, p.T, p.base, SLS_PLAN_WEIGHTS_UPDATABLE};
+    sls_csc_f64 b1 = p.B1.f64();
+    sls::Symbolic D;
+    D.Nx = p.Nx; D.Nu = p.Nu; D.T = p.T; D.subs = Sp.subs; D.idx_pool = Sp.idx_pool;
+    D.wu.updatable = true; D.wu.diag = Sp.wu.diag;
+    D.obj_pool.assign(2 * Sp.subs.size(), 0.0);
+    sls::LocalizedLayout lay;
+    for (size_t c = 0; c < D.subs.size(); ++c) {
+      D.subs[c].has_w = 0; D.subs[c].off_w = 0; D.obj_pool[2 * c] = c == 5 ? 1.0 : Sp.wu.b2[c];     // as localized_layout leaves them
+      lay.idx_off.push_back(D.subs[c].off_sx);
+    }
+    lay.idx_total = (int64_t)D.idx_pool.size();
+    EXPECT(sls::localized_weight_records(&dims, &b1, lay, D, msg) == 0, "localized_weight_records");
+    EXPECT(D.wu.b2 == Sp.wu.b2 && D.wu.owner == Sp.wu.owner, "device route: b2 and the value rule's scale");
+    EXPECT((int64_t)D.w_pool.size() == 2 * lay.idx_total && D.obj_pool.size() == Sp.obj_pool.size(), "device route: pool sizes");
+    for (size_t c = 0; c < D.subs.size(); ++c) {
+      const sls::SubDesc &a = D.subs[c], &b = Sp.subs[c];
+      EXPECT(a.has_w == b.has_w && (a.has_w == 0 || a.off_w == 2 * lay.idx_off[c]), "device route: which columns have a record, and where");
+      EXPECT(D.obj_pool[2 * c] == Sp.obj_pool[2 * c] && D.obj_pool[2 * c + 1] == Sp.obj_pool[2 * c + 1], "device route: objective record");
+      if (a.has_w == 1 && b.has_w == 1)
+        EXPECT(std::memcmp(D.w_pool.data() + a.off_w, Sp.w_pool.data() + b.off_w, 2 * (size_t)(a.n + a.m) * sizeof(double)) == 0, "device route: record content");
+    }
+    // a plan-time weight that breaks the value rule is refused with the route's suffix
+    D.wu.diag[0] = 0.0;
+    EXPECT(sls::localized_weight_records(&dims, &b1, lay, D, msg) == SLS_EUNSUPPORTED && msg.find("(plan-time weights)") != std::string::npos, "zero plan-time weight accepted");
+  }
   std::printf("base=%d ridge=%d: %zu subproblems, %zu pool doubles\n", base, (int)ridge, Sp.subs.size(), Sp.w_pool.size());
 }
 

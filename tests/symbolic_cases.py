@@ -1,4 +1,4 @@
-"""Plants for the device symbolic pass (csrc/sls_masks.hip, expand_tables_kernel, the retry loops of csrc/sls_api.cpp) at its
+"""Plants for the device symbolic pass (csrc/sls_masks.hip, expand_tables_kernel, the retry loop of csrc/sls_symbolic_device.cpp) at its
 bitmap, level-list and mask-word edges, and an independent reference for everything that pass produces.
 
 The reference is NumPy/SciPy only and takes nothing from the library:
@@ -23,26 +23,21 @@ CSRC = os.path.join(ROOT, "systemlevelcontrol.jl_amd", "csrc")
 # ------------------------------------------------------------------ the limits, read from the sources
 @functools.lru_cache(maxsize=None)
 def limits():
-    """The constants the edges are measured against, parsed out of the sources so that the case table cannot drift from
-    them silently: LDS limit, the starting capacities of the three retry loops, bytes per list entry, the fixed LDS words of
-    the tables kernel, the level limit, and the column round of level_prefix_kernel."""
-    api = open(os.path.join(CSRC, "sls_api.cpp"), encoding="utf-8").read()
+    """The constants the edges are measured against, read from the sources so that the case table cannot drift from them
+    silently: LDS limit, the starting capacities of the three retry loops, bytes per list entry, the fixed LDS words of the
+    tables kernel (named constants of csrc/sls_symbolic_device.h, which host and kernel share), the level limit, and the
+    column round of level_prefix_kernel."""
+    plan = open(os.path.join(CSRC, "sls_symbolic_device.h"), encoding="utf-8").read()
     rout = open(os.path.join(CSRC, "sls_routing.h"), encoding="utf-8").read()
     sym = open(os.path.join(CSRC, "sls_symbolic.cpp"), encoding="utf-8").read()
     msk = open(os.path.join(CSRC, "sls_masks.hip"), encoding="utf-8").read()
     m = re.search(r"constexpr int kMaxLds = (\d+) \* 1024;", rout)
     lim = {"max_lds": int(m.group(1)) * 1024}
-    caps = re.findall(r"int cap = std::min\(cap_limit, (\d+)\);", api)
-    assert len(caps) == 3, caps
-    lim["cap0_masks"], lim["cap0_index"], lim["cap0_tables"] = (int(c) for c in caps)
-    per = re.findall(r"\(kMaxLds - bm_bytes\) / (\d+)\)", api)
-    assert len(per) == 2, per
-    lim["entry_masks"], lim["entry_index"] = int(per[0]), int(per[1])
-    m = re.search(r"const int cap_limit = \(int\)\(\(kMaxLds - fixed_bytes\) / (\d+)\);", api)
-    lim["entry_tables"] = int(m.group(1))
-    m = re.search(r"\* 4 \+ 2 \* (\d+) \* 4 \+ 4 \* T \* 4;", api)
-    lim["level_starts"] = int(m.group(1))
-    assert f"int32_t* pu = px + {lim['level_starts']};" in msk
+    const = {k: int(v) for k, v in re.findall(r"constexpr int (k\w+) = (\d+);", plan)}
+    lim["cap0_masks"], lim["cap0_index"], lim["cap0_tables"] = const["kMaskCap0"], const["kIndexCap0"], const["kTablesCap0"]
+    lim["entry_masks"], lim["entry_index"], lim["entry_tables"] = const["kMaskEntryBytes"], const["kIndexEntryBytes"], const["kTablesEntryBytes"]
+    lim["level_starts"] = const["kLevelStarts"]
+    assert "int32_t* pu = px + kLevelStarts;" in msk
     m = re.search(r"if \(L\.kmax \+ 2 > (\d+)\)", sym)
     lim["max_levels"] = int(m.group(1))
     m = re.search(r"for \(int b = 0; b < Nx; b \+= (\d+)\)", msk)

@@ -2,7 +2,7 @@
 proven on the host by tests/test_symbolic_cases_host.py).  Everything here is compared BIT FOR BIT with the NumPy/SciPy
 reference of that module — Boolean matrix powers, not the library's host pass — in both index bases:
 
-  sls_localization_masks_device    mask_levels_kernel + its retry loop               (csrc/sls_masks.hip, csrc/sls_api.cpp)
+  sls_localization_masks_device    mask_levels_kernel + its retry loop               (csrc/sls_masks.hip, csrc/sls_symbolic_device.cpp)
   sls_index_sets_device            index_sets_kernel + its retry loop
   sls_debug_plan_tables_localized  column_tables_kernel + its retry loop, level_prefix_kernel, expand_tables_kernel
 
