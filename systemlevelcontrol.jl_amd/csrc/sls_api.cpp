@@ -1,13 +1,12 @@
-// sls_api.cpp — implementation of include/sls_mi355x.h (the drop-in C ABI): the context, its pinned staging buffer, and the resident
-// plans (build, execute, batch, status, objective, residual, download, destroy).  Plant and weights updates and partial re-solves
-// of a plan are in sls_plan_update.cpp, the one-shot calls built on plans (sls_h2_sf_solve ≙ SLS_𝓗₂(P, 𝓢; 𝓘),
+// sls_api.cpp — implementation of include/sls_mi355x.h (the drop-in C ABI): the context, the error plumbing, the slot's pinned
+// staging paths, and what runs and reads a resident plan (execute, batch, synchronize, status, objective, residual, describe,
+// timing, values, download, scatter).  Plans are built and destroyed in sls_plan_build.cpp; plant and weights updates and partial
+// re-solves of a plan are in sls_plan_update.cpp, the one-shot calls built on plans (sls_h2_sf_solve ≙ SLS_𝓗₂(P, 𝓢; 𝓘),
 // src/synthesis.jl:11-32) in sls_dropin.cpp, the three device symbolic passes (sls_localization_masks_device,
 // sls_index_sets_device, sls_h2_sf_plan_localized) in sls_symbolic_device.cpp, the exports of include/sls_mi355x_debug.h in
 // sls_debug.cpp.
 //
 // Host side of the path that replaces reference src/synthesis.jl:11-72:
-//   sls_h2_sf_plan       ≙ the per-column set-up the reference redoes inside the loop
-//                           (src/reduction.jl:11-27, src/synthesis.jl:40-43,57-60)
 //   sls_plan_execute     ≙ the @distributed loop body's solve   (src/synthesis.jl:46-62)
 //   sls_plan_download    ≙ the scatter into Φx[t], Φu[t]         (src/synthesis.jl:65-67)
 // No CPU fallback exists: without a gfx950 device every compute entry point fails
@@ -17,7 +16,6 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <set>
@@ -28,6 +26,7 @@
 #include "sls_device.h"
 #include "sls_dropin_host.h"
 #include "sls_internal.h"
+#include "sls_object.h"
 #include "sls_objective.h"
 #include "sls_plan.h"
 #include "sls_residual.h"
@@ -68,43 +67,6 @@ int wait_plan_done(sls_plan* pl) {
 }  // namespace sls
 
 using namespace sls;
-
-namespace {
-constexpr int64_t kT4StaticBudget = 64ll << 20;   // bytes of plan-time static blocks a plan may hold (four-wave kernel)
-
-// Device memory of a plan comes from ONE allocation: requests are recorded first and committed together (one hipMalloc,
-// one staged H2D copy).  A README-sized plan used to spend 2 ms in ~25 hipMalloc/hipMemcpy calls for a 0.2 ms solve.
-template <class V>
-int upload(sls_plan* pl, const V& v, const typename V::value_type** out) {
-  using T = typename V::value_type;
-  sls_plan::ArenaReq r{};
-  r.src = v.empty() ? nullptr : static_cast<const void*>(v.data());
-  r.bytes = v.size() * sizeof(T);
-  r.out = reinterpret_cast<void**>(const_cast<T**>(out));
-  pl->arena_reqs.push_back(r);
-  return 0;
-}
-template <class T>
-int dalloc(sls_plan* pl, size_t count, T** out) {
-  sls_plan::ArenaReq r{};
-  r.src = nullptr; r.bytes = count * sizeof(T); r.out = reinterpret_cast<void**>(out); r.zero = true;
-  pl->arena_reqs.push_back(r);
-  return 0;
-}
-// Aux streams (launches 1… of a plan).  Launches of a handful of workgroups (the edge classes of a chain: 6–8 columns) go to
-// streams of the LOWEST priority: the launch with the most work — launch 0, on the caller's stream — then gets its workgroups
-// placed first and the stragglers take what is left, instead of 22 workgroups scattered over CUs that each lose a slot for the
-// whole pass (chain-4096: 1.95 → 1.75 ms).  Launches of real size keep the default priority (random10000_d2 with eleven of them:
-// 62.6 ms, against 66.5 ms when they all ran at low priority).  SLS_AUX_PRIORITY=0: default priority for all.
-hipError_t create_aux_stream(hipStream_t* st, bool low) {
-  int least = 0, greatest = 0;
-  const char* e = sls_knob("SLS_AUX_PRIORITY");
-  if (low && !(e && e[0] == '0') && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-    return hipStreamCreateWithPriority(st, hipStreamNonBlocking, least);
-  return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-}
-
-}  // namespace
 
 // The context slot's pinned staging memory (created on first use, 8 MiB): nullptr when unavailable or too small.
 unsigned char* sls::slot_pinned(sls_ctx* ctx, int slot, size_t bytes) {
@@ -190,80 +152,6 @@ int sls::pinned_download(sls_ctx* ctx, int slot, int dev, const void* d_src, con
 
 namespace {
 
-int arena_commit(sls_plan* pl) {
-  auto al = [](size_t b) { return (std::max<size_t>(b, 16) + 255) / 256 * 256; };
-  constexpr size_t kSmall = 256u << 10;
-  // order: small uploads (staged on the host and copied with ONE hipMemcpy — a README plan has ~15 tables of a few KB
-  // and each synchronous pageable copy costs ≈20 µs), then large uploads (copied in place), then scratch
-  auto rank = [&](const sls_plan::ArenaReq& r) { return r.src == nullptr ? 2 : (r.bytes <= kSmall ? 0 : 1); };
-  std::stable_sort(pl->arena_reqs.begin(), pl->arena_reqs.end(),
-                   [&](const sls_plan::ArenaReq& a, const sls_plan::ArenaReq& b) { return rank(a) < rank(b); });
-  size_t total = 0, small_bytes = 0;
-  for (auto& r : pl->arena_reqs) { r.off = total; total += al(r.bytes); if (rank(r) == 0) small_bytes = total; }
-  void* base = nullptr;
-  hipError_t e = hipSuccess;
-  {
-    // the context keeps one arena for reuse (a drop-in call builds and drops a plan per call: a hipMalloc + hipFree pair of
-    // tens of MB costs ≈0.2 ms, of a few hundred KB ≈30 µs); a second live plan gets its own
-    sls_ctx::Slot* sl = (ctx_is_live(pl->ctx) && pl->slot < (int)pl->ctx->slots.size()) ? &pl->ctx->slots[pl->slot] : nullptr;
-    const size_t want = std::max<size_t>(total, 256);
-    if (sl && !sl->arena_in_use) {
-      if (sl->arena_bytes < want || sl->arena_bytes > 4 * want + (64u << 20)) {      // too small, or wastefully large
-        if (sl->arena) (void)hipFree(sl->arena);
-        sl->arena = nullptr; sl->arena_bytes = 0;
-        e = hipMalloc(&sl->arena, want);
-        if (e != hipSuccess) return hipfail(pl->ctx, e, "hipMalloc (plan arena)");
-        sl->arena_bytes = want;
-      }
-      base = sl->arena; sl->arena_in_use = true; pl->arena_borrowed = true;
-    } else {
-      e = hipMalloc(&base, want);
-      if (e != hipSuccess) return hipfail(pl->ctx, e, "hipMalloc (plan arena)");
-      pl->dev_allocs.push_back(base);
-    }
-  }
-  pl->info.workspace_bytes += (int64_t)total;
-  if (small_bytes) {
-    // staged in the slot's pinned buffer when it fits (a pageable source costs the runtime one more copy and ≈15 µs)
-    std::vector<unsigned char> stage_v;
-    unsigned char* stage = slot_pinned(pl->ctx, pl->slot, small_bytes);
-    if (!stage) { stage_v.resize(small_bytes); stage = stage_v.data(); }
-    for (auto& r : pl->arena_reqs)
-      if (rank(r) == 0 && r.bytes) std::memcpy(stage + r.off, r.src, r.bytes);
-    e = hipMemcpy(base, stage, small_bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return hipfail(pl->ctx, e, "hipMemcpy H2D (plan arena, staged tables)");
-  }
-  for (auto& r : pl->arena_reqs) {
-    if (rank(r) == 1) {
-      e = hipMemcpy(static_cast<unsigned char*>(base) + r.off, r.src, r.bytes, hipMemcpyHostToDevice);
-      if (e != hipSuccess) return hipfail(pl->ctx, e, "hipMemcpy H2D (plan arena)");
-    }
-  }
-  // status / residual words are cleared (one memset over their contiguous range); the big workspaces need no clear
-  size_t z0 = total, z1 = 0;
-  for (auto& r : pl->arena_reqs) {
-    *r.out = static_cast<unsigned char*>(base) + r.off;
-    if (!r.src && r.zero && r.bytes <= (1u << 20)) { z0 = std::min(z0, r.off); z1 = std::max(z1, r.off + r.bytes); }
-  }
-  if (z1 > z0) {
-    bool contiguous = true;
-    for (auto& r : pl->arena_reqs)
-      if (!r.src && r.off >= z0 && r.off < z1 && !(r.zero && r.bytes <= (1u << 20))) contiguous = false;
-    if (contiguous) {
-      e = hipMemsetAsync(static_cast<unsigned char*>(base) + z0, 0, z1 - z0, pl->stream);
-      if (e != hipSuccess) return hipfail(pl->ctx, e, "hipMemset");
-    } else {
-      for (auto& r : pl->arena_reqs)
-        if (!r.src && r.zero && r.bytes <= (1u << 20)) {
-          e = hipMemsetAsync(static_cast<unsigned char*>(base) + r.off, 0, r.bytes, pl->stream);
-          if (e != hipSuccess) return hipfail(pl->ctx, e, "hipMemset");
-        }
-    }
-  }
-  pl->arena_reqs.clear();
-  return 0;
-}
-
 // Fold the timing events of finished launches into the accumulator.  blocking = false (the hot path, when the pool is
 // full): only launches the GPU has already completed are folded (hipEventQuery) — the host never waits; events still in
 // flight stay in the pool, compacted to its front.
@@ -287,20 +175,6 @@ int fold_events(sls_plan* pl, bool blocking = true) {
 }
 
 }  // namespace
-
-hipError_t sls::launch_twisted4_prepares(sls_plan* pl, hipStream_t stream) {
-  for (const auto& L : pl->launches) {
-    if (!(L.kind == LaunchKind::Twisted && L.four)) continue;
-    KernelParams q = pl->kp;
-    q.order_off = L.order_off; q.nsub = L.nsub; q.t4_stride = pl->t4_stride;
-    q.w_mcap = L.mcap;
-    q.t4_static = pl->d_t4s ? pl->d_t4s + L.t4s_off : nullptr; q.t4_static_stride = L.t4s_stride;
-    q.t4_images = pl->d_t4s ? pl->d_t4i + L.t4i_off : nullptr; q.t4_images_stride = L.t4i_stride;
-    hipError_t e = launch_twisted4_prepare(L.cls, q, pl->d_t4 + L.t4_off * pl->t4_stride, stream);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
 
 extern "C" {
 
@@ -450,296 +324,6 @@ int sls_h2_sf_packed_layout(const sls_dims* dims, const sls_plant* P, const sls_
     I.t_symbolic_s = now_s() - t0;
     *info = I;
   }
-  return 0;
-}
-
-int sls_h2_sf_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx,
-                   const sls_csc_bool* Su, int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols,
-                   int64_t group_begin, int64_t group_end, sls_plan** plan_out) {
-  return plan_create(ctx, dev_slot, dims, P, Sx, Su, ngroups, group_ptr, group_cols, group_begin, group_end, true, PlanOpts{}, plan_out);
-}
-
-// (extern "C++": declared in sls_plan.h with C++ linkage, defined here inside the extern "C" block of the ABI)
-extern "C++" int sls::plan_create(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx,
-                                  const sls_csc_bool* Su, int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols,
-                                  int64_t group_begin, int64_t group_end, bool want_packed, const PlanOpts& opt, sls_plan** plan_out) {
-  if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
-  if (!plan_out) return fail(ctx, SLS_EINVAL, "null plan_out");
-  *plan_out = nullptr;
-  if (dev_slot < 0 || dev_slot >= (int)ctx->devs.size()) return fail(ctx, SLS_EINVAL, "dev_slot out of range");
-  Inputs in{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
-  std::string msg;
-  int rc = validate_inputs(in, msg);
-  if (rc) return fail(ctx, rc, msg);
-  if (!ctx->ridge_x.empty() || !ctx->ridge_u.empty()) {
-    if ((!ctx->ridge_x.empty() && (int64_t)ctx->ridge_x.size() != dims->Nx) || (!ctx->ridge_u.empty() && (int64_t)ctx->ridge_u.size() != dims->Nu))
-      return fail(ctx, SLS_EINVAL, "sls_set_ridge: the weights' lengths do not match this plant's Nx / Nu");
-    if (dims->flags & SLS_SOLVE_SUM_OF_NORMS) return fail(ctx, SLS_EUNSUPPORTED, "the ridge term is not built for the sum-of-norms objective");
-    in.reg_x = ctx->ridge_x.empty() ? nullptr : ctx->ridge_x.data();
-    in.reg_u = ctx->ridge_u.empty() ? nullptr : ctx->ridge_u.data();
-  }
-
-  sls_plan* pl = new (std::nothrow) sls_plan();
-  if (!pl) return fail(ctx, SLS_ENOMEM, "out of memory");
-  pl->ctx = ctx; pl->dev = ctx->devs[dev_slot]; pl->slot = dev_slot;
-  pl->gbeg = group_begin; pl->gend = group_end; pl->ngroups_in = ngroups;
-  const double t0 = now_s();
-  pl->sym.want_packed = want_packed;
-  if (opt.force_tile && want_packed && opt.pk_override) pl->sym.pk_override = *opt.pk_override;
-  {
-    const char* e = sls_knob("SLS_HOST_TABLES");       // "1": mask / destination tables built on the host (diagnostics)
-    const bool host_tables = opt.host_tables >= 0 ? opt.host_tables != 0 : (e && e[0] == '1');
-    pl->sym.compact = !want_packed && !host_tables;
-  }
-
-  rc = build_symbolic(in, group_begin, group_end, pl->sym, msg);
-  if (rc) { delete pl; return fail(ctx, rc, msg); }
-  return plan_finish(ctx, dev_slot, dims, pl, t0, want_packed, opt, nullptr, plan_out);
-}
-
-// second half of plan creation (contract: sls_plan.h)
-extern "C++" int sls::plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_plan* pl, double t0, bool want_packed,
-                                  const PlanOpts& opt, const DeviceTables* dt, sls_plan** plan_out) {
-  int rc = 0;
-  const double t1 = now_s();
-  Symbolic& S = pl->sym;
-
-  auto bail = [&](int code) { sls_plan_destroy(pl); return code; };
-  const bool dbg_t = sls_knob("SLS_DEBUG_TIMING") != nullptr;
-  double tdbg = now_s();
-  auto tick = [&](const char* what) { if (dbg_t) { const double n = now_s(); std::fprintf(stderr, "[sls plan] %-28s %8.3f ms\n", what, 1e3 * (n - tdbg)); tdbg = n; } };
-  hipError_t e = hipSetDevice(pl->dev);
-  if (e != hipSuccess) return bail(hipfail(ctx, e, "hipSetDevice"));
-  {
-    sls_ctx::Slot& sl = ctx->slots[dev_slot];
-    if (sl.streams_in_use == 0) {
-      if (sl.streams.empty()) {
-        hipStream_t st0 = nullptr;
-        e = hipStreamCreateWithFlags(&st0, hipStreamNonBlocking);
-        if (e != hipSuccess) return bail(hipfail(ctx, e, "hipStreamCreate"));
-        sl.streams.push_back(st0);
-      }
-      pl->stream = sl.streams[0]; pl->streams_borrowed = true; sl.streams_in_use = 1;
-    } else if (opt.force_tile) {
-      // the refinement plan of the drop-in call: a stream of its own kept by the context (a hipStreamCreate per call cost 3 ms)
-      if (!sl.refine_stream) {
-        e = hipStreamCreateWithFlags(&sl.refine_stream, hipStreamNonBlocking);
-        if (e != hipSuccess) return bail(hipfail(ctx, e, "hipStreamCreate"));
-      }
-      pl->stream = sl.refine_stream; pl->stream_external = true;
-    } else {
-      e = hipStreamCreateWithFlags(&pl->stream, hipStreamNonBlocking);
-      if (e != hipSuccess) return bail(hipfail(ctx, e, "hipStreamCreate"));
-    }
-  }
-  for (int i = 0; i < kEventPool; ++i) { pl->ev_start[i] = nullptr; pl->ev_stop[i] = nullptr; }   // created on first use
-  pl->events_ok = true;
-  tick("setdevice+stream");
-
-  KernelParams& kp = pl->kp;
-  kp.T = (int32_t)S.T; kp.nsub = (int32_t)S.subs.size();
-  kp.delta_rel = 1e-12; kp.tol = 1e-12; kp.tol_ok = 1e-9; kp.max_iters = 8;   // δ scan: tools/iters_hist.py, DESIGN.md §3
-  kp.stag = 0.5;
-  kp.objective = (dims->flags & SLS_SOLVE_SUM_OF_NORMS) ? 1 : 0;
-  kp.son_maxit = 4000; kp.son_tol = 1e-9;
-  if (const char* e = sls_knob("SLS_SON_MAXIT")) kp.son_maxit = std::max(1, std::atoi(e));
-  if (const char* e = sls_knob("SLS_SON_TOL")) kp.son_tol = std::atof(e);
-  kp.son_anderson = 1;
-  if (const char* e = sls_knob("SLS_SON_ANDERSON")) kp.son_anderson = e[0] != '0';
-  kp.son_aa_start = 20;
-  if (const char* e = sls_knob("SLS_SON_AA_START")) kp.son_aa_start = std::max(0, std::atoi(e));
-  if (kp.objective == 1) {
-    // diagonal weights without feed-through only: a dense Hessian or a D11 column would change the cone structure
-    for (const SubDesc& sd : S.subs) {
-      bool bad = sd.has_w >= 2;
-      if (sd.has_w == 1) for (int32_t i = 0; i < sd.n + sd.m && !bad; ++i) bad = S.w_pool[(size_t)sd.off_w + sd.n + sd.m + i] != 0.0;
-      if (bad) return bail(fail(ctx, SLS_EUNSUPPORTED, "SLS_SOLVE_SUM_OF_NORMS needs a diagonal [C1 D12]'[C1 D12] and D11 = 0"));
-    }
-  }
-  kp.delta_first = 1e-15;            // one-wave (throughput) kernel only: DESIGN.md §5
-  if (const char* e = sls_knob("SLS_DELTA_FIRST")) kp.delta_first = std::atof(e);   // 0 = single attempt with delta_rel
-  if (const char* e = sls_knob("SLS_STAG")) kp.stag = std::atof(e);   // experiments only
-  if (const char* e = sls_knob("SLS_MAX_ITERS")) kp.max_iters = std::max(1, std::atoi(e));   // experiments only
-  kp.max_iters_slow = 48;
-  if (const char* e = sls_knob("SLS_MAX_ITERS_SLOW")) kp.max_iters_slow = std::max(0, std::atoi(e));   // 0: rounds 1–2 rule
-  if (const char* e = sls_knob("SLS_TOL")) kp.tol = std::atof(e);
-  if (const char* e = sls_knob("SLS_DELTA_REL")) kp.delta_rel = std::atof(e);
-  const int ncu = ctx->ncu[dev_slot];
-
-  // kernel selection (sls_routing.cpp): the launch list in submission order, its workspace layout, S.order launch by launch
-  RoutingResult route;
-  {
-    std::string msg;
-    rc = build_launch_list(S, kp.T, kp.objective, ncu, opt.force_tile, RoutingKnobs::from_env(), route, msg);
-    if (rc) return bail(fail(ctx, rc, msg));
-  }
-  pl->launches = std::vector<sls_plan::Launch>(route.launches.begin(), route.launches.end());
-  pl->has_tile = route.has_tile;
-  pl->too_large_subs = route.too_large;
-  pl->info_unsupported = (int64_t)route.too_large.size();
-  kp.w_nzA = S.max_row_A; kp.w_nzAc = S.max_row_At; kp.w_nzB = S.max_row_B; kp.w_nzBc = S.max_row_Bt;
-
-#define UP(vec, field)                                         \
-  do { int rc__ = upload(pl, vec, &kp.field); if (rc__) return bail(rc__); } while (0)
-  UP(S.A_csr.ptr, A_rowptr); UP(S.A_csr.idx, A_colidx); UP(S.A_csr.val, A_val);
-  UP(S.At_csr.ptr, At_rowptr); UP(S.At_csr.idx, At_colidx); UP(S.At_csr.val, At_val);
-  UP(S.B_csr.ptr, B_rowptr); UP(S.B_csr.idx, B_colidx); UP(S.B_csr.val, B_val);
-  UP(S.Bt_csr.ptr, Bt_rowptr); UP(S.Bt_csr.idx, Bt_colidx); UP(S.Bt_csr.val, Bt_val);
-  UP(S.subs, subs); UP(S.order, order);
-  if (dt) kp.idx_pool = dt->d_idx; else UP(S.idx_pool, idx_pool);
-  UP(S.w_pool, w_pool);
-  const uint64_t* d_cmask = nullptr; const int32_t* d_cbase = nullptr; const int64_t* d_coff = nullptr;
-  if (S.compact) {
-    // tables expanded on the device (expand_tables_kernel) from the compact form: 16 B per (column, time step) uploaded
-    // instead of 5 B per masked position
-    if (dt) { d_cmask = dt->d_cmask; d_cbase = dt->d_cbase; d_coff = dt->d_coff; }
-    else if ((rc = upload(pl, S.cmask, &d_cmask)) || (rc = upload(pl, S.cbase, &d_cbase)) || (rc = upload(pl, S.coff, &d_coff))) return bail(rc);
-    if ((rc = dalloc(pl, (size_t)std::max<int64_t>(S.md_total, 1), const_cast<uint8_t**>(&kp.mask_pool)))) return bail(rc);
-    if ((rc = dalloc(pl, (size_t)std::max<int64_t>(S.md_total, 1), const_cast<int32_t**>(&pl->d_dest)))) return bail(rc);
-  } else {
-    UP(S.mask_pool, mask_pool);
-    if ((rc = upload(pl, S.dest_pool, &pl->d_dest))) return bail(rc);
-  }
-#undef UP
-  if (want_packed && (rc = upload(pl, S.pdest_pool, &pl->d_pdest))) return bail(rc);
-  {
-    const size_t fac_need = route.fac_doubles, vec_need = route.vec_doubles, big_need = route.big_bytes;
-    // the two big scratch workspaces (never initialised, never read before written) come from the context's cache
-    const size_t need = (std::max<size_t>(fac_need, 1) + vec_need + 32) * sizeof(double) + 512 + big_need + 256;
-    sls_ctx::Slot& sl = ctx->slots[dev_slot];
-    void* sbase = nullptr;
-    if (!sl.scratch_in_use) {
-      if (sl.scratch_bytes < need) {
-        if (sl.scratch) (void)hipFree(sl.scratch);
-        sl.scratch = nullptr; sl.scratch_bytes = 0;
-        e = hipMalloc(&sl.scratch, need);
-        if (e != hipSuccess) return bail(hipfail(ctx, e, "hipMalloc (scratch workspace)"));
-        sl.scratch_bytes = need;
-      }
-      sbase = sl.scratch; sl.scratch_in_use = true; pl->scratch_borrowed = true;
-    } else {
-      e = hipMalloc(&pl->own_scratch, need);
-      if (e != hipSuccess) return bail(hipfail(ctx, e, "hipMalloc (scratch workspace)"));
-      sbase = pl->own_scratch;
-    }
-    pl->info.workspace_bytes += (int64_t)need;
-    kp.fac_ws = reinterpret_cast<double*>(sbase);
-    kp.vec_ws = vec_need ? kp.fac_ws + ((fac_need + 31) / 32) * 32 : nullptr;
-    if (big_need) {
-      const size_t boff = ((((fac_need + 31) / 32) * 32 + vec_need + 32) * sizeof(double) + 255) / 256 * 256;
-      pl->d_big = static_cast<unsigned char*>(sbase) + boff;
-    }
-  }
-  size_t n_lo = 0;
-  for (size_t li = 1; li < pl->launches.size(); ++li) {
-    sls_ctx::Slot& sl = ctx->slots[dev_slot];
-    const bool low = (int64_t)pl->launches[li].grid * 16 <= ncu;
-    if (pl->streams_borrowed) {
-      std::vector<hipStream_t>& pool = low ? sl.streams_lo : sl.streams;
-      const size_t idx = low ? n_lo++ : li;
-      while (pool.size() <= idx) {
-        hipStream_t st = nullptr;
-        if (create_aux_stream(&st, low) != hipSuccess) return bail(fail(ctx, SLS_EHIP, "aux stream creation failed"));
-        pool.push_back(st);
-      }
-      pl->launches[li].stream = pool[idx];
-    } else if (create_aux_stream(&pl->launches[li].stream, low) != hipSuccess) {
-      return bail(fail(ctx, SLS_EHIP, "aux stream creation failed"));
-    }
-    if (hipEventCreateWithFlags(&pl->launches[li].done, hipEventDisableTiming) != hipSuccess)
-      return bail(fail(ctx, SLS_EHIP, "aux event creation failed"));
-  }
-  if (pl->launches.size() > 1 && hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming) != hipSuccess)
-    return bail(fail(ctx, SLS_EHIP, "fork event creation failed"));
-  pl->status_init.assign((size_t)std::max(kp.nsub, 1), SLS_COL_OK);
-  for (int32_t q : pl->too_large_subs) pl->status_init[(size_t)S.subs[q].out_index] = SLS_COL_UNSUPPORTED;
-  if ((rc = upload(pl, pl->status_init, const_cast<const int32_t**>(&kp.status)))) return bail(rc);   // the kernels overwrite the words of what they solve
-  if ((rc = dalloc(pl, (size_t)std::max(kp.nsub, 1), &kp.resid))) return bail(rc);
-  if ((rc = dalloc(pl, (size_t)std::max(kp.nsub, 1), &kp.iters))) return bail(rc);
-  if ((rc = dalloc(pl, (size_t)std::max<size_t>(pl->launches.size(), 1), &pl->d_counters))) return bail(rc);   // tile kernel work queues
-  {
-    // objective evaluation: dense columns and coupled groups go to the general build, one workgroup each; their z_t is staged
-    // in LDS when the largest of them fits 48 KiB
-    int64_t need = 0;
-    for (size_t q = 0; q < S.subs.size(); ++q) {
-      const SubDesc& sd = S.subs[q];
-      if (sd.has_w != 2 && sd.has_w != 3) continue;
-      pl->obj_gen.push_back((int32_t)q);
-      need = std::max<int64_t>(need, (int64_t)(sd.has_w == 3 ? sd.pad_ : 1) * (sd.n + sd.m));
-    }
-    pl->obj_lds_doubles = (int)std::min<int64_t>(need, 6144);
-    if ((rc = upload(pl, S.obj_pool, &pl->d_obj)) || (rc = upload(pl, pl->obj_gen, &pl->d_gen))) return bail(rc);
-    if ((rc = dalloc(pl, (size_t)std::max(kp.nsub, 1) + 1, &pl->d_colobj))) return bail(rc);
-  }
-  if (const char* lv = sls_knob("SLS_PHASE_TIMERS")) {
-    if ((rc = dalloc(pl, (size_t)std::max(kp.nsub, 1) * 8, &kp.dbg))) return bail(rc);
-    kp.dbg_level = std::max(1, std::atoi(lv));
-  }
-  if (const char* ko = sls_knob("SLS_KNOCK_OUT")) kp.knock_out = std::atoi(ko);
-  {
-    // operator update: every plan can take new values of A / B2 (the device-resident route's operator comes through here too)
-    build_operator_value_map(S, pl->opmap);
-    const size_t nop = pl->opmap.row_pos.size();
-    if ((rc = upload(pl, pl->opmap.row_pos, &pl->d_upd_pos)) || (rc = upload(pl, pl->opmap.zero, &pl->d_upd_zero))) return bail(rc);
-    if ((rc = dalloc(pl, std::max<size_t>(nop, 1), &pl->d_upd_stage)) || (rc = dalloc(pl, 1, &pl->d_upd_rejected))) return bail(rc);
-  }
-  if (S.wu.updatable) {
-    // weights update (SLS_PLAN_WEIGHTS_UPDATABLE): what sls_plan_update_weights reads and writes besides w_pool, all from the arena
-    const size_t nv = (size_t)(S.Nx + S.Nu);
-    if ((rc = upload(pl, S.wu.b2, &pl->d_w_b2)) || (rc = upload(pl, S.wu.owner, &pl->d_w_owner)) ||
-        (rc = upload(pl, S.wu.diag, const_cast<const double**>(&pl->d_w_diag)))) return bail(rc);
-    if (!S.wu.ridge.empty() && (rc = upload(pl, S.wu.ridge, &pl->d_w_ridge))) return bail(rc);
-    if ((rc = dalloc(pl, nv, &pl->d_w_stage)) || (rc = dalloc(pl, 1, &pl->d_w_rejected))) return bail(rc);
-  }
-  for (auto& L : pl->launches)
-    if (L.kind == LaunchKind::Twisted && L.four) {
-      L.t4_off = pl->t4_records; pl->t4_records += L.nsub;
-      L.t4s_stride = twisted4_static_doubles(L.cls, kp.T);
-      L.t4s_off = pl->t4s_doubles; pl->t4s_doubles += L.t4s_stride * L.nsub;
-      L.t4i_stride = twisted4_image_doubles(L.cls, kp.T);
-      L.t4i_off = pl->t4i_doubles; pl->t4i_doubles += L.t4i_stride * L.nsub;
-    }
-  if (pl->t4_records) {
-    pl->t4_stride = twisted4_record_bytes(kp.w_nzA, kp.w_nzAc, kp.w_nzB, kp.w_nzBc, kp.T);
-    if ((rc = dalloc(pl, (size_t)(pl->t4_records * pl->t4_stride), &pl->d_t4))) return bail(rc);
-    // A four-wave launch has at most one column per compute unit, a column (T + 1) slots of 3 or 5 KiB: the README chain takes
-    // 5.3 MiB, 256 columns at T = 29 take 23 MiB.  Beyond the budget (256 columns: horizons past 84 in the three-tile classes,
-    // past 50 in the four-tile ones) the plan keeps no pool and its launches use the rebuild instantiation.  The setup images
-    // (15 KiB a column on the README chain: 0.9 MiB) belong to the same decision and the same budget.
-    const char* pre = sls_knob("SLS_T4_PRESTATIC");
-    if (!(pre && pre[0] == '0') && (pl->t4s_doubles + pl->t4i_doubles) * (int64_t)sizeof(double) <= kT4StaticBudget)
-      if ((rc = dalloc(pl, (size_t)pl->t4s_doubles, &pl->d_t4s)) || (rc = dalloc(pl, (size_t)pl->t4i_doubles, &pl->d_t4i))) return bail(rc);
-  }
-  tick("launch list + requests");
-  if ((rc = arena_commit(pl))) return bail(rc);
-  tick("arena commit (malloc+H2D)");
-  if (S.compact) {
-    e = launch_expand_tables(kp.subs, kp.nsub, kp.T, d_cmask, d_cbase, d_coff, const_cast<uint8_t*>(kp.mask_pool),
-                             const_cast<int32_t*>(pl->d_dest), pl->stream);
-    if (e != hipSuccess) return bail(hipfail(ctx, e, "launch expand_tables_kernel"));
-  }
-  // four-wave launches: the per-column records, behind the tables they read (same stream)
-  e = launch_twisted4_prepares(pl, pl->stream);
-  if (e != hipSuccess) return bail(hipfail(ctx, e, "launch twisted4_prepare_kernel"));
-  // the plan's own set-up work (status clear, table expansion) ran on the plan's stream: wait for that stream only — a
-  // device-wide wait here would also wait for whatever the caller has in flight on other streams (an RCCL collective, another plan)
-  e = hipStreamSynchronize(pl->stream);
-  if (e != hipSuccess) return bail(hipfail(ctx, e, "hipStreamSynchronize (plan set-up)"));
-  const double t2 = now_s();
-  tick("set-up stream synchronize");
-
-  sls_plan_info& I = pl->info;
-  I.n_subproblems = kp.nsub; I.n_values = S.n_values;
-  I.n_values_x = S.off_x[S.T]; I.n_values_u = S.n_values - S.off_x[S.T];
-  I.n_packed = S.n_packed; I.max_nx = S.max_n; I.max_nu = S.max_m; I.T = (int32_t)S.T; I.device = pl->dev;
-  I.flops_alg = S.flops_alg; I.bytes_alg = S.bytes_alg; I.t_symbolic_s = t1 - t0; I.t_upload_s = t2 - t1;
-  // the big host pools are no longer needed
-  pool_vec<uint8_t>().swap(S.mask_pool);
-  pool_vec<int32_t>().swap(S.dest_pool);
-  pool_vec<int32_t>().swap(S.pdest_pool);
-  pool_vec<int32_t>().swap(S.idx_pool);
-  pool_vec<uint64_t>().swap(S.cmask); pool_vec<int32_t>().swap(S.cbase); pool_vec<int64_t>().swap(S.coff);
-  *plan_out = pl;
   return 0;
 }
 
@@ -1016,19 +600,12 @@ static int residual_ensure(sls_plan* plan) {
   std::vector<int64_t> hp;
   std::vector<int32_t> hr;
   build_halo_rows(S.At_csr, S.Bt_csr, S.subs.data(), (int64_t)ns, idx.data(), S.sub_col.data(), hp, hr);
-  auto al = [](size_t b) { return (std::max<size_t>(b, 16) + 255) / 256 * 256; };
-  const size_t o_col = 0, o_ptr = o_col + al(4 * ns), o_rows = o_ptr + al(8 * (ns + 1)), o_out = o_rows + al(4 * hr.size()),
-               total = o_out + al(8 * (3 * ns + 2));
-  unsigned char* base = nullptr;
-  HIPCHK(plan->ctx, hipMalloc(reinterpret_cast<void**>(&base), total));
+  Arena ar;
+  ar.table(S.sub_col, &rs.sub_col); ar.table(hp, &rs.halo_ptr); ar.table(hr, &rs.halo_rows);     // hr may be empty: nothing to copy
+  ar.buffer(3 * ns + 2, &rs.out);
+  void* base = nullptr;
+  if (int rc = ar.commit(plan->ctx, &base, "hipMalloc (residual tables)", "hipMemcpy H2D (residual tables)")) return rc;
   plan->dev_allocs.push_back(base);
-  HIPCHK(plan->ctx, hipMemcpy(base + o_col, S.sub_col.data(), 4 * ns, hipMemcpyHostToDevice));
-  HIPCHK(plan->ctx, hipMemcpy(base + o_ptr, hp.data(), 8 * (ns + 1), hipMemcpyHostToDevice));
-  if (!hr.empty()) HIPCHK(plan->ctx, hipMemcpy(base + o_rows, hr.data(), 4 * hr.size(), hipMemcpyHostToDevice));
-  rs.sub_col = reinterpret_cast<const int32_t*>(base + o_col);
-  rs.halo_ptr = reinterpret_cast<const int64_t*>(base + o_ptr);
-  rs.halo_rows = reinterpret_cast<const int32_t*>(base + o_rows);
-  rs.out = reinterpret_cast<double*>(base + o_out);
   rs.ready = true;
   return 0;
 }
@@ -1174,37 +751,6 @@ int sls_plan_download(sls_plan* plan, const double* d_values, double* const* phi
   return 0;
 }
 
-void sls_plan_destroy(sls_plan* plan) {
-  if (!plan) return;
-  if (plan->refine) { sls_plan_destroy(plan->refine); plan->refine = nullptr; }
-  (void)hipSetDevice(plan->dev);
-  const bool ctx_alive = ctx_is_live(plan->ctx);
-  // a stream lent by the context (slot stream, refinement stream) died with it: sls_destroy has waited for nothing, hipFree below does
-  const bool stream_gone = !ctx_alive && (plan->streams_borrowed || plan->stream_external);
-  if (plan->stream && !stream_gone) (void)hipStreamSynchronize(plan->stream);
-  for (void* d : plan->dev_allocs) (void)hipFree(d);
-  if (plan->events_ok)
-    for (int i = 0; i < kEventPool; ++i) { if (plan->ev_start[i]) (void)hipEventDestroy(plan->ev_start[i]); if (plan->ev_stop[i]) (void)hipEventDestroy(plan->ev_stop[i]); }
-  for (auto& L : plan->launches) {
-    if (L.done) (void)hipEventDestroy(L.done);
-    if (L.stream && !plan->streams_borrowed) (void)hipStreamDestroy(L.stream);
-  }
-  if (plan->ev_fork) (void)hipEventDestroy(plan->ev_fork);
-  if (plan->ev_done) (void)hipEventDestroy(plan->ev_done);
-  if (plan->ev_batch) (void)hipEventDestroy(plan->ev_batch);
-  if (plan->ev_batch_done) (void)hipEventDestroy(plan->ev_batch_done);
-  if (plan->ev_upd) (void)hipEventDestroy(plan->ev_upd);
-  if (plan->stream && !plan->streams_borrowed && !plan->stream_external) (void)hipStreamDestroy(plan->stream);
-  if (ctx_alive && plan->slot < (int)plan->ctx->slots.size()) {
-    if (plan->streams_borrowed) plan->ctx->slots[plan->slot].streams_in_use = 0;
-    if (plan->scratch_borrowed) plan->ctx->slots[plan->slot].scratch_in_use = false;
-    if (plan->arena_borrowed) plan->ctx->slots[plan->slot].arena_in_use = false;
-    if (plan->ltab_borrowed) plan->ctx->slots[plan->slot].ltab_in_use = false;
-  }
-  if (plan->own_scratch) (void)hipFree(plan->own_scratch);
-  delete plan;
-}
-
 int sls_scatter_f64(sls_ctx* ctx, int dev_slot, void* hip_stream, const double* d_src, const int64_t* d_idx, int64_t n,
                     double* d_dst) {
   if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
@@ -1214,75 +760,6 @@ int sls_scatter_f64(sls_ctx* ctx, int dev_slot, void* hip_stream, const double* 
   hipError_t e = launch_scatter(d_src, d_idx, n, d_dst, reinterpret_cast<hipStream_t>(hip_stream));
   if (e != hipSuccess) return hipfail(ctx, e, "launch scatter_f64_kernel");
   return 0;
-}
-
-// Refinement (which columns and why: select_refinement_groups, sls_dropin_host.h; contract: sls_plan.h)
-extern "C++" int sls::attach_refinement(sls_plan* pl, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx,
-                                        const sls_csc_bool* Su, int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols,
-                                        hipStream_t stream, double* d_values, int64_t* n_refined, std::vector<int32_t>& stt,
-                                        std::vector<double>& res, std::vector<int32_t>& its, int packed) {
-  sls_ctx* ctx = pl->ctx;
-  *n_refined = 0;
-  const int64_t ns = pl->info.n_subproblems;
-  stt.resize(ns); its.resize(ns); res.resize(ns);
-  if (ns == 0) return 0;
-  if (pl->refine) { *n_refined = pl->refine->info.n_subproblems; return sls_plan_fetch_status(pl, stt.data(), res.data(), its.data()); }
-  int rc = fetch_status_raw(pl, stt.data(), res.data(), its.data());
-  if (rc) return rc;
-  const bool all_tile = pl->launches.size() == 1 && pl->launches[0].kind == LaunchKind::Tile;
-  if (all_tile) return 0;
-  std::vector<int64_t> gptr_all, gcols_all;
-  Inputs in0{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
-  normalise_groups(in0, gptr_all, gcols_all);
-  if (pl->gend > (int64_t)gptr_all.size() - 1 || gptr_all[pl->gend] - gptr_all[pl->gbeg] != ns)
-    return fail(ctx, SLS_EINVAL, "sls_plan_refine: the group list does not match the one this plan was built from");
-  std::vector<int32_t> cls((size_t)ns);
-  for (int64_t q = 0; q < ns; ++q) cls[(size_t)q] = pl->sym.subs[q].cls;
-  std::vector<char> on_twisted((size_t)ns, 0);
-  for (const auto& L : pl->launches)
-    if (L.kind == LaunchKind::Twisted)
-      for (int i = 0; i < L.nsub; ++i) {
-        const int64_t q = pl->sym.order[(size_t)L.order_off + i];
-        if (q >= 0 && q < ns) on_twisted[(size_t)q] = 1;
-      }
-  std::vector<int64_t> rg_ptr, rg_cols, rg_dst;
-  select_refinement_groups(pl->gbeg, pl->gend, gptr_all, gcols_all, dims->index_base, cls.data(), on_twisted.data(), stt.data(), its.data(),
-                           res.data(), rg_ptr, rg_cols, rg_dst);
-  if (rg_dst.empty()) return 0;
-  const int64_t nrg = (int64_t)rg_ptr.size() - 1;
-  sls_plan* rp = nullptr;
-  // a plan with the packed layout gets a refinement that numbers its free variables where the plan put them (pk_base of the
-  // refined subproblems), so that either layout of d_values can be written in place
-  const bool with_packed = pl->d_pdest != nullptr;
-  if (packed && !with_packed) return fail(ctx, SLS_EINVAL, "this plan was built without the packed layout");
-  std::vector<int64_t> pk_over;
-  if (with_packed) for (int64_t q : rg_dst) pk_over.push_back(pl->sym.pk_base[q]);
-  PlanOpts ropt; ropt.force_tile = true; ropt.pk_override = &pk_over;
-  rc = plan_create(ctx, pl->slot, dims, P, Sx, Su, nrg, rg_ptr.data(), rg_cols.data(), 0, nrg, with_packed, ropt, &rp);
-  if (rc) return rc;
-  rc = sls_plan_execute(rp, stream, d_values, packed);
-  if (rc == 0) rc = sls_plan_synchronize(rp, stream);
-  if (rc) { sls_plan_destroy(rp); return rc; }
-  pl->refine = rp; pl->refine_dst = std::move(rg_dst);
-  *n_refined = rp->info.n_subproblems;
-  return sls_plan_fetch_status(pl, stt.data(), res.data(), its.data());       // merged with the refinement's
-}
-
-int sls_plan_refine(sls_plan* plan, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
-                    int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, void* hip_stream, double* d_values,
-                    int packed, int64_t* n_refined) {
-  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
-  if (!dims || !P || !Sx || !Su || !d_values) return fail(plan->ctx, SLS_EINVAL, "null argument");
-  if (dims->flags & SLS_SOLVE_SUM_OF_NORMS) return fail(plan->ctx, SLS_EUNSUPPORTED, "sls_plan_refine: 𝓗₂ objective only");
-  if (plan->kp.objective != 0) return fail(plan->ctx, SLS_EUNSUPPORTED, "sls_plan_refine: 𝓗₂ objective only");
-  if (ngroups != plan->ngroups_in) return fail(plan->ctx, SLS_EINVAL, "sls_plan_refine: the group list does not match the one this plan was built from");
-  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
-  int64_t nr = 0;
-  std::vector<int32_t> stt, its; std::vector<double> res;
-  int rc = attach_refinement(plan, dims, P, Sx, Su, ngroups, group_ptr, group_cols, reinterpret_cast<hipStream_t>(hip_stream), d_values, &nr,
-                             stt, res, its, packed);
-  if (n_refined) *n_refined = nr;
-  return rc;
 }
 
 }  // extern "C"

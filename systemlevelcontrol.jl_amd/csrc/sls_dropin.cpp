@@ -1,4 +1,4 @@
-// sls_dropin.cpp — the one-shot calls of include/sls_mi355x.h, clients of the resident-plan API (sls_api.cpp):
+// sls_dropin.cpp — the one-shot calls of include/sls_mi355x.h, clients of the resident-plan API (sls_plan_build.cpp, sls_api.cpp):
 //   sls_h2_sf_solve            ≙ SLS_𝓗₂(P, 𝓢; 𝓘)                    (src/synthesis.jl:11-32)
 //   sls_h2_sf_solve_batch        several plants as one block-diagonal solve
 //   sls_h2_sf_solve_localized    masks built on the device from (d, α)

@@ -1,5 +1,5 @@
 // sls_object.h — what the objects that evaluate a resident Φ share (closed loop, controller, rollout, margin and its box, norms and
-// its covariance): the arena every one of them keeps its tables and buffers in, the gather that brings Φ from mask order into
+// its covariance): the arena every one of them keeps its tables and buffers in (sls_arena.h), the gather that brings Φ from mask order into
 // the object's own order, the scenario slots of a wave, and the per-scenario plant values of rollout and margin.  DESIGN §3.17.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,37 +8,10 @@
 #include <string>
 #include <vector>
 
+#include "sls_arena.h"
 #include "sls_internal.h"
 
 namespace sls {
-
-// One device allocation per object, laid out in the order of the declarations: tables to upload and buffers the object owns.
-// Nothing touches the device before commit; the object that receives the arena owns it and frees it with hipFree.
-class Arena {
- public:
-  // the room a block of b bytes takes: at least 16 bytes, rounded up to 256
-  static size_t al(size_t b) { return (std::max<size_t>(b, 16) + 255) / 256 * 256; }
-  // a table to upload; *out is its device copy after commit
-  template <class T>
-  void table(const std::vector<T>& v, const T** out) { add(v.data(), v.size() * sizeof(T), reinterpret_cast<const void**>(out)); }
-  // n elements the object owns, uninitialised; *out after commit
-  template <class T>
-  void buffer(size_t n, T** out) { add(nullptr, n * sizeof(T), reinterpret_cast<const void**>(const_cast<const T**>(out))); }
-  // bytes laid out so far: the offset of the next declaration, and after the last one the size of the arena
-  size_t bytes() const { return total_; }
-  // hipMalloc on the current device, the uploads (synchronous), the pointers.  On a failure nothing stays allocated, *arena is
-  // NULL and the result is hipfail's, with `what_malloc` or `what_upload`.
-  int commit(sls_ctx* ctx, void** arena, const char* what_malloc, const char* what_upload);
-  // The same layout inside bytes() of device memory the caller owns: the tables, declared first, are staged on the host and go
-  // up in ONE synchronous copy.  A failure is hipfail's with `what_upload`.
-  int commit_in(sls_ctx* ctx, void* base, const char* what_upload);
-
- private:
-  struct Req { const void* src; size_t bytes; const void** out; };
-  void add(const void* src, size_t bytes, const void** out) { reqs_.push_back({src, bytes, out}); total_ += al(bytes); }
-  std::vector<Req> reqs_;
-  size_t total_ = 0;
-};
 
 // vals[k] = values[perm[k]], k < n: Φ from the solve's mask order into the order of an object's table; nothing for n = 0.
 // A launch error is recorded on `ctx`.

@@ -55,14 +55,30 @@ int Arena::commit(sls_ctx* ctx, void** arena, const char* what_malloc, const cha
   return 0;
 }
 
-int Arena::commit_in(sls_ctx* ctx, void* base, const char* what_upload) {
-  size_t off = 0, up_end = 0;
-  for (const Req& r : reqs_) { *r.out = static_cast<unsigned char*>(base) + off; off += al(r.bytes); if (r.src) up_end = off; }
-  std::vector<unsigned char> stage(up_end);
-  off = 0;
-  for (const Req& r : reqs_) { if (r.src && r.bytes) std::memcpy(stage.data() + off, r.src, r.bytes); off += al(r.bytes); }
-  const hipError_t e = up_end ? hipMemcpy(base, stage.data(), up_end, hipMemcpyHostToDevice) : hipSuccess;
+int Arena::commit_in(sls_ctx* ctx, void* base, const Layout& lay, unsigned char* stage, const char* what_upload) {
+  unsigned char* b = static_cast<unsigned char*>(base);
+  std::vector<unsigned char> stage_v;
+  if (!stage) { stage_v.resize(lay.staged_end); stage = stage_v.data(); }
+  for (size_t i = 0; i < reqs_.size(); ++i) {
+    *reqs_[i].out = b + lay.off[i];
+    if (reqs_[i].src && lay.off[i] < lay.staged_end) std::memcpy(stage + lay.off[i], reqs_[i].src, reqs_[i].bytes);
+  }
+  hipError_t e = lay.staged_end ? hipMemcpy(b, stage, lay.staged_end, hipMemcpyHostToDevice) : hipSuccess;
+  for (size_t i = 0; i < reqs_.size() && e == hipSuccess; ++i)
+    if (reqs_[i].src && lay.off[i] >= lay.staged_end) e = hipMemcpy(b + lay.off[i], reqs_[i].src, reqs_[i].bytes, hipMemcpyHostToDevice);
   return e == hipSuccess ? 0 : hipfail(ctx, e, what_upload);
+}
+
+int Arena::clear(sls_ctx* ctx, void* base, const Layout& lay, hipStream_t stream, const char* what) const {
+  unsigned char* b = static_cast<unsigned char*>(base);
+  hipError_t e = hipSuccess;
+  if (lay.clear_hull) {
+    if (lay.clear_end > lay.clear_begin) e = hipMemsetAsync(b + lay.clear_begin, 0, lay.clear_end - lay.clear_begin, stream);
+  } else {
+    for (size_t i = 0; i < reqs_.size() && e == hipSuccess; ++i)
+      if (reqs_[i].own && reqs_[i].bytes <= kClearUpTo) e = hipMemsetAsync(b + lay.off[i], 0, reqs_[i].bytes, stream);
+  }
+  return e == hipSuccess ? 0 : hipfail(ctx, e, what);
 }
 
 int launch_gather_phi(sls_ctx* ctx, const double* d_values, const int32_t* d_perm, int64_t n, double* d_vals, hipStream_t stream) {

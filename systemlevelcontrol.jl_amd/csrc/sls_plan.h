@@ -1,10 +1,11 @@
-// sls_plan.h — the resident plan as the units behind the C ABI see it: sls_api.cpp builds, runs and destroys it, sls_plan_update.cpp
-// (updates and partial re-solves), sls_dropin.cpp (the one-shot calls), sls_symbolic_device.cpp (the device-resident symbolic
-// route, which ends in plan_finish) and sls_debug.cpp (include/sls_mi355x_debug.h) are its clients.
+// sls_plan.h — the resident plan as the units behind the C ABI see it: sls_plan_build.cpp builds and destroys it, sls_api.cpp runs
+// and reads it, sls_plan_update.cpp (updates and partial re-solves), sls_dropin.cpp (the one-shot calls), sls_symbolic_device.cpp
+// (the device-resident symbolic route, which ends in plan_finish) and sls_debug.cpp (include/sls_mi355x_debug.h) are its clients.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <vector>
 
 #include "sls_internal.h"
@@ -27,8 +28,6 @@ struct sls_plan {
   hipStream_t stream = nullptr;
   // device buffers
   std::vector<void*> dev_allocs;
-  struct ArenaReq { const void* src; size_t bytes; void** out; size_t off; bool zero; };
-  std::vector<ArenaReq> arena_reqs;
   sls::KernelParams kp{};  // dest_pool / out are patched per execute
   const int32_t* d_dest = nullptr;
   const int32_t* d_pdest = nullptr;
@@ -49,13 +48,11 @@ struct sls_plan {
   // the same kernel; kept exactly when d_t4s is, and counted in the same budget.
   double* d_t4i = nullptr;
   int64_t t4i_doubles = 0;
-  struct Launch : sls::LaunchSpec {    // what kernel selection decided + what the launch runs on
+  // what kernel selection decided + where a four-wave launch's columns sit in d_t4, d_t4s, d_t4i + what the launch runs on
+  struct Launch : sls::LaunchSpec, sls::T4Slot {
     explicit Launch(const sls::LaunchSpec& spec) : sls::LaunchSpec(spec) {}
     hipStream_t stream = nullptr;      // aux stream (launch 0 runs on the caller's stream)
     hipEvent_t done = nullptr;
-    int64_t t4_off = 0;                // four-wave launch: its first record in d_t4
-    int64_t t4s_off = 0, t4s_stride = 0;   // … its first double in d_t4s, doubles per column
-    int64_t t4i_off = 0, t4i_stride = 0;   // … and in d_t4i
   };
   std::vector<Launch> launches;
   hipEvent_t ev_fork = nullptr;
@@ -141,8 +138,20 @@ struct PlanOpts {
   int host_tables = -1;                             // mask / destination tables: 1 built on the host, 0 expanded on the device, -1 = SLS_HOST_TABLES decides
 };
 
-// sls_api.cpp (what sls_plan_update.cpp needs of it: wait_plan_done, enqueue_launches, launch_twisted4_prepares)
+// sls_api.cpp
 double now_s();
+// SLS_DEBUG_TIMING: the time since the last call (or since construction) to stderr, as "[prefix] what          1.234 ms"
+struct DebugTicker {
+  const char* prefix; int width; bool on; double last;
+  DebugTicker(const char* prefix_, int width_) : prefix(prefix_), width(width_), on(sls_knob("SLS_DEBUG_TIMING") != nullptr), last(now_s()) {}
+  void operator()(const char* what) {
+    if (!on) return;
+    const double n = now_s();
+    std::fprintf(stderr, "[%s] %-*s %8.3f ms\n", prefix, width, what, 1e3 * (n - last));
+    last = n;
+  }
+};
+// sls_plan_build.cpp
 int plan_create(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
                 int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, int64_t group_begin, int64_t group_end,
                 bool want_packed, const PlanOpts& opt, sls_plan** plan_out);
@@ -154,6 +163,7 @@ struct DeviceTables {            // sls_h2_sf_plan_localized (sls_symbolic_devic
 // uploads, workspaces.  `dt` != NULL: index sets and compact tables are used where they sit on the device.  Owns `pl`: a failure destroys it.
 int plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_plan* pl, double t0, bool want_packed, const PlanOpts& opt,
                 const DeviceTables* dt, sls_plan** plan_out);
+// sls_api.cpp (what sls_plan_update.cpp needs of it: wait_plan_done, enqueue_launches)
 // Host waits for the plan's last execute (and for nothing else on the device: a status read or a download must not stall on
 // a collective or on another plan running on some other stream).
 int wait_plan_done(sls_plan* pl);
@@ -168,11 +178,11 @@ struct SelectedRun {
 // join back into it (event edges only; nothing blocks the host).  sel = NULL: every launch in full.  Otherwise the same kernels,
 // LDS plans, workspaces and launch parameters over the kept items of each launch; a launch that keeps none is skipped.
 int enqueue_launches(sls_plan* plan, const KernelParams& kp, hipStream_t st, const SelectedRun* sel);
-// the prepared records of every four-wave launch of the plan, from the operator values the plan holds now
+// sls_plan_build.cpp: the prepared records of every four-wave launch of the plan, from the operator values the plan holds now
 hipError_t launch_twisted4_prepares(sls_plan* pl, hipStream_t stream);
-// the plan's own status words, without those of an attached refinement (sls_plan_fetch_status merges the two)
+// sls_api.cpp: the plan's own status words, without those of an attached refinement (sls_plan_fetch_status merges the two)
 int fetch_status_raw(sls_plan* plan, int32_t* col_status, double* residual, int32_t* iters);
-// the groups select_refinement_groups (sls_dropin_host.h) names get a second plan on the tile kernel (PlanOpts::force_tile), run
+// sls_plan_build.cpp: the groups select_refinement_groups (sls_dropin_host.h) names get a second plan on the tile kernel (PlanOpts::force_tile), run
 // into the same device array after the first and attached to `pl`, so that later executes and status reads include it; stt /
 // res / its come back merged.  Waits for `stream`; costs one status read when nothing qualifies.
 int attach_refinement(sls_plan* pl, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,

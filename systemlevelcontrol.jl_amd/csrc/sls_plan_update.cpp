@@ -1,4 +1,4 @@
-// sls_plan_update.cpp — what changes a resident plan after sls_api.cpp built it (include/sls_mi355x.h; the plan: sls_plan.h):
+// sls_plan_update.cpp — what changes a resident plan after sls_plan_build.cpp built it (include/sls_mi355x.h; the plan: sls_plan.h):
 //   partial re-solve   sls_plan_execute_columns, sls_plan_track_changes, sls_plan_execute_dirty, sls_plan_clear_dirty,
 //                      sls_plan_fetch_dirty                                                        
 //   plant update       sls_plan_update_plant, sls_plan_update_result, sls_plan_fetch_plant
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/sls_mi355x.h"
+#include "sls_object.h"
 #include "sls_plan.h"
 #include "sls_weights.h"
 
@@ -32,17 +33,15 @@ int partial_ensure(sls_plan* plan) {
     no = std::max(no, (size_t)L.order_off + (size_t)L.nsub);
     tab[3 * li] = L.order_off; tab[3 * li + 1] = L.nsub; tab[3 * li + 2] = (L.kind == LaunchKind::Tile && L.gw) ? 1 : 0;
   }
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t o_dirty = 0, o_marks = o_dirty + al(ns), o_chg = o_marks + al(ns), o_row = o_chg + al(nop), o_sel = o_row + al(nx),
-               o_pos = o_sel + al(4 * no), o_cnt = o_pos + al(4 * no), o_tab = o_cnt + al(8 * nl), total = o_tab + al(12 * nl);
-  unsigned char* base = nullptr;
-  HIPCHK(plan->ctx, hipMalloc(reinterpret_cast<void**>(&base), total));
+  Arena ar;
+  ar.buffer(ns, &pt.dirty); ar.buffer(ns, &pt.marks); ar.buffer(nop, &pt.chg); ar.buffer(nx, &pt.row_chg);
+  ar.buffer(no, &pt.sel_order); ar.buffer(no, &pt.sel_pos); ar.buffer(2 * nl, &pt.count);
+  const size_t buffer_bytes = ar.bytes();                  // the table, declared last, lies behind what is cleared
+  ar.table(tab, &pt.launch_tab);
+  void* base = nullptr;
+  if (int rc = ar.commit(plan->ctx, &base, "hipMalloc (partial re-solve buffers)", "hipMemcpy H2D (partial re-solve launch table)")) return rc;
   plan->dev_allocs.push_back(base);
-  HIPCHK(plan->ctx, hipMemset(base, 0, total));
-  HIPCHK(plan->ctx, hipMemcpy(base + o_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  pt.dirty = base + o_dirty; pt.marks = base + o_marks; pt.chg = base + o_chg; pt.row_chg = base + o_row;
-  pt.sel_order = reinterpret_cast<int32_t*>(base + o_sel); pt.sel_pos = reinterpret_cast<int32_t*>(base + o_pos);
-  pt.count = reinterpret_cast<int32_t*>(base + o_cnt); pt.launch_tab = reinterpret_cast<const int32_t*>(base + o_tab);
+  HIPCHK(plan->ctx, hipMemset(base, 0, buffer_bytes));
   pt.h_count.assign(2 * nl, 0);
   pt.ready = true;
   return 0;

@@ -11,6 +11,8 @@ namespace {
 bool knob_is(const char* name, char c) { const char* e = sls_knob(name); return e && e[0] == c; }
 char knob_char(const char* name) { const char* e = sls_knob(name); return e ? e[0] : 0; }
 int knob_int(const char* name, int dflt) { const char* e = sls_knob(name); return e ? std::atoi(e) : dflt; }
+double knob_double(const char* name, double dflt) { const char* e = sls_knob(name); return e ? std::atof(e) : dflt; }
+size_t round_up(size_t b, size_t to) { return (b + to - 1) / to * to; }
 
 enum class Bin { Wave, General, Wide, TileLds, TileGlb, TileBig };   // what a bin's columns run on (TileLds / TileGlb: where the block lives)
 enum TileBin { kLdsSmall, kLds, kGlbSmall, kGlb, kBig, kNumTileBins };   // small: two workgroups per CU (LDS: ≤ 6 tile rows; workspace: two panels fit twice)
@@ -42,6 +44,65 @@ RoutingKnobs RoutingKnobs::from_env() {
   k.tiny_first = sls_knob("SLS_TINY_FIRST") != nullptr;
   if (sls_knob("SLS_TILE_WPE")) k.tile_wpe = knob_is("SLS_TILE_WPE", '4');
   return k;
+}
+
+SolverKnobs SolverKnobs::from_env() {
+  SolverKnobs k;
+  k.delta_rel = knob_double("SLS_DELTA_REL", k.delta_rel);
+  k.tol = knob_double("SLS_TOL", k.tol);
+  k.max_iters = std::max(1, knob_int("SLS_MAX_ITERS", k.max_iters));
+  k.stag = knob_double("SLS_STAG", k.stag);
+  k.son_maxit = std::max(1, knob_int("SLS_SON_MAXIT", k.son_maxit));
+  k.son_tol = knob_double("SLS_SON_TOL", k.son_tol);
+  k.son_anderson = !knob_is("SLS_SON_ANDERSON", '0');
+  k.son_aa_start = std::max(0, knob_int("SLS_SON_AA_START", k.son_aa_start));
+  k.delta_first = knob_double("SLS_DELTA_FIRST", k.delta_first);
+  k.max_iters_slow = std::max(0, knob_int("SLS_MAX_ITERS_SLOW", k.max_iters_slow));
+  if (sls_knob("SLS_PHASE_TIMERS")) k.dbg_level = std::max(1, knob_int("SLS_PHASE_TIMERS", 1));
+  k.knock_out = knob_int("SLS_KNOCK_OUT", 0);
+  k.t4_prestatic = !knob_is("SLS_T4_PRESTATIC", '0');
+  return k;
+}
+
+void SolverKnobs::apply(KernelParams& kp) const {
+  kp.delta_rel = delta_rel; kp.tol = tol; kp.tol_ok = tol_ok; kp.max_iters = max_iters; kp.stag = stag;
+  kp.son_maxit = son_maxit; kp.son_tol = son_tol; kp.son_anderson = son_anderson; kp.son_aa_start = son_aa_start;
+  kp.delta_first = delta_first; kp.max_iters_slow = max_iters_slow; kp.dbg_level = dbg_level; kp.knock_out = knock_out;
+}
+
+int check_sum_of_norms_weights(const Symbolic& S, std::string& err) {
+  for (const SubDesc& sd : S.subs) {
+    bool bad = sd.has_w >= 2;
+    if (sd.has_w == 1) for (int32_t i = 0; i < sd.n + sd.m && !bad; ++i) bad = S.w_pool[(size_t)sd.off_w + sd.n + sd.m + i] != 0.0;
+    if (bad) { err = "SLS_SOLVE_SUM_OF_NORMS needs a diagonal [C1 D12]'[C1 D12] and D11 = 0"; return SLS_EUNSUPPORTED; }
+  }
+  return 0;
+}
+
+ScratchLayout scratch_layout(size_t fac_doubles, size_t vec_doubles, size_t big_bytes) {
+  ScratchLayout L;
+  // the slack (32 doubles, 512 + 256 bytes) covers the two roundings below whatever the sizes
+  L.bytes = (std::max<size_t>(fac_doubles, 1) + vec_doubles + 32) * sizeof(double) + 512 + big_bytes + 256;
+  L.vec_off = round_up(fac_doubles, 32);
+  L.big_off = round_up((L.vec_off + vec_doubles + 32) * sizeof(double), 256);
+  return L;
+}
+
+T4Pools t4_pool_layout(const std::vector<LaunchSpec>& launches, int T, bool prestatic) {
+  T4Pools P;
+  P.slots.resize(launches.size());
+  for (size_t li = 0; li < launches.size(); ++li) {
+    const LaunchSpec& L = launches[li];
+    if (!(L.kind == LaunchKind::Twisted && L.four)) continue;
+    T4Slot& s = P.slots[li];
+    s.t4_off = P.records; P.records += L.nsub;
+    s.t4s_stride = twisted4_static_doubles(L.cls, T);
+    s.t4s_off = P.static_doubles; P.static_doubles += s.t4s_stride * L.nsub;
+    s.t4i_stride = twisted4_image_doubles(L.cls, T);
+    s.t4i_off = P.image_doubles; P.image_doubles += s.t4i_stride * L.nsub;
+  }
+  P.keep_static = P.records > 0 && prestatic && (P.static_doubles + P.image_doubles) * (int64_t)sizeof(double) <= kT4StaticBudget;
+  return P;
 }
 
 // small wave classes (0..5) → ONE multi-class launch; mid classes (6..8) → one launch each;
@@ -273,7 +334,7 @@ int build_launch_list(Symbolic& S, int T, int objective, int ncu, bool force_til
       while (!L.big && L.oth_rows < npadL && tile_kernel_lds_bytes(nmax, mmax, nnzA, nnzB, L.mlds, L.oth_rows + 16) <= budget) L.oth_rows += 16;
       lds = tile_kernel_lds_bytes(nmax, mmax, nnzA, nnzB, L.mlds, L.oth_rows);
       if (L.big) {                                       // the carve goes to global memory; LDS only holds the block-reduction words
-        L.big_stride = (lds + 255) / 256 * 256;
+        L.big_stride = (int64_t)round_up(lds, 256);
         lds = 256;
       }
       L.vec_in_lds = 0;

@@ -1,6 +1,8 @@
 // sls_routing.h — kernel selection of a plan (pure C++, no HIP): which kernel every column runs on, the launch list with its
-// LDS plans, grids and submission order, and the layout of the launches' workspaces.  Host arithmetic over the symbolic
-// pass's result, so it is tested without a device (tests/test_host.py: golden launch lists, sanitizer build).
+// LDS plans, grids and submission order, and the layout of the launches' workspaces; with it the rest of plan construction's
+// host arithmetic (sls_plan_build.cpp): the solver parameters, the sum-of-norms weights check, the scratch workspace and the
+// four-wave pools.  Host arithmetic over the symbolic pass's result, so it is tested without a device (tests/test_host.py:
+// golden launch lists, sanitizer build).
 #pragma once
 #include <climits>
 #include <cstdint>
@@ -77,5 +79,50 @@ int build_launch_list(Symbolic& S, int T, int objective, int ncu, bool force_til
 
 // one launch as sls_plan_describe prints it
 std::string describe_launch(const LaunchSpec& L);
+
+// The solver's parameters and their diagnostic knobs (dead unless SLS_LAB=1), read once per plan.
+struct SolverKnobs {
+  double delta_rel = 1e-12, tol = 1e-12, tol_ok = 1e-9;   // SLS_DELTA_REL, SLS_TOL; δ scan: tools/iters_hist.py, DESIGN.md §3
+  int max_iters = 8;               // SLS_MAX_ITERS (≥ 1), experiments only
+  double stag = 0.5;               // SLS_STAG, experiments only
+  int son_maxit = 4000;            // SLS_SON_MAXIT (≥ 1)
+  double son_tol = 1e-9;           // SLS_SON_TOL
+  int son_anderson = 1;            // SLS_SON_ANDERSON=0 turns it off
+  int son_aa_start = 20;           // SLS_SON_AA_START (≥ 0)
+  double delta_first = 1e-15;      // SLS_DELTA_FIRST: one-wave (throughput) kernel only; 0 = single attempt with delta_rel
+  int max_iters_slow = 48;         // SLS_MAX_ITERS_SLOW (≥ 0); 0: rounds 1–2 rule
+  int dbg_level = 0;               // SLS_PHASE_TIMERS (≥ 1 when set): the plan then holds the phase counters
+  int knock_out = 0;               // SLS_KNOCK_OUT
+  bool t4_prestatic = true;        // SLS_T4_PRESTATIC=0: no plan-time static blocks
+  static SolverKnobs from_env();
+  void apply(KernelParams& kp) const;
+};
+
+// SLS_SOLVE_SUM_OF_NORMS takes diagonal weights without feed-through only (a dense Hessian or a D11 column would change the
+// cone structure): 0, or SLS_EUNSUPPORTED with `err` filled.
+int check_sum_of_norms_weights(const Symbolic& S, std::string& err);
+
+// The scratch workspace of a plan, from the totals of kernel selection: the factor workspace at its start, the vector workspace
+// vec_off doubles in (behind the factor doubles rounded up to 32), the big launches' carve buffers big_off bytes in.
+struct ScratchLayout { size_t bytes = 0, vec_off = 0, big_off = 0; };
+ScratchLayout scratch_layout(size_t fac_doubles, size_t vec_doubles, size_t big_bytes);
+
+// The pools of the four-wave launches (layouts: sls_device.h).  A launch has at most one column per compute unit, a column
+// (T + 1) slots of 3 or 5 KiB: the README chain takes 5.3 MiB, 256 columns at T = 29 take 23 MiB.  Beyond the budget (256
+// columns: horizons past 84 in the three-tile classes, past 50 in the four-tile ones) the plan keeps no pool of static blocks
+// and its launches use the rebuild instantiation.  The setup images (15 KiB a column on the README chain: 0.9 MiB) belong to
+// the same decision and the same budget.
+constexpr int64_t kT4StaticBudget = 64ll << 20;   // bytes of plan-time static blocks a plan may hold
+struct T4Slot {                          // where a four-wave launch's columns sit in the pools
+  int64_t t4_off = 0;                    // its first record
+  int64_t t4s_off = 0, t4s_stride = 0;   // its first double among the static blocks, doubles per column
+  int64_t t4i_off = 0, t4i_stride = 0;   // … and among the setup images
+};
+struct T4Pools {
+  std::vector<T4Slot> slots;             // one per launch (zeros for the others)
+  int64_t records = 0, static_doubles = 0, image_doubles = 0;
+  bool keep_static = false;              // static blocks and images are kept: within the budget and not SLS_T4_PRESTATIC=0
+};
+T4Pools t4_pool_layout(const std::vector<LaunchSpec>& launches, int T, bool prestatic);
 
 }  // namespace sls

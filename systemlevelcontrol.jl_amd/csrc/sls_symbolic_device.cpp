@@ -1,6 +1,6 @@
 // sls_symbolic_device.cpp — host drivers of the three device symbolic passes (kernels: sls_masks.hip; LDS list plans:
 // sls_symbolic_device.h): sls_localization_masks_device (mask_levels_kernel), sls_index_sets_device (index_sets_kernel) and
-// sls_h2_sf_plan_localized (column_tables_kernel, level_prefix_kernel), which ends in plan_finish (sls_api.cpp).  Each is a count
+// sls_h2_sf_plan_localized (column_tables_kernel, level_prefix_kernel), which ends in plan_finish (sls_plan_build.cpp).  Each is a count
 // pass, repeated with a doubled list capacity while a list overflows (count_with_retry), exclusive prefixes of the sizes, and
 // a fill pass with the same grid and LDS.
 #include <hip/hip_runtime.h>
@@ -203,9 +203,7 @@ int sls_h2_sf_plan_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dims, c
   if (rc) return fail(ctx, rc, msg);
   const int64_t Nx = dims->Nx, Nu = dims->Nu, T = dims->T;
   pl->gbeg = 0; pl->gend = Nx; pl->ngroups_in = 0;
-  const bool dbg_t = sls_knob("SLS_DEBUG_TIMING") != nullptr;
-  double tdbg = now_s();
-  auto tick = [&](const char* what) { if (dbg_t) { const double n = now_s(); std::fprintf(stderr, "[sls localized] %-34s %8.3f ms\n", what, 1e3 * (n - tdbg)); tdbg = n; } };
+  DebugTicker tick("sls localized", 34);
   tick("host: checks, pattern, operator CSR");
   hipError_t e = hipSetDevice(pl->dev);
   if (e != hipSuccess) return hipfail(ctx, e, "hipSetDevice");

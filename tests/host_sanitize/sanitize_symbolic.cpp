@@ -5,15 +5,20 @@
 // the two device passes (also on the hub, long-range, dense and stored-zero plants of tests/symbolic_cases.py), their LDS list plans
 // (csrc/sls_symbolic_device.h) and the host arithmetic of the device-resident route (localized_layout, against the host pass), the closed-loop FIR operator (restated exactly from the masks: check_fir), kernel selection (csrc/sls_routing.cpp: the launch list of every shard for
 // 1, 8 and 256 CUs, both objectives, with and without force_tile) — on a chain, a 2-D grid and a random plant, in both index bases, plus
-// malformed inputs that must be refused without touching memory out of bounds.  Exit code 0 = clean.
+// malformed inputs that must be refused without touching memory out of bounds; and the host arithmetic of plan construction: the arena's
+// layout (csrc/sls_arena.h) against offsets worked out by hand, the scratch workspace against its formula written out, the solver
+// knobs (every parse and clamp in lab mode; "defaults" as the first argument: the defaults, with lab mode off and every knob set),
+// the sum-of-norms weights check.  Exit code 0 = clean.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <string>
 #include <vector>
 
+#include "../../systemlevelcontrol.jl_amd/csrc/sls_arena.h"
 #include "../../systemlevelcontrol.jl_amd/csrc/sls_routing.h"
 #include "../../systemlevelcontrol.jl_amd/csrc/sls_symbolic.h"
 #include "../../systemlevelcontrol.jl_amd/csrc/sls_symbolic_device.h"
@@ -577,9 +582,155 @@ void check_localized_layout(const Plant& P, int64_t d, int64_t T, double alpha, 
               L.kx[T - 1] + 1 > L.kmax ? ">" : "<=");
 }
 
+// ---- host arithmetic of plan construction (csrc/sls_arena.h, csrc/sls_routing.h) ----
+// The arena's ranked layout, against offsets worked out by hand from the rule: tables of at most 256 KiB first (staged), larger
+// tables next, then empty tables and buffers, declaration order within each; every block takes max(bytes, 16) rounded up to 256.
+void check_arena_layout() {
+  using sls::Arena;
+  const std::vector<char> t100(100), t300k(300 << 10), tempty, t4k(4 << 10);
+  const char *p100, *p300k, *pempty, *p4k;
+  char *b64, *b2m, *b8;
+  auto same = [](const std::vector<size_t>& got, std::initializer_list<size_t> want) { return got == std::vector<size_t>(want); };
+  {
+    Arena a;
+    a.table(t100, &p100); a.table(t300k, &p300k); a.table(tempty, &pempty);
+    a.buffer(64, &b64); a.buffer((size_t)2 << 20, &b2m); a.buffer(8, &b8);
+    a.table(t4k, &p4k);
+    const Arena::Layout L = a.lay_out((size_t)256 << 10);
+    // 100 B at 0, 4 KiB at 256 → staged prefix 4352; 300 KiB (1200 · 256) at 4352 → 311552; the empty table's 256 B there; 64 B at
+    // 311808; 2 MiB at 312064 → 2409216; 8 B there; 2409472 in all
+    EXPECT(same(L.off, {0, 4352, 311552, 311808, 312064, 2409216, 256}), "arena: offsets of the mixed list");
+    EXPECT(L.total == 2409472 && a.bytes() == 2409472 && L.staged_end == 4352, "arena: total and staged prefix");
+    EXPECT(L.clear_begin == 311808 && L.clear_end == 2409224 && !L.clear_hull, "arena: the 2 MiB buffer splits the clear in two");
+    // every table staged (the localized route): 300 KiB joins the prefix, in declaration order
+    const Arena::Layout A = a.lay_out();
+    EXPECT(same(A.off, {0, 256, 311552, 311808, 312064, 2409216, 307456}) && A.staged_end == 311552 && A.total == 2409472, "arena: everything staged");
+  }
+  {
+    Arena a;
+    a.table(t100, &p100); a.table(t300k, &p300k); a.table(tempty, &pempty);
+    a.buffer(64, &b64); a.buffer(8, &b8);
+    a.table(t4k, &p4k);
+    const Arena::Layout L = a.lay_out((size_t)256 << 10);
+    EXPECT(same(L.off, {0, 4352, 311552, 311808, 312064, 256}) && L.total == 312320 && L.staged_end == 4352, "arena: offsets without the large buffer");
+    EXPECT(L.clear_begin == 311808 && L.clear_end == 312072 && L.clear_hull, "arena: one clear over the hull");
+  }
+  {
+    Arena a;                                      // tables only: nothing to clear
+    a.table(t100, &p100);
+    const Arena::Layout L = a.lay_out();
+    EXPECT(L.clear_begin == L.clear_end && L.clear_hull && L.total == 256 && L.staged_end == 256, "arena: no buffer, no clear");
+    EXPECT(Arena().lay_out().total == 0 && Arena().lay_out().staged_end == 0, "arena: empty");
+  }
+  std::printf("arena layout: done\n");
+}
+
+// the scratch workspace against the formula plan construction used before it was a function, written out
+void check_scratch_layout() {
+  const size_t cases[4][3] = {{0, 0, 0}, {33, 0, 0}, {1000, 77, 0}, {1000, 77, 4096}};
+  for (const auto& c : cases) {
+    const size_t fac = c[0], vec = c[1], big = c[2];
+    const sls::ScratchLayout L = sls::scratch_layout(fac, vec, big);
+    EXPECT(L.bytes == (std::max<size_t>(fac, 1) + vec + 32) * sizeof(double) + 512 + big + 256, "scratch: bytes");
+    EXPECT(L.vec_off == ((fac + 31) / 32) * 32, "scratch: vector workspace behind the factor doubles rounded to 32");
+    EXPECT(L.big_off == ((((fac + 31) / 32) * 32 + vec + 32) * sizeof(double) + 255) / 256 * 256, "scratch: carve buffers");
+    EXPECT((L.vec_off + vec) * sizeof(double) <= L.bytes && L.big_off + big <= L.bytes && (vec == 0 || L.vec_off >= fac), "scratch: regions inside");
+  }
+  const sls::ScratchLayout L = sls::scratch_layout(1000, 77, 4096);
+  EXPECT(L.bytes == 13736 && L.vec_off == 1024 && L.big_off == 9216, "scratch: (1000, 77, 4096) by hand");
+  std::printf("scratch layout: done\n");
+}
+
+const char* const kSolverKnobs[] = {"SLS_SON_MAXIT", "SLS_SON_TOL", "SLS_SON_ANDERSON", "SLS_SON_AA_START", "SLS_DELTA_FIRST", "SLS_STAG", "SLS_MAX_ITERS",
+                                    "SLS_MAX_ITERS_SLOW", "SLS_TOL", "SLS_DELTA_REL", "SLS_PHASE_TIMERS", "SLS_KNOCK_OUT", "SLS_T4_PRESTATIC"};
+
+bool solver_defaults(const sls::SolverKnobs& k) {
+  return k.delta_rel == 1e-12 && k.tol == 1e-12 && k.tol_ok == 1e-9 && k.max_iters == 8 && k.stag == 0.5 && k.son_maxit == 4000 && k.son_tol == 1e-9 &&
+         k.son_anderson == 1 && k.son_aa_start == 20 && k.delta_first == 1e-15 && k.max_iters_slow == 48 && k.dbg_level == 0 && k.knock_out == 0 &&
+         k.t4_prestatic;
+}
+
+// what the knobs write into the kernel parameters, and nothing else of them
+void check_apply(const sls::SolverKnobs& k) {
+  sls::KernelParams kp;
+  std::memset(&kp, 0x5a, sizeof kp);
+  sls::KernelParams before = kp;
+  k.apply(kp);
+  EXPECT(kp.delta_rel == k.delta_rel && kp.tol == k.tol && kp.tol_ok == k.tol_ok && kp.max_iters == k.max_iters && kp.stag == k.stag, "apply: 𝓗₂ parameters");
+  EXPECT(kp.son_maxit == k.son_maxit && kp.son_tol == k.son_tol && kp.son_anderson == k.son_anderson && kp.son_aa_start == k.son_aa_start, "apply: sum-of-norms parameters");
+  EXPECT(kp.delta_first == k.delta_first && kp.max_iters_slow == k.max_iters_slow && kp.dbg_level == k.dbg_level && kp.knock_out == k.knock_out, "apply: the rest");
+  EXPECT(kp.T == before.T && kp.nsub == before.nsub && kp.objective == before.objective && kp.dbg == before.dbg && kp.out == before.out, "apply: touches nothing else");
+}
+
+// lab mode off (SLS_LAB is latched on first use, so this is a process of its own): every knob is set and none is read
+int check_solver_defaults() {
+  unsetenv("SLS_LAB");
+  for (const char* name : kSolverKnobs) setenv(name, "7", 1);
+  const sls::SolverKnobs k = sls::SolverKnobs::from_env();
+  EXPECT(solver_defaults(k), "solver knobs: defaults outside lab mode");
+  check_apply(k);
+  if (fails) { std::fprintf(stderr, "%d check(s) failed\n", fails); return 1; }
+  std::printf("sanitize_symbolic: defaults clean\n");
+  return 0;
+}
+
+// lab mode on: nothing set gives the defaults; every knob's parse and clamp
+void check_solver_knobs() {
+  for (const char* name : kSolverKnobs) unsetenv(name);
+  EXPECT(solver_defaults(sls::SolverKnobs::from_env()), "solver knobs: defaults in lab mode");
+  auto with = [](std::initializer_list<std::pair<const char*, const char*>> env) {
+    for (const char* name : kSolverKnobs) unsetenv(name);
+    for (const auto& e : env) setenv(e.first, e.second, 1);
+    const sls::SolverKnobs k = sls::SolverKnobs::from_env();
+    for (const char* name : kSolverKnobs) unsetenv(name);
+    return k;
+  };
+  sls::SolverKnobs k = with({{"SLS_SON_MAXIT", "123"}, {"SLS_SON_TOL", "1e-6"}, {"SLS_SON_ANDERSON", "0"}, {"SLS_SON_AA_START", "5"}, {"SLS_DELTA_FIRST", "1e-13"},
+                            {"SLS_STAG", "0.25"}, {"SLS_MAX_ITERS", "12"}, {"SLS_MAX_ITERS_SLOW", "7"}, {"SLS_TOL", "1e-10"}, {"SLS_DELTA_REL", "1e-11"},
+                            {"SLS_PHASE_TIMERS", "2"}, {"SLS_KNOCK_OUT", "3"}, {"SLS_T4_PRESTATIC", "0"}});
+  EXPECT(k.son_maxit == 123 && k.son_tol == 1e-6 && k.son_anderson == 0 && k.son_aa_start == 5 && k.delta_first == 1e-13, "solver knobs: parse (1)");
+  EXPECT(k.stag == 0.25 && k.max_iters == 12 && k.max_iters_slow == 7 && k.tol == 1e-10 && k.delta_rel == 1e-11 && k.tol_ok == 1e-9, "solver knobs: parse (2)");
+  EXPECT(k.dbg_level == 2 && k.knock_out == 3 && !k.t4_prestatic, "solver knobs: parse (3)");
+  check_apply(k);
+  k = with({{"SLS_MAX_ITERS", "0"}, {"SLS_SON_MAXIT", "-4"}, {"SLS_SON_AA_START", "-3"}, {"SLS_MAX_ITERS_SLOW", "-1"}, {"SLS_DELTA_FIRST", "0"},
+            {"SLS_PHASE_TIMERS", "0"}, {"SLS_SON_ANDERSON", "1"}, {"SLS_T4_PRESTATIC", "1"}});
+  EXPECT(k.max_iters == 1 && k.son_maxit == 1 && k.son_aa_start == 0 && k.max_iters_slow == 0, "solver knobs: clamps");
+  EXPECT(k.delta_first == 0.0 && k.dbg_level == 1 && k.son_anderson == 1 && k.t4_prestatic, "solver knobs: DELTA_FIRST=0, PHASE_TIMERS=0 → level 1");
+  k = with({{"SLS_MAX_ITERS_SLOW", "0"}, {"SLS_SON_ANDERSON", "yes"}, {"SLS_PHASE_TIMERS", "x"}});
+  EXPECT(k.max_iters_slow == 0 && k.son_anderson == 1 && k.dbg_level == 1 && k.max_iters == 8, "solver knobs: 0 stays 0, anything but '0' is on");
+  std::printf("solver knobs: done\n");
+}
+
+// the sum-of-norms weights check: diagonal weights (has_w 0 / 1 with D11 = 0) pass; a dense Hessian and a D11 entry are refused
+void check_son_weights() {
+  const std::string text = "SLS_SOLVE_SUM_OF_NORMS needs a diagonal [C1 D12]'[C1 D12] and D11 = 0";
+  auto sub = [](int n, int m, int has_w, int64_t off_w) { sls::SubDesc sd{}; sd.n = n; sd.m = m; sd.has_w = has_w; sd.off_w = off_w; return sd; };
+  sls::Symbolic S;
+  S.subs.push_back(sub(2, 1, 0, 0));
+  S.subs.push_back(sub(2, 1, 1, 0));
+  S.w_pool.assign(6, 0.0); S.w_pool[0] = 2.0; S.w_pool[1] = 3.0; S.w_pool[2] = 0.5;     // diagonal, then a zero D11 part
+  std::string msg = "untouched";
+  EXPECT(sls::check_sum_of_norms_weights(S, msg) == 0 && msg == "untouched", "sum-of-norms weights: diagonal accepted");
+  sls::Symbolic D = S;
+  D.subs[0].has_w = 2;
+  EXPECT(sls::check_sum_of_norms_weights(D, msg) == SLS_EUNSUPPORTED && msg == text, "sum-of-norms weights: dense Hessian refused");
+  sls::Symbolic F = S;
+  F.w_pool[5] = 1e-300;                                                                 // the last D11 entry of the second column
+  msg.clear();
+  EXPECT(sls::check_sum_of_norms_weights(F, msg) == SLS_EUNSUPPORTED && msg == text, "sum-of-norms weights: D11 entry refused");
+  EXPECT(sls::check_sum_of_norms_weights(sls::Symbolic{}, msg) == 0, "sum-of-norms weights: no subproblem");
+  std::printf("sum-of-norms weights: done\n");
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+  if (argc > 1 && std::strcmp(argv[1], "defaults") == 0) return check_solver_defaults();
+  setenv("SLS_LAB", "1", 1);                             // latched by the first knob read: before everything else
+  check_solver_knobs();
+  check_arena_layout();
+  check_scratch_layout();
+  check_son_weights();
   check_list_plans();
   for (int base = 0; base < 2; ++base)
     for (int64_t T : {(int64_t)1, (int64_t)4})

@@ -253,7 +253,9 @@ def test_symbolic_pass_under_sanitizers(tmp_path):
     """The host symbolic pass and kernel selection (csrc/sls_symbolic.cpp, csrc/sls_routing.cpp: plain C++, no HIP) compiled by g++ with AddressSanitizer and
     UndefinedBehaviorSanitizer and driven by tests/host_sanitize/sanitize_symbolic.cpp over chain / grid / random plants, both
     index bases, all four table layouts, shard ranges with an empty shard, caller groups, the device passes' input builders, the
-    closed-loop operator and malformed inputs.  (GPU sanitizers are not available on this pool; this is the CPU build.)"""
+    closed-loop operator and malformed inputs; and over the host arithmetic of plan construction (csrc/sls_arena.h, the solver
+    knobs, the scratch layout and the sum-of-norms weights check of csrc/sls_routing.cpp).  A second run, outside lab mode, checks
+    the solver parameters' defaults.  (GPU sanitizers are not available on this pool; this is the CPU build.)"""
     import shutil
     import subprocess
     if shutil.which("g++") is None:
@@ -272,6 +274,12 @@ def test_symbolic_pass_under_sanitizers(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     assert "sanitize_symbolic: clean" in r.stdout and "runtime error" not in r.stderr
+    for done in ("solver knobs: done", "arena layout: done", "scratch layout: done", "sum-of-norms weights: done"):
+        assert done in r.stdout
+    env.pop("SLS_LAB", None)                                  # latched on first use: the defaults need a process of their own
+    r = subprocess.run([exe, "defaults"], capture_output=True, text=True, timeout=60, env=env)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "sanitize_symbolic: defaults clean" in r.stdout and "runtime error" not in r.stderr
 
 
 def _launch_list_cases():
