@@ -190,27 +190,66 @@ static inline int64_t wave_kernel_lds_bytes(int cls, int T, int mcap, int nzA, i
   return d * 8 + i * 4 + ((int64_t)T * nm_max + 15) / 16 * 16 + 16;
 }
 
-// LDS bytes of the twisted two-wave kernel (must match the carve in twisted_solve_column)
-static inline int64_t twisted_kernel_lds_bytes(int cls, int T, int mcap, int nzA, int nzAc, int nzB, int nzBc, int nm_max) {
-  const WaveClass w = wave_class(cls);
-  const int64_t NPL = w.npl, NP = (64 / w.npl) * w.rpl, LDM = NPL + 1;
-  const int64_t priv = NP * (NPL == 32 ? 40 : LDM) + 3 * NPL + 64;     // NPL = 32: image widened for the tiled Gauss–Jordan
-  int64_t d = 2 * priv + NP * LDM + 2 * NPL + 2 * 64 + 8 + (NPL + 64 + 8) / 2 + 3LL * (T + 1) * NPL + NPL * mcap + (int64_t)T * mcap +
-              (int64_t)(nzA + nzAc + nzB) * NPL + (int64_t)nzBc * 64;
-  int64_t i = (int64_t)(nzA + nzAc + nzB) * NPL + (int64_t)nzBc * 64;
-  return d * 8 + i * 4 + ((int64_t)T * nm_max + 15) / 16 * 16 + 16;
+// The column data both twisted kernels keep in LDS behind their private parts, in LDS order, written once: walked with a
+// pointer (D = double*, I = int) it gives a kernel its pointers, walked with a count that starts at the private part's
+// doubles (D = I = int64_t) it gives the host the byte count.  The two-wave kernel takes its pointers from it, so its carve and
+// twisted_kernel_lds_bytes cannot differ; the four-wave kernel writes the same walk out by hand (taking it from here costs one
+// instantiation scratch) and must be kept in step with it.  The int32 index lists start where the doubles end and are given as
+// word offsets from there; the masks (T·(ñx + ñu) bytes) follow the last list.
+template <class D, class I>
+struct ColumnCarve {
+  D hx, gx, hu, gu;         // hinv_x, g_x [NPL] each; hinv_u, g_u [64] each
+  D red, words;             // [8]: per-wave maxima, δ, (four-wave) the mask-repeat words; NPL + 64 + 8 int32: s_x, s_u, list lengths
+  D lam, rq, xs, Bd, us;    // [(T + 1)·NPL] each; dense B̃ [NPL·mcap]; [T·mcap]
+  D wxt, wut;               // the four-wave kernel's weight tables [(T + 1)·NPL], [T·mcap]; without them both equal arow_v
+  D arow_v, acol_v, brow_v, bcol_v, end;   // values [nzA·NPL], [nzAc·NPL], [nzB·NPL], [nzBc·64]; the end of the doubles
+  I arow_c, acol_c, brow_c, bcol_c, ints;  // local indices, same shapes; int32 words of the lists
+};
+template <class D, class I>
+__host__ __device__ static inline ColumnCarve<D, I> column_carve(D dp, I NPL, I T, I mcap, I nzA, I nzAc, I nzB, I nzBc, bool tables) {
+  ColumnCarve<D, I> c;
+  c.hx = dp;     dp += NPL;             c.gx = dp;     dp += NPL;
+  c.hu = dp;     dp += 64;              c.gu = dp;     dp += 64;
+  c.red = dp;    dp += 8;               c.words = dp;  dp += (NPL + 64 + 8) / 2;
+  c.lam = dp;    dp += (T + 1) * NPL;   c.rq = dp;     dp += (T + 1) * NPL;   c.xs = dp;   dp += (T + 1) * NPL;
+  c.Bd = dp;     dp += NPL * mcap;      c.us = dp;     dp += T * mcap;
+  c.wxt = dp;    if (tables) dp += (T + 1) * NPL;
+  c.wut = dp;    if (tables) dp += T * mcap;
+  c.arow_v = dp; dp += nzA * NPL;       c.acol_v = dp; dp += nzAc * NPL;
+  c.brow_v = dp; dp += nzB * NPL;       c.bcol_v = dp; dp += nzBc * 64;       c.end = dp;
+  I ip = 0;
+  c.arow_c = ip; ip += nzA * NPL;       c.acol_c = ip; ip += nzAc * NPL;
+  c.brow_c = ip; ip += nzB * NPL;       c.bcol_c = ip; ip += nzBc * 64;       c.ints = ip;
+  return c;
+}
+// LDS bytes of a kernel with `priv` private doubles in front of the block
+static inline int64_t column_carve_bytes(int64_t priv, int npl, int T, int mcap, int nzA, int nzAc, int nzB, int nzBc, int nm_max, bool tables) {
+  const ColumnCarve<int64_t, int64_t> c = column_carve<int64_t, int64_t>(priv, npl, T, mcap, nzA, nzAc, nzB, nzBc, tables);
+  return c.end * 8 + c.ints * 4 + ((int64_t)T * nm_max + 15) / 16 * 16 + 16;
 }
 
-// LDS bytes of the four-wave twisted kernel (must match the carve in twisted4_solve_column; NPL = 32 classes only)
-static inline int64_t twisted4_kernel_lds_bytes(int cls, int T, int mcap, int nzA, int nzAc, int nzB, int nzBc, int nm_max) {
+// LDS bytes of the twisted two-wave kernel: the private part of twisted_solve_column (which static_asserts it) + the shared block
+constexpr int64_t twisted_kernel_private_doubles(int npl, int rpl) {
+  const int64_t NPL = npl, NP = (64 / npl) * rpl, LDM = NPL + 1;
+  const int64_t priv = NP * (NPL == 32 ? 40 : LDM) + 3 * NPL + 64;     // per wave: mat (NPL = 32: widened for the tiled Gauss–Jordan), tmp, tmp2, wl, wul
+  return 2 * priv + NP * LDM;                                          // … and the hand-over image xch
+}
+static inline int64_t twisted_kernel_lds_bytes(int cls, int T, int mcap, int nzA, int nzAc, int nzB, int nzBc, int nm_max) {
   const WaveClass w = wave_class(cls);
-  const int64_t NPL = w.npl, NP = (64 / w.npl) * w.rpl;
+  return column_carve_bytes(twisted_kernel_private_doubles(w.npl, w.rpl), w.npl, T, mcap, nzA, nzAc, nzB, nzBc, nm_max, false);
+}
+
+// LDS bytes of the four-wave twisted kernel (NPL = 32 classes only): the private part of twisted4_solve_column (which
+// static_asserts it) + the shared block, whose walk that kernel repeats by hand
+constexpr int64_t twisted4_kernel_private_doubles(int npl, int rpl) {
+  const int64_t NPL = npl, NP = (64 / npl) * rpl;
   const int64_t TR = (NP + 7) / 8, NR = 8 * TR, LDT = 40, RS = (TR == 3) ? 32 : 48;
   const int64_t privc = NR * LDT + 2 * NPL, privh = 32, dirsz = NR * RS + NR * LDT + 2;
-  int64_t d = 2 * privc + 2 * privh + 2 * dirsz + NR * LDT + 2 * NPL + 2 * 64 + 8 + (NPL + 64 + 8) / 2 + 4LL * (T + 1) * NPL + NPL * mcap +
-              2LL * T * mcap + (int64_t)(nzA + nzAc + nzB) * NPL + (int64_t)nzBc * 64;
-  int64_t i = (int64_t)(nzA + nzAc + nzB) * NPL + (int64_t)nzBc * 64;
-  return d * 8 + i * 4 + ((int64_t)T * nm_max + 15) / 16 * 16 + 16;
+  return 2 * privc + 2 * privh + 2 * dirsz + NR * LDT;                 // chain waves, helpers, two directions, the image of Ã
+}
+static inline int64_t twisted4_kernel_lds_bytes(int cls, int T, int mcap, int nzA, int nzAc, int nzB, int nzBc, int nm_max) {
+  const WaveClass w = wave_class(cls);
+  return column_carve_bytes(twisted4_kernel_private_doubles(w.npl, w.rpl), w.npl, T, mcap, nzA, nzAc, nzB, nzBc, nm_max, true);
 }
 
 // Prepared record of one four-wave column (twisted4_prepare_kernel writes it at plan time, twisted4_solve_column copies it

@@ -43,6 +43,7 @@
 #include <utility>
 #include "sls_device.h"
 #include "sls_wave_util.h"
+#include "sls_column_ops.h"
 
 namespace sls {
 
@@ -506,7 +507,8 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
   const int capA = p.w_nzA, capAc = p.w_nzAc, capB = p.w_nzB, capBc = p.w_nzBc;
   const int c = twisted4_middle(T);
 
-  // ---- LDS carve (must match twisted4_kernel_lds_bytes) ----
+  // ---- LDS carve (must match twisted4_kernel_lds_bytes: the private part, then the walk of column_carve, sls_device.h) ----
+  static_assert(2 * PRIVC + 2 * PRIVH + 2 * DIRSZ + NR * LDT == twisted4_kernel_private_doubles(NPL, RPL), "the private part twisted4_kernel_lds_bytes counts");
   double* dp = reinterpret_cast<double*>(lds_raw);
   double* privc = dp + dir * PRIVC; dp += 2 * PRIVC;
   double* mat = privc; double* tmp = mat + NR * LDT; double* tmp2 = tmp + NPL;
@@ -1291,30 +1293,11 @@ __global__ __launch_bounds__(256) void twisted4_prepare_kernel(const KernelParam
     int cntA = 0, cntB = 0, cntAc = 0, cntBc = 0;
     if (lane < n) {
       const int g = sx[lane];
-      for (int e = p.A_rowptr[g]; e < p.A_rowptr[g + 1]; ++e) {
-        const double v = p.A_val[e];
-        const int loc = (v != 0.0) ? wbsearch(sx, n, p.A_colidx[e]) : -1;
-        if (loc >= 0 && cntA < capA) { arow_c[cntA * NPL + lane] = loc; arow_v[cntA * NPL + lane] = v; ++cntA; }
-      }
-      for (int e = p.B_rowptr[g]; e < p.B_rowptr[g + 1]; ++e) {
-        const double v = p.B_val[e];
-        const int loc = (v != 0.0) ? wbsearch(su, m, p.B_colidx[e]) : -1;
-        if (loc >= 0 && cntB < capB) { brow_c[cntB * NPL + lane] = loc; brow_v[cntB * NPL + lane] = v; ++cntB; }
-      }
-      for (int e = p.At_rowptr[g]; e < p.At_rowptr[g + 1]; ++e) {
-        const double v = p.At_val[e];
-        const int loc = (v != 0.0) ? wbsearch(sx, n, p.At_colidx[e]) : -1;
-        if (loc >= 0 && cntAc < capAc) { acol_c[cntAc * NPL + lane] = loc; acol_v[cntAc * NPL + lane] = v; ++cntAc; }
-      }
+      cntA = gather_list(p.A_rowptr, p.A_colidx, p.A_val, g, sx, n, capA, NPL, lane, arow_c, arow_v);
+      cntB = gather_list(p.B_rowptr, p.B_colidx, p.B_val, g, su, m, capB, NPL, lane, brow_c, brow_v);
+      cntAc = gather_list(p.At_rowptr, p.At_colidx, p.At_val, g, sx, n, capAc, NPL, lane, acol_c, acol_v);
     }
-    if (lane < m) {
-      const int g = su[lane];
-      for (int e = p.Bt_rowptr[g]; e < p.Bt_rowptr[g + 1]; ++e) {
-        const double v = p.Bt_val[e];
-        const int loc = (v != 0.0) ? wbsearch(sx, n, p.Bt_colidx[e]) : -1;
-        if (loc >= 0 && cntBc < capBc) { bcol_c[cntBc * 64 + lane] = loc; bcol_v[cntBc * 64 + lane] = v; ++cntBc; }
-      }
-    }
+    if (lane < m) cntBc = gather_list(p.Bt_rowptr, p.Bt_colidx, p.Bt_val, su[lane], sx, n, capBc, 64, lane, bcol_c, bcol_v);
     if (lane < NPL) {
       for (int e = cntA; e < capA; ++e) { arow_c[e * NPL + lane] = 0; arow_v[e * NPL + lane] = 0.0; }
       for (int e = cntB; e < capB; ++e) { brow_c[e * NPL + lane] = 0; brow_v[e * NPL + lane] = 0.0; }
@@ -1380,13 +1363,7 @@ __global__ __launch_bounds__(256) void twisted4_prepare_kernel(const KernelParam
     const int nzA = snz[0], nzB = snz[2];
     if (wv == 0) {
       // δ: the launch's reduction, operation for operation (rebuild instantiation, setup)
-      double sc = 0.0;
-      if (lane < n) {
-        sc = hx[lane];
-        for (int e = 0; e < nzA; ++e) { const double v = arow_v[e * NPL + lane]; sc = __builtin_fma(v * v, hx[arow_c[e * NPL + lane]], sc); }
-        for (int e = 0; e < nzB; ++e) { const double v = brow_v[e * NPL + lane]; sc = __builtin_fma(v * v, hu[brow_c[e * NPL + lane]], sc); }
-      }
-      const double dl_ = p.delta_rel * wave_max_f64(sc);
+      const double dl_ = p.delta_rel * wave_max_f64(tikhonov_scale<NPL>(lane, n, hx, hu, arow_c, arow_v, nzA, brow_c, brow_v, nzB));
       if (lane == 0) { sdelta = dl_; *reinterpret_cast<double*>(rec + twisted4_record_tail(capA, capAc, capB, capBc)) = dl_; }
     } else if (wv == 1) {
       if (lane < n) {

@@ -19,6 +19,7 @@
 #include <utility>
 #include "sls_device.h"
 #include "sls_wave_util.h"
+#include "sls_column_ops.h"
 
 namespace sls {
 
@@ -336,29 +337,13 @@ __device__ __forceinline__ void wave_solve_column(const KernelParams& p, const S
   int cntA = 0, cntAc = 0, cntB = 0, cntBc = 0;
   if (lane < n) {
     const int g = sx[lane];
-    for (int e = p.A_rowptr[g]; e < p.A_rowptr[g + 1]; ++e) {
-      const double v = p.A_val[e];
-      const int loc = (v != 0.0) ? wbsearch(sx, n, p.A_colidx[e]) : -1;
-      if (loc >= 0 && cntA < capA) { arow_c[cntA * NPL + lane] = loc; arow_v[cntA * NPL + lane] = v; ++cntA; }
-    }
-    for (int e = p.At_rowptr[g]; e < p.At_rowptr[g + 1]; ++e) {
-      const double v = p.At_val[e];
-      const int loc = (v != 0.0) ? wbsearch(sx, n, p.At_colidx[e]) : -1;
-      if (loc >= 0 && cntAc < capAc) { acol_c[cntAc * NPL + lane] = loc; acol_v[cntAc * NPL + lane] = v; ++cntAc; }
-    }
-    for (int e = p.B_rowptr[g]; e < p.B_rowptr[g + 1]; ++e) {
-      const double v = p.B_val[e];
-      const int loc = (v != 0.0) ? wbsearch(su, m, p.B_colidx[e]) : -1;
-      if (loc >= 0 && cntB < capB) { brow_c[cntB * NPL + lane] = loc; brow_v[cntB * NPL + lane] = v; Bd[lane * MC + loc] = v; ++cntB; }
-    }
+    cntA = gather_list(p.A_rowptr, p.A_colidx, p.A_val, g, sx, n, capA, NPL, lane, arow_c, arow_v);
+    cntAc = gather_list(p.At_rowptr, p.At_colidx, p.At_val, g, sx, n, capAc, NPL, lane, acol_c, acol_v);
+    cntB = gather_list<true>(p.B_rowptr, p.B_colidx, p.B_val, g, su, m, capB, NPL, lane, brow_c, brow_v, Bd + lane * MC);
   }
   if (lane < m) {
     const int g = su[lane];
-    for (int e = p.Bt_rowptr[g]; e < p.Bt_rowptr[g + 1]; ++e) {
-      const double v = p.Bt_val[e];
-      const int loc = (v != 0.0) ? wbsearch(sx, n, p.Bt_colidx[e]) : -1;
-      if (loc >= 0 && cntBc < capBc) { bcol_c[cntBc * 64 + lane] = loc; bcol_v[cntBc * 64 + lane] = v; ++cntBc; }
-    }
+    cntBc = gather_list(p.Bt_rowptr, p.Bt_colidx, p.Bt_val, g, sx, n, capBc, 64, lane, bcol_c, bcol_v);
   }
   const int nzA = wave_max_i32(cntA), nzAc = wave_max_i32(cntAc), nzB = wave_max_i32(cntB), nzBc = wave_max_i32(cntBc);
   WSYNC();
@@ -391,13 +376,7 @@ __device__ __forceinline__ void wave_solve_column(const KernelParams& p, const S
   };
 
   // ---- Tikhonov shift: relative to the largest possible Schur diagonal ----
-  double sc = 0.0;
-  if (lane < n) {
-    sc = hx[lane];
-    for (int e = 0; e < nzA; ++e) { const double v = arow_v[e * NPL + lane]; sc = __builtin_fma(v * v, hx[arow_c[e * NPL + lane]], sc); }
-    for (int e = 0; e < nzB; ++e) { const double v = brow_v[e * NPL + lane]; sc = __builtin_fma(v * v, hu[brow_c[e * NPL + lane]], sc); }
-  }
-  const double scmax = wave_max_f64(sc);
+  const double scmax = wave_max_f64(tikhonov_scale<NPL>(lane, n, hx, hu, arow_c, arow_v, nzA, brow_c, brow_v, nzB));
   double delta = p.delta_rel * scmax;      // set per attempt below
 
   // ---- residual pass: r = f − E z(λ) into rq, z to the output array, returns ‖r‖∞ ----
@@ -550,21 +529,7 @@ __device__ __forceinline__ void wave_solve_column(const KernelParams& p, const S
 
   if (resid > p.tol) {
     // =========================== factor: M = P_k = (D_k − L_k P_{k−1} L_kᵀ + δI)⁻¹ ===========================
-    auto matvec = [&](const double (&Pk)[RPL]) -> double {
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-#pragma unroll
-      for (int r = 0; r < RPL; ++r) {
-        const double y = tmp2[HS * r + h];
-        if ((r & 3) == 0) a0 = __builtin_fma(Pk[r], y, a0);
-        else if ((r & 3) == 1) a1 = __builtin_fma(Pk[r], y, a1);
-        else if ((r & 3) == 2) a2 = __builtin_fma(Pk[r], y, a2);
-        else a3 = __builtin_fma(Pk[r], y, a3);
-      }
-      double part = (a0 + a1) + (a2 + a3);
-      if (HS >= 2) part = xsum32(part);
-      if (HS >= 4) part = xsum16(part);
-      return part;
-    };
+    auto matvec = [&](const double (&Pk)[RPL]) -> double { return matvec_columns<NPL, RPL>(Pk, tmp2, h); };
     // ---- P_k in the workspace: stored half only, packed by columns (element (i ≤ j) at j(j+1)/2 + i), for the NPL = 32 classes
     // (the chains' ñx = 27: 378 of the 896 doubles of the register image — the P_k trips are what is left of this kernel's HBM
     // traffic).  Both directions go through the LDS image, which is idle between the block build and the next one and during
@@ -1214,8 +1179,9 @@ __device__ __forceinline__ void twisted_solve_column(const KernelParams& p, cons
   constexpr int HS = 64 / NPL, NP = HS * RPL, LDM = NPL + 1;
   constexpr bool TILED = (NPL == 32) && (SLS_TILED_GJ != 0);   // Gauss–Jordan on an 8×8 lane grid (see gauss_jordan_tiled)
   constexpr int LDT = 40;                                 // leading dimension of the image during layout changes (8·a + b: no bank conflict)
-  constexpr int MATSZ = NP * (NPL == 32 ? LDT : LDM);     // must match twisted_kernel_lds_bytes
+  constexpr int MATSZ = NP * (NPL == 32 ? LDT : LDM);
   constexpr int PRIV = MATSZ + 3 * NPL + 64;             // doubles per wave: mat, tmp, tmp2, wl, wul
+  static_assert(2 * PRIV + NP * LDM == twisted_kernel_private_doubles(NPL, RPL), "the private part twisted_kernel_lds_bytes counts");
   const int wv = threadIdx.x >> 6;                        // 0: upward wave (blocks 0..c), 1: downward wave (blocks T..c+1)
   const int lane = threadIdx.x & 63;
   const int h = lane / NPL, j = lane % NPL;
@@ -1224,36 +1190,26 @@ __device__ __forceinline__ void twisted_solve_column(const KernelParams& p, cons
   const int capA = p.w_nzA, capAc = p.w_nzAc, capB = p.w_nzB, capBc = p.w_nzBc;
   const int c = twisted_middle(T);
 
-  // ---- LDS carve (must match twisted_kernel_lds_bytes): per-wave private block first, then the shared column data ----
+  // ---- LDS carve: per-wave private blocks and the hand-over image first, then the shared column data, whose pointers come from
+  //      the walk twisted_kernel_lds_bytes counts with (column_carve, sls_device.h) ----
   double* dp = reinterpret_cast<double*>(lds_raw);
   double* priv = dp + wv * PRIV; dp += 2 * PRIV;
   double* mat = priv; double* tmp = mat + MATSZ; double* tmp2 = tmp + NPL; double* wl = tmp2 + NPL;
   double* wul = wl + NPL;
   double* xch = dp;    dp += NP * LDM;                   // W_c(ÃᵀP_{c+1}Ã)W_c handed from wave 1 to wave 0
-  double* hx = dp;     dp += NPL;
-  double* gx = dp;     dp += NPL;
-  double* hu = dp;     dp += 64;
-  double* gu = dp;     dp += 64;
-  double* red = dp;    dp += 8;                           // [0..1] per-wave maxima, [2] δ
-  int32_t* sx = reinterpret_cast<int32_t*>(dp);
+  const ColumnCarve<double*, int> cv = column_carve(dp, NPL, T, MC, capA, capAc, capB, capBc, false);
+  double* hx = cv.hx; double* gx = cv.gx; double* hu = cv.hu; double* gu = cv.gu;
+  double* red = cv.red;                                   // [0..1] per-wave maxima, [2] δ
+  int32_t* sx = reinterpret_cast<int32_t*>(cv.words);
   int32_t* su = sx + NPL;
   int32_t* nzs = su + 64;                                 // nzA, nzAc, nzB, nzBc
-  dp += (NPL + 64 + 8) / 2;
-  double* lam = dp;    dp += (T + 1) * NPL;
-  double* rq = dp;     dp += (T + 1) * NPL;
-  double* xs = dp;     dp += (T + 1) * NPL;               // x_t of the current residual pass (x_T ≡ 0)
-  double* Bd = dp;     dp += NPL * MC;
-  double* us = dp;     dp += T * MC;
-  double* arow_v = dp; dp += capA * NPL;
-  double* acol_v = dp; dp += capAc * NPL;
-  double* brow_v = dp; dp += capB * NPL;
-  double* bcol_v = dp; dp += capBc * 64;
-  int32_t* ip = reinterpret_cast<int32_t*>(dp);
-  int32_t* arow_c = ip; ip += capA * NPL;
-  int32_t* acol_c = ip; ip += capAc * NPL;
-  int32_t* brow_c = ip; ip += capB * NPL;
-  int32_t* bcol_c = ip; ip += capBc * 64;
-  uint8_t* mask = reinterpret_cast<uint8_t*>(ip);
+  double* lam = cv.lam; double* rq = cv.rq;
+  double* xs = cv.xs;                                     // x_t of the current residual pass (x_T ≡ 0)
+  double* Bd = cv.Bd; double* us = cv.us;
+  double* arow_v = cv.arow_v; double* acol_v = cv.acol_v; double* brow_v = cv.brow_v; double* bcol_v = cv.bcol_v;
+  int32_t* ip = reinterpret_cast<int32_t*>(cv.end);
+  int32_t* arow_c = ip + cv.arow_c; int32_t* acol_c = ip + cv.acol_c; int32_t* brow_c = ip + cv.brow_c; int32_t* bcol_c = ip + cv.bcol_c;
+  uint8_t* mask = reinterpret_cast<uint8_t*>(ip + cv.ints);
   double* pl = reinterpret_cast<double*>(lds_raw + p.w_pl_off);          // P_k blocks in LDS (PL only)
   const int32_t* dest = p.dest_pool + sd.off_dest;
   unsigned long long tc[4] = {0, 0, 0, 0};
@@ -1291,44 +1247,22 @@ __device__ __forceinline__ void twisted_solve_column(const KernelParams& p, cons
     int cntA = 0, cntB = 0;
     if (lane < n) {
       const int g = sx[lane];
-      for (int e = p.A_rowptr[g]; e < p.A_rowptr[g + 1]; ++e) {
-        const double v = p.A_val[e];
-        const int loc = (v != 0.0) ? wbsearch(sx, n, p.A_colidx[e]) : -1;
-        if (loc >= 0 && cntA < capA) { arow_c[cntA * NPL + lane] = loc; arow_v[cntA * NPL + lane] = v; ++cntA; }
-      }
-      for (int e = p.B_rowptr[g]; e < p.B_rowptr[g + 1]; ++e) {
-        const double v = p.B_val[e];
-        const int loc = (v != 0.0) ? wbsearch(su, m, p.B_colidx[e]) : -1;
-        if (loc >= 0 && cntB < capB) { brow_c[cntB * NPL + lane] = loc; brow_v[cntB * NPL + lane] = v; Bd[lane * MC + loc] = v; ++cntB; }
-      }
+      cntA = gather_list(p.A_rowptr, p.A_colidx, p.A_val, g, sx, n, capA, NPL, lane, arow_c, arow_v);
+      cntB = gather_list<true>(p.B_rowptr, p.B_colidx, p.B_val, g, su, m, capB, NPL, lane, brow_c, brow_v, Bd + lane * MC);
     }
     const int a0 = wave_max_i32(cntA), a2 = wave_max_i32(cntB);
     WSYNC();
-    double sc = 0.0;
-    if (lane < n) {
-      sc = hx[lane];
-      for (int e = 0; e < a0; ++e) { const double v = arow_v[e * NPL + lane]; sc = __builtin_fma(v * v, hx[arow_c[e * NPL + lane]], sc); }
-      for (int e = 0; e < a2; ++e) { const double v = brow_v[e * NPL + lane]; sc = __builtin_fma(v * v, hu[brow_c[e * NPL + lane]], sc); }
-    }
-    const double dl_ = p.delta_rel * wave_max_f64(sc);
+    const double dl_ = p.delta_rel * wave_max_f64(tikhonov_scale<NPL>(lane, n, hx, hu, arow_c, arow_v, a0, brow_c, brow_v, a2));
     if (lane == 0) { nzs[0] = a0; nzs[2] = a2; red[2] = dl_; }
   } else {
     int cntAc = 0, cntBc = 0;
     if (lane < n) {
       const int g = sx[lane];
-      for (int e = p.At_rowptr[g]; e < p.At_rowptr[g + 1]; ++e) {
-        const double v = p.At_val[e];
-        const int loc = (v != 0.0) ? wbsearch(sx, n, p.At_colidx[e]) : -1;
-        if (loc >= 0 && cntAc < capAc) { acol_c[cntAc * NPL + lane] = loc; acol_v[cntAc * NPL + lane] = v; ++cntAc; }
-      }
+      cntAc = gather_list(p.At_rowptr, p.At_colidx, p.At_val, g, sx, n, capAc, NPL, lane, acol_c, acol_v);
     }
     if (lane < m) {
       const int g = su[lane];
-      for (int e = p.Bt_rowptr[g]; e < p.Bt_rowptr[g + 1]; ++e) {
-        const double v = p.Bt_val[e];
-        const int loc = (v != 0.0) ? wbsearch(sx, n, p.Bt_colidx[e]) : -1;
-        if (loc >= 0 && cntBc < capBc) { bcol_c[cntBc * 64 + lane] = loc; bcol_v[cntBc * 64 + lane] = v; ++cntBc; }
-      }
+      cntBc = gather_list(p.Bt_rowptr, p.Bt_colidx, p.Bt_val, g, sx, n, capBc, 64, lane, bcol_c, bcol_v);
     }
     const int a1 = wave_max_i32(cntAc), a3 = wave_max_i32(cntBc);
     if (lane == 0) { nzs[1] = a1; nzs[3] = a3; }
@@ -1436,21 +1370,7 @@ __device__ __forceinline__ void twisted_solve_column(const KernelParams& p, cons
     WSYNC();
   };
 
-  auto matvec = [&](const double (&Pk)[RPL]) -> double {
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-#pragma unroll
-    for (int r = 0; r < RPL; ++r) {
-      const double y = tmp2[HS * r + h];
-      if ((r & 3) == 0) a0 = __builtin_fma(Pk[r], y, a0);
-      else if ((r & 3) == 1) a1 = __builtin_fma(Pk[r], y, a1);
-      else if ((r & 3) == 2) a2 = __builtin_fma(Pk[r], y, a2);
-      else a3 = __builtin_fma(Pk[r], y, a3);
-    }
-    double part = (a0 + a1) + (a2 + a3);
-    if (HS >= 2) part = xsum32(part);
-    if (HS >= 4) part = xsum16(part);
-    return part;
-  };
+  auto matvec = [&](const double (&Pk)[RPL]) -> double { return matvec_columns<NPL, RPL>(Pk, tmp2, h); };
   auto load_P = [&](int k, double (&Pk)[RPL]) {
     if constexpr (PL) {
       const double* b = pl + k * n * n;
