@@ -10,7 +10,9 @@
 //     upward:    D'_k = S_k − X P_{k−1} Xᵀ,   X = Ã W_{k−1}        downward:  G_k = S_k − X P_{k+1} Xᵀ,   X = W_k Ãᵀ
 // the next block is the Schur complement of the bordered matrix [[G, Xᵀ], [X, S]] on G = the block being inverted RIGHT NOW:
 // eliminating G's pivots from the border produces S − X G⁻¹ Xᵀ in place of S.  The chain wave inverts G by the same tiled
-// Gauss–Jordan as before and, per pivot, drops the pivot row (its pre-update values) and 1/pivot into LDS; the helper —
+// Gauss–Jordan as before and, per pivot, drops the pivot row (its pre-update values, times 1/pivot) and 1/pivot into LDS — the
+// lanes that own the row publish it one pivot ahead, and the chain wave itself reads its copy of the scaled row from that record
+// (two DS reads) instead of fetching the row lane by lane and scaling it again; the helper —
 // one or two pivots behind — applies that pivot to its own tiles of X and S (6 ds_swizzle, column p of X as a row through one
 // narrow LDS record, 18 FMA, no reciprocal chain).  When the chain wave has finished block k (store + fused
 // sweep), block k+1 is waiting for it in LDS in exactly the lane layout its Gauss–Jordan starts from.  Chain per block:
@@ -48,7 +50,7 @@
 namespace sls {
 
 #ifndef SLS_T4_EXP
-#define SLS_T4_EXP 0          // timing experiments (WRONG results on purpose): 1 = helper does not eliminate, 2 = helper without cross-lane traffic, 3 = without ds_bpermute
+#define SLS_T4_EXP 0          // timing experiment (WRONG results on purpose): 1 = helper does not eliminate
 #endif
 
 // meeting block.  The upward side carries the mask ramp (its helper needs a fresh static part for every block while the
@@ -131,22 +133,24 @@ typedef double d2_t __attribute__((ext_vector_type(2)));
 //   TR = 3: {row·d [b], row·d [b+8], row·d [b+16], d}        (SB = 4: two ds_write_b128)
 //   TR = 4: {row·d [b], [b+8], [b+16], [b+24], d, –}          (SB = 6: two ds_write_b128 + one ds_write_b64)
 // then the flag word: three (four) DS instructions per pivot instead of five (six) — each costs a lone wave ≈ 12 issue cycles.
+// The eight lanes are switched by a wave-uniform mask m (0xff: store, 0: the DS instructions issue with no lane active and write
+// nothing): a pivot that may not be published costs no branch, and no register merges behind one.
 template <int A, int O0>
-__device__ __forceinline__ void store_row8_3(unsigned addr, double v0, double v1, double v2, double d, unsigned addr_flag, int flagval) {
+__device__ __forceinline__ void store_row8_3(unsigned long long m, unsigned addr, double v0, double v1, double v2, double d, unsigned addr_flag, int flagval) {
   const d2_t q0 = {v0, v1}, q1 = {v2, d};
-  asm volatile("s_mov_b64 exec, 0xff\n\ts_lshl_b64 exec, exec, %[sh]\n\t"
+  asm volatile("s_lshl_b64 exec, %[m], %[sh]\n\t"
                "ds_write_b128 %[a], %[q0] offset:%[o0]\n\tds_write_b128 %[a], %[q1] offset:%[o1]\n\t"
                "ds_write_b32 %[af], %[vf]\n\ts_mov_b64 exec, -1"
-               :: [sh] "n"(8 * A), [a] "v"(addr), [q0] "v"(q0), [q1] "v"(q1), [af] "v"(addr_flag), [vf] "v"(flagval),
+               :: [m] "s"(m), [sh] "n"(8 * A), [a] "v"(addr), [q0] "v"(q0), [q1] "v"(q1), [af] "v"(addr_flag), [vf] "v"(flagval),
                   [o0] "n"(O0), [o1] "n"(O0 + 16) : "memory", "scc");
 }
 template <int A, int O0>
-__device__ __forceinline__ void store_row8_4(unsigned addr, double v0, double v1, double v2, double v3, double d, unsigned addr_flag, int flagval) {
+__device__ __forceinline__ void store_row8_4(unsigned long long m, unsigned addr, double v0, double v1, double v2, double v3, double d, unsigned addr_flag, int flagval) {
   const d2_t q0 = {v0, v1}, q1 = {v2, v3};
-  asm volatile("s_mov_b64 exec, 0xff\n\ts_lshl_b64 exec, exec, %[sh]\n\t"
+  asm volatile("s_lshl_b64 exec, %[m], %[sh]\n\t"
                "ds_write_b128 %[a], %[q0] offset:%[o0]\n\tds_write_b128 %[a], %[q1] offset:%[o1]\n\tds_write_b64 %[a], %[vd] offset:%[o2]\n\t"
                "ds_write_b32 %[af], %[vf]\n\ts_mov_b64 exec, -1"
-               :: [sh] "n"(8 * A), [a] "v"(addr), [q0] "v"(q0), [q1] "v"(q1), [vd] "v"(d), [af] "v"(addr_flag), [vf] "v"(flagval),
+               :: [m] "s"(m), [sh] "n"(8 * A), [a] "v"(addr), [q0] "v"(q0), [q1] "v"(q1), [vd] "v"(d), [af] "v"(addr_flag), [vf] "v"(flagval),
                   [o0] "n"(O0), [o1] "n"(O0 + 16), [o2] "n"(O0 + 32) : "memory", "scc");
 }
 // Lanes 0, 8, 16, … 56 (column 0 of the lane grid): TR doubles to addr + O0 + 64·q
@@ -185,17 +189,39 @@ __device__ __forceinline__ void store_xcol8_4(unsigned addr, double v0, double v
 
 // Tiled Gauss–Jordan of the chain wave on the 8×8 lane grid (lane (a, b) holds {rows a + 8·ri} × {columns b + 8·cj}), in place
 // on the tiles, publishing every pivot's row and reciprocal for the helper wave: rowbuf[pv] = eight packed records (RS doubles per pivot, see store_row8_*), then *flag = seqbase + pv + 1.
+// The chain wave takes its own copy of the scaled pivot row from that record.  The owner lanes of pivot p + 1 (lane-grid row
+// (p + 1) mod 8) hold row p + 1 in their tiles; as soon as the FMAs of pivot p that touch it are done they multiply it with the
+// predicted reciprocal and publish it, flag included, and every lane reads the record of its grid column back: two DS reads
+// where 2·TR ds_bpermute and TR multiplies used to fetch and scale the row a second time.  Same operands, same product, formed by
+// the lane that owns the row.  The reads follow the stores in the program of ONE wave, whose DS operations execute in order, and
+// every pivot has a slot of its own: a read can see neither an older nor a newer record than its pivot's.  A flag value is only
+// ever raised earlier than before (record p + 1 while pivot p is still being eliminated), which the helper's rule — flag ≥
+// seqbase + p + 1 ⇒ record p is valid — does not notice, except that its speculative read succeeds more often.
 template <int NP, int TR, int RS>
 __device__ __forceinline__ void gj_tiles_publish(double (&Tt)[TR * TR], const int lane, const int n, double* rowbuf, int* flag,
-                                                 const int seqbase, double* junk) {
+                                                 const int seqbase) {
   int ta = lane >> 3, tb = lane & 7, nn = __builtin_amdgcn_readfirstlane(n);
   asm volatile("" : "+v"(ta), "+v"(tb), "+s"(nn));
   double dnext = fast_rcp(readlane_f64(Tt[0], 0));
   constexpr int SB = (TR == 3) ? 4 : 6;                   // doubles per published record (see store_row8_*)
   static_assert(RS == 8 * SB, "row stride = eight records");
+  static_assert(TR == 3 || TR == 4, "store_row8_* are written for three or four tile columns");
   const unsigned pub_addr = lds_addr(rowbuf + SB * tb), flag_addr = lds_addr(flag);
-  (void)junk;
-  double col[TR], row[TR];
+  const double* row_rec = rowbuf + SB * tb;               // the record of this lane's grid column
+  double col[TR], tj[TR];
+  // Pivot q for the helper and for this wave: the row as it is BEFORE the update of pivot q, times 1/pivot (what an LU step uses),
+  // 1/pivot, then the flag — every lane multiplies, the eight owner lanes (a = q mod 8) store (m = 0xff; m = 0: nobody does).
+  auto publish = [&](auto q_c, const double xr, const unsigned long long m) {
+    constexpr int q = decltype(q_c)::value;
+    constexpr int qs = q / 8;
+    double t[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int cj = 0; cj < TR; ++cj) t[cj] = Tt[qs * TR + cj] * xr;
+    if constexpr (TR == 3) store_row8_3<q % 8, q * RS * 8>(m, pub_addr, t[0], t[1], t[2], xr, flag_addr, seqbase + q + 1);
+    else store_row8_4<q % 8, q * RS * 8>(m, pub_addr, t[0], t[1], t[2], t[3], xr, flag_addr, seqbase + q + 1);
+  };
+  // Column q by ds_swizzle inside the 8-lane group; the scaled row q from the record published just before: two DS reads (1/pivot,
+  // the fourth double of a three-tile record and the fifth of a four-tile one, is wave-uniform here already and is not read)
   auto fetch = [&](auto q_c) {
     constexpr int q = decltype(q_c)::value;
     constexpr int qa = q % 8, qs = q / 8;
@@ -203,14 +229,14 @@ __device__ __forceinline__ void gj_tiles_publish(double (&Tt)[TR * TR], const in
     for (int ri = 0; ri < TR; ++ri) {
       col[ri] = bcast8<qa>(Tt[ri * TR + qs]);
     }
-    const int src = (qa * 8 + tb) << 2;
-#pragma unroll
-    for (int cj = 0; cj < TR; ++cj) {
-      const double v = Tt[qs * TR + cj];
-      row[cj] = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(v)),
-                                 __builtin_amdgcn_ds_bpermute(src, __double2loint(v)));
-    }
+    const double* rec = row_rec + q * RS;
+    const d2_t r0 = *reinterpret_cast<const d2_t*>(rec);
+    tj[0] = r0[0]; tj[1] = r0[1];
+    if constexpr (TR == 3) tj[2] = rec[2];
+    else { const d2_t r1 = *reinterpret_cast<const d2_t*>(rec + 2); tj[2] = r1[0]; tj[TR - 1] = r1[1]; }
   };
+  // pivot 0 is published here: the caller's receive() has seen the helper's hand-over, so the previous block's records are consumed
+  publish(std::integral_constant<int, 0>{}, dnext, 0xffull);
   fetch(std::integral_constant<int, 0>{});
   static_for<NP>([&](auto pv_c) {
     constexpr int pv = decltype(pv_c)::value;
@@ -228,13 +254,13 @@ __device__ __forceinline__ void gj_tiles_publish(double (&Tt)[TR * TR], const in
         if (SLS_GJ_NR >= 1) xr = __builtin_fma(__builtin_fma(-pn, xr, 1.0), xr, xr);
         if (SLS_GJ_NR >= 2) xr = __builtin_fma(__builtin_fma(-pn, xr, 1.0), xr, xr);
       }
-      double c0[TR], tj[TR], tfix[TR];
+      double c0[TR], t0[TR], tfix[TR];
 #pragma unroll
       for (int ri = 0; ri < TR; ++ri) c0[ri] = col[ri];
 #pragma unroll
       for (int cj = 0; cj < TR; ++cj) {
-        tj[cj] = row[cj] * d;
-        tfix[cj] = (cj == ps && tb == pa) ? (1.0 + d) : tj[cj];
+        t0[cj] = tj[cj];
+        tfix[cj] = (cj == ps && tb == pa) ? (1.0 + d) : t0[cj];
       }
       __builtin_amdgcn_sched_barrier(0);
       SLS_ISA_MARK("chain-pivot");
@@ -247,19 +273,18 @@ __device__ __forceinline__ void gj_tiles_publish(double (&Tt)[TR * TR], const in
       const bool own = ta == pa;
 #pragma unroll
       for (int cj = 0; cj < TR; ++cj) {                     // (selects, not a branch: a register write inside a divergent region made the
-        const double nv = (cj == ps && tb == pa) ? d : tj[cj];   //  allocator copy the whole tile array around it, ≈30 v_mov per pivot)
+        const double nv = (cj == ps && tb == pa) ? d : t0[cj];   //  allocator copy the whole tile array around it, ≈30 v_mov per pivot)
         Tt[ps * TR + cj] = own ? nv : Tt[ps * TR + cj];
       }
-      if (SLS_T4_EXP != 4) {
-        // The helper's copy of this pivot: the row as it was BEFORE the update, times 1/pivot (what an LU step uses; `tj`, not `row`:
-        // a store of the raw row made the chain wave wait for its ds_bpermute results a whole reciprocal chain early), 1/pivot,
-        // then the flag — stored by the eight owner lanes (a = p mod 8) only, see store_row8_*.
-        static_assert(TR == 3 || TR == 4, "store_row8_* are written for three or four tile columns");
-        if constexpr (TR == 3) store_row8_3<pa, pv * RS * 8>(pub_addr, tj[0], tj[1], tj[2], d, flag_addr, seqbase + pv + 1);
-        else store_row8_4<pa, pv * RS * 8>(pub_addr, tj[0], tj[1], tj[2], tj[3], d, flag_addr, seqbase + pv + 1);
+      if constexpr (have_next) {
+        // Row pv + 1 is final once the FMAs above have touched tile row ns: publish it now, with the predicted reciprocal, and read it
+        // back behind the rest of this pivot's FMAs.  Not for a pivot that is not eliminated (pv + 1 = nn): no record, no flag —
+        // the stores then run with no lane active, and what the reads return is never used.
+        __builtin_amdgcn_sched_barrier(0);
+        publish(std::integral_constant<int, have_next ? pv + 1 : 0>{}, xr, (pv + 1 < nn) ? 0xffull : 0ull);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(std::integral_constant<int, have_next ? pv + 1 : 0>{});
       }
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (have_next) fetch(std::integral_constant<int, have_next ? pv + 1 : 0>{});
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int ri = 0; ri < TR; ++ri) {
@@ -308,6 +333,8 @@ __device__ __forceinline__ void helper_eliminate(double (&Xw)[TR * TR], double (
   // every lane reads back record b (rows b + 8·cj): two DS writes by eight lanes + two reads instead of 2·TR ds_bpermute.  The
   // slot is reused by the next pivot without a wait: DS operations of one wave execute in program order, the read of pivot q is
   // done before the write of pivot q + 1.  Only the S update (phase B) uses the row form, off the step's dependent chain.
+  // The column form stays a broadcast inside the 8-lane group: read from record a of the same buffer it costs four DS instructions
+  // less, and the launch was SLOWER (the helper's busy time fell, the chain wave's Gauss–Jordan grew).
   double xc[2][TR], xrw[2][TR];
   const unsigned xw_addr = lds_addr(xbuf + 4 * ta);
   const double* xr_rec = xbuf + 4 * tb;
@@ -957,7 +984,7 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
           unsigned long long q0 = (SLS_T4_PHASES != 0) ? __builtin_amdgcn_s_memtime() : 0;
           receive(M, s, mid);
           if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[0] += q1 - q0; q0 = q1; }
-          gj_tiles_publish<NP, TR, RS>(M, lane, n, rowbuf, flagA, s * 64, mat);
+          gj_tiles_publish<NP, TR, RS>(M, lane, n, rowbuf, flagA, s * 64);
           if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { __builtin_amdgcn_sched_barrier(0); asm volatile("" :: "v"(M[0])); const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[1] += q1 - q0; q0 = q1; }
           SLS_ISA_MARK("chain-tail");
           store_P(k, M);
@@ -984,7 +1011,7 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
           double Tt[TT];
           receive(Tt, s, mid);
           if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[0] += q1 - q0; q0 = q1; }
-          gj_tiles_publish<NP, TR, RS>(Tt, lane, n, rowbuf, flagA, s * 64, mat);
+          gj_tiles_publish<NP, TR, RS>(Tt, lane, n, rowbuf, flagA, s * 64);
           if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { __builtin_amdgcn_sched_barrier(0); asm volatile("" :: "v"(Tt[0])); const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[1] += q1 - q0; q0 = q1; }
           SLS_ISA_MARK("chain-tail");
           // tiles → column layout (lane (h, j): rows HS·r + h of column j) through the private image
@@ -1146,7 +1173,7 @@ __device__ __forceinline__ void twisted4_solve_column(const KernelParams& p, con
           for (int q = 0; q < TT; ++q) Xw[q] = Xn[q];
           if (s + 1 <= s_end) load_border((dir == 0) ? s + 1 : T - s, Xn);      // next step's border: its loads fly during this elimination
           if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[0] += q1 - q0; q0 = q1; }
-          if (SLS_T4_EXP != 1 && SLS_T4_EXP != 4) helper_eliminate<NP, TR, RS>(Xw, Sw, lane, n, rowbuf, flagA, (s - 1) * 64, xbuf, ph[2]);
+          if (SLS_T4_EXP != 1) helper_eliminate<NP, TR, RS>(Xw, Sw, lane, n, rowbuf, flagA, (s - 1) * 64, xbuf, ph[2]);
           if (SLS_T4_PHASES != 0 && p.dbg_level >= 2) { __builtin_amdgcn_sched_barrier(0); asm volatile("" :: "v"(Sw[0])); const unsigned long long q1 = __builtin_amdgcn_s_memtime(); ph[1] += q1 - q0; q0 = q1; }
         }
         hand_over(Sw, s);
