@@ -427,8 +427,13 @@ int  sls_plan_fetch_residual(sls_plan* plan, const double* d_values, int packed,
  * layers: no single objective belongs to a column); SLS_EINVAL when no solve has run with the option on, or n is wrong.   */
 int  sls_ctx_want_objective(sls_ctx* ctx, int on);
 int  sls_ctx_last_objective(sls_ctx* ctx, double* col_objective, int64_t n, double* total);
-/* average device time of the solve kernel over the launches since the last call, from
- * HIP events recorded on the launch stream around every sls_plan_execute.             */
+/* average device time of the solve over the timed sls_plan_execute calls since the last call, from HIP events on the launch
+ * stream.  A plan that executes as one launch (sls_plan_describe lists one kernel, no refinement is attached) has the events
+ * bound to that kernel's dispatch whenever its previous execute is still in flight: the average is then the dispatch's own
+ * begin -> end, the interval a kernel trace reports, and no marker is queued around the kernel.  Every other plan
+ * (size classes on forked streams, an attached refinement, the tile kernel behind its counter memset), an execute behind one
+ * that has already finished and an execute on a capturing stream record the two events around the execute's work: the average
+ * is the interval between the two stream markers, as before, which on one launch reads a few microseconds more.              */
 int  sls_plan_kernel_time_ms(sls_plan* plan, double* avg_ms, int64_t* n_launches);
 /* Human-readable list of the kernels one sls_plan_execute launches ("name nsub= grid= block= lds=;" per launch). */
 int  sls_plan_describe(const sls_plan* plan, char* buf, int64_t buflen);

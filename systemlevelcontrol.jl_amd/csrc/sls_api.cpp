@@ -340,7 +340,18 @@ int sls_plan_value_offsets(const sls_plan* plan, int64_t* off_x, int64_t* off_u)
   return 0;
 }
 
-extern "C++" int sls::enqueue_launches(sls_plan* plan, const KernelParams& kp, hipStream_t st, const SelectedRun* sel) {
+extern "C++" bool sls::one_kernel_run(const sls_plan* plan, hipStream_t st, const SelectedRun* sel) {
+  if (plan->exec_markers || plan->launches.size() != 1 || plan->has_tile) return false;   // has_tile: a counter memset goes first
+  if (sel && sel->count[0] <= 0) return false;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;       // a capturing stream keeps the recorded events: they become graph nodes
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return false;
+  // A full execute takes the dispatch path only behind an execute of this plan that is still in flight: that is where a record
+  // queues a marker the kernel then waits for.  A caller that waits for every execute gains nothing from it (no marker is queued
+  // on an idle stream), and the host wait for a dispatch with bound events was measured 7 µs longer than the wait for a marker.
+  return sel || (plan->last_done && hipEventQuery(plan->last_done) == hipErrorNotReady);
+}
+
+extern "C++" int sls::enqueue_launches(sls_plan* plan, const KernelParams& kp, hipStream_t st, const SelectedRun* sel, const LaunchEvents* ev) {
   const bool multi = plan->launches.size() > 1;
   if (plan->has_tile) HIPCHK(plan->ctx, hipMemsetAsync(plan->d_counters, 0, plan->launches.size() * sizeof(int32_t), st));
   if (multi) HIPCHK(plan->ctx, hipEventRecord(plan->ev_fork, st));
@@ -363,7 +374,7 @@ extern "C++" int sls::enqueue_launches(sls_plan* plan, const KernelParams& kp, h
       q.tile_oth_rows = L.oth_rows;
       q.work_counter = tile ? plan->d_counters + li : nullptr;
       q.big_ws = L.big ? plan->d_big + L.big_off : nullptr; q.big_stride = L.big_stride;
-      e = tile ? launch_tile(q, grid, L.lds, ls, L.mlds, L.two_per_cu, L.gw, L.big) : launch_general(q, grid, L.lds, ls, L.wide);
+      e = tile ? launch_tile(q, grid, L.lds, ls, L.mlds, L.two_per_cu, L.gw, L.big, ev) : launch_general(q, grid, L.lds, ls, L.wide, ev);
     } else {
       q.w_mcap = L.mcap; q.w_nm_max = L.nm_max; q.w_pl_off = L.pl_off;
       q.work_counter = (kp.objective == 1 && L.kind == LaunchKind::OneWave) ? plan->d_counters + li : nullptr;
@@ -374,8 +385,8 @@ extern "C++" int sls::enqueue_launches(sls_plan* plan, const KernelParams& kp, h
         q.t4_static = plan->d_t4s ? plan->d_t4s + L.t4s_off : nullptr; q.t4_static_stride = L.t4s_stride;
         q.t4_images = plan->d_t4s ? plan->d_t4i + L.t4i_off : nullptr; q.t4_images_stride = L.t4i_stride;
       }
-      e = (L.kind == LaunchKind::Twisted) ? (L.four ? launch_twisted4(L.cls, q, grid, L.lds, ls) : launch_twisted(L.cls, q, grid, L.lds, ls))
-                        : launch_wave(L.cls, q, grid, L.lds, ls);
+      e = (L.kind == LaunchKind::Twisted) ? (L.four ? launch_twisted4(L.cls, q, grid, L.lds, ls, ev) : launch_twisted(L.cls, q, grid, L.lds, ls, ev))
+                        : launch_wave(L.cls, q, grid, L.lds, ls, ev);
     }
     if (e != hipSuccess) return hipfail(plan->ctx, e, "kernel launch");
     if (li > 0) {
@@ -402,6 +413,18 @@ int sls_plan_execute(sls_plan* plan, void* hip_stream, double* d_values, int pac
   if (timed && !plan->ev_start[ev]) {
     HIPCHK(plan->ctx, hipEventCreate(&plan->ev_start[ev]));
     HIPCHK(plan->ctx, hipEventCreate(&plan->ev_stop[ev]));
+  }
+  // One solve kernel and nothing else (no forked size classes, no counter memset, no refinement behind it): the events ride on
+  // the kernel's own dispatch packet and no hipEventRecord is made.  A record on a busy stream queues a marker, a barrier packet
+  // with a completion signal of its own, so marker → kernel → marker were three dependent hand-offs in the queue where the
+  // result needs one.  The timed interval is then the dispatch's begin → end; last_done is the same handle as on the marker path.
+  if (!plan->refine && one_kernel_run(plan, st, nullptr)) {
+    if (!timed && !plan->ev_done) HIPCHK(plan->ctx, hipEventCreateWithFlags(&plan->ev_done, hipEventDisableTiming));
+    const LaunchEvents le = timed ? LaunchEvents{plan->ev_start[ev], plan->ev_stop[ev]} : LaunchEvents{nullptr, plan->ev_done};
+    if (int rc = enqueue_launches(plan, kp, st, nullptr, &le)) return rc;
+    if (timed) plan->ev_used = ev + 1;
+    plan->last_done = le.stop;
+    return 0;
   }
   if (timed) HIPCHK(plan->ctx, hipEventRecord(plan->ev_start[ev], st));
   // size classes run concurrently (enqueue_launches)

@@ -8,6 +8,7 @@
 
 #include "../../include/sls_mi355x.h"
 #include "sls_device.h"
+#include "sls_launch.h"
 #include "sls_objective.h"
 #include "sls_residual.h"
 
@@ -63,14 +64,14 @@ int fetch_to_host(sls_ctx* ctx, int slot, hipStream_t st, void* dst, const void*
 // ptrs[i]) through the slot's pinned ring.  0, a negative error, or 1 when the ring is not available (the caller falls back).
 int pinned_download(sls_ctx* ctx, int slot, int dev, const void* d_src, const std::vector<int64_t>& beg, const std::vector<void*>& ptrs);
 // the launchers of the .hip units
-hipError_t launch_general(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool wide);
+hipError_t launch_general(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool wide, const LaunchEvents* ev = nullptr);
 hipError_t launch_scatter(const double* src, const int64_t* idx, int64_t n, double* dst, hipStream_t stream);
-hipError_t launch_wave(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream);
-hipError_t launch_twisted(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream);
-hipError_t launch_twisted4(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_wave(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, const LaunchEvents* ev = nullptr);
+hipError_t launch_twisted(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, const LaunchEvents* ev = nullptr);
+hipError_t launch_twisted4(int cls, const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, const LaunchEvents* ev = nullptr);
 hipError_t launch_twisted4_prepare(int cls, const KernelParams& p, unsigned char* pool, hipStream_t stream);
 hipError_t launch_tile(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool mlds, bool two_per_cu,
-                       bool general_weights, bool big);
+                       bool general_weights, bool big, const LaunchEvents* ev = nullptr);
 hipError_t launch_expand_tables(const SubDesc* subs, int nsub, int T, const uint64_t* cmask, const int32_t* cbase, const int64_t* coff,
                                 uint8_t* mask_pool, int32_t* dest_pool, hipStream_t stream);
 hipError_t launch_mask_levels(const MaskParams& p, bool fill, int grid, size_t lds_bytes, hipStream_t stream);

@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <stdint.h>
 #include "sls_device.h"
+#include "sls_launch.h"
 
 namespace sls {
 
@@ -561,15 +562,16 @@ __global__ void expand_tables_kernel(const SubDesc* __restrict__ subs, int nsub,
 namespace sls {
 
 template <int TIMAX, bool OG>
-static hipError_t launch_general_v(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream) {
+static hipError_t launch_general_v(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, const LaunchEvents* ev) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&h2_column_general_kernel<TIMAX, OG>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((h2_column_general_kernel<TIMAX, OG>), dim3(grid), dim3(BLOCK), lds_bytes, stream, p);
+  if (ev) hipExtLaunchKernelGGL((h2_column_general_kernel<TIMAX, OG>), dim3(grid), dim3(BLOCK), (uint32_t)lds_bytes, stream, ev->start, ev->stop, 0, p);
+  else hipLaunchKernelGGL((h2_column_general_kernel<TIMAX, OG>), dim3(grid), dim3(BLOCK), lds_bytes, stream, p);
   return hipGetLastError();
 }
-hipError_t launch_general(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool wide) {
-  return wide ? launch_general_v<9, true>(p, grid, lds_bytes, stream) : launch_general_v<6, false>(p, grid, lds_bytes, stream);
+hipError_t launch_general(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool wide, const LaunchEvents* ev) {
+  return wide ? launch_general_v<9, true>(p, grid, lds_bytes, stream, ev) : launch_general_v<6, false>(p, grid, lds_bytes, stream, ev);
 }
 
 hipError_t launch_scatter(const double* src, const int64_t* idx, int64_t n, double* dst, hipStream_t stream) {

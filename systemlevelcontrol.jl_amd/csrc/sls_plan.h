@@ -58,6 +58,10 @@ struct sls_plan {
   hipEvent_t ev_fork = nullptr;
   hipEvent_t ev_done = nullptr;         // recorded on the caller's stream at the end of an execute that the event pool could not time
   hipEvent_t last_done = nullptr;       // the end of the last execute: its ev_stop (timed) or ev_done (untimed); what status reads and downloads wait for
+  // An execute that enqueues one solve kernel and nothing else, behind an execute still in flight (one_kernel_run), binds those
+  // events to the kernel's own dispatch (LaunchEvents, sls_launch.h) instead of recording them around it; SLS_EXEC_MARKERS=1
+  // (lab mode, read when the plan is built) keeps the records everywhere.
+  bool exec_markers = false;
   // event timing
   hipEvent_t ev_start[sls::kEventPool], ev_stop[sls::kEventPool];
   int ev_used = 0;
@@ -177,7 +181,12 @@ struct SelectedRun {
 // The launches of one execute on the caller's stream `st`: launch 0 there, the others on plan-owned streams that fork from /
 // join back into it (event edges only; nothing blocks the host).  sel = NULL: every launch in full.  Otherwise the same kernels,
 // LDS plans, workspaces and launch parameters over the kept items of each launch; a launch that keeps none is skipped.
-int enqueue_launches(sls_plan* plan, const KernelParams& kp, hipStream_t st, const SelectedRun* sel);
+// `ev` != NULL: the events go to the kernel's dispatch; only for a run of one kernel (one_kernel_run).
+int enqueue_launches(sls_plan* plan, const KernelParams& kp, hipStream_t st, const SelectedRun* sel, const LaunchEvents* ev = nullptr);
+// Whether a run (sel = NULL: a full execute) may bind its events to the dispatch: it enqueues exactly one kernel, the plan does
+// not ask for markers (exec_markers), `st` is not being captured into a graph, and — a full execute — the plan's last execute is
+// still in flight (a caller that waits for every execute keeps the markers: DESIGN §6, "One launch, no markers").
+bool one_kernel_run(const sls_plan* plan, hipStream_t st, const SelectedRun* sel);
 // sls_plan_build.cpp: the prepared records of every four-wave launch of the plan, from the operator values the plan holds now
 hipError_t launch_twisted4_prepares(sls_plan* pl, hipStream_t stream);
 // sls_api.cpp: the plan's own status words, without those of an attached refinement (sls_plan_fetch_status merges the two)

@@ -69,6 +69,7 @@ int take_main_stream(sls_plan* pl, bool refinement) {
   }
   for (int i = 0; i < kEventPool; ++i) { pl->ev_start[i] = nullptr; pl->ev_stop[i] = nullptr; }   // created on first use
   pl->events_ok = true;
+  { const char* e = sls_knob("SLS_EXEC_MARKERS"); pl->exec_markers = e && e[0] == '1'; }   // lab mode, read once per plan
   return 0;
 }
 

@@ -50,8 +50,9 @@ int partial_ensure(sls_plan* plan) {
 // The selected run over the subproblems marked in `d_marks` (by out_index).  compact_order_kernel builds the launch lists on
 // `st`; the host then WAITS for `st` — the one host wait of the partial re-solve — to read the per-launch counts (two int32 per
 // launch), because grids and skipped launches are decided on the host.  No timing events: sls_plan_kernel_time_ms keeps
-// averaging full executes.
-int execute_marked(sls_plan* plan, hipStream_t st, double* d_values, int packed, const uint8_t* d_marks, int64_t* n_solved) {
+// averaging full executes.  Ends with the run's end on `st` as last_done (ev_done): what status reads and downloads wait for.
+// clear_marks: the marks are zeroed on `st` inside the run (sls_plan_execute_dirty), once the compaction has read them.
+int execute_marked(sls_plan* plan, hipStream_t st, double* d_values, int packed, uint8_t* d_marks, bool clear_marks, int64_t* n_solved) {
   sls_plan::Partial& pt = plan->part;
   const size_t nl = plan->launches.size();
   KernelParams kp = plan->kp;
@@ -67,14 +68,20 @@ int execute_marked(sls_plan* plan, hipStream_t st, double* d_values, int packed,
   int64_t items = 0, cols = 0;
   for (size_t li = 0; li < nl; ++li) { items += pt.h_count[li]; cols += pt.h_count[nl + li]; }
   if (n_solved) *n_solved = cols;
-  if (items == 0) return 0;
-  SelectedRun sel{pt.sel_order, pt.sel_pos, pt.h_count.data()};
-  return enqueue_launches(plan, kp, st, &sel);
-}
-
-// the end of a partial run on the caller's stream: what status reads and downloads wait for
-int record_partial_done(sls_plan* plan, hipStream_t st) {
+  const size_t nmarks = (size_t)plan->kp.nsub;
   if (!plan->ev_done) HIPCHK(plan->ctx, hipEventCreateWithFlags(&plan->ev_done, hipEventDisableTiming));
+  SelectedRun sel{pt.sel_order, pt.sel_pos, pt.h_count.data()};
+  if (items > 0 && one_kernel_run(plan, st, &sel)) {
+    // one kernel: ev_done is the stop event of its dispatch, no marker behind it.  The marks go first — the host has waited for
+    // the compaction, their only reader — so that the kernel's end is still the end of the run.
+    if (clear_marks) HIPCHK(plan->ctx, hipMemsetAsync(d_marks, 0, nmarks, st));
+    const LaunchEvents le{nullptr, plan->ev_done};
+    if (int rc = enqueue_launches(plan, kp, st, &sel, &le)) return rc;
+    plan->last_done = plan->ev_done;
+    return 0;
+  }
+  if (items > 0) if (int rc = enqueue_launches(plan, kp, st, &sel)) return rc;
+  if (clear_marks) HIPCHK(plan->ctx, hipMemsetAsync(d_marks, 0, nmarks, st));
   HIPCHK(plan->ctx, hipEventRecord(plan->ev_done, st));
   plan->last_done = plan->ev_done;
   return 0;
@@ -153,8 +160,7 @@ int sls_plan_execute_columns(sls_plan* plan, void* hip_stream, double* d_values,
   for (int64_t i = 0; i < nsubs; ++i) pt.h_marks[(size_t)subs[i]] = 1;
   // h_marks belongs to the plan and execute_marked waits for `st` before it returns: the copy has read it by then
   HIPCHK(plan->ctx, hipMemcpyAsync(pt.marks, pt.h_marks.data(), (size_t)ns, hipMemcpyHostToDevice, st));
-  if (int rc = execute_marked(plan, st, d_values, packed, pt.marks, n_solved)) return rc;
-  return record_partial_done(plan, st);
+  return execute_marked(plan, st, d_values, packed, pt.marks, false, n_solved);
 }
 
 int sls_plan_track_changes(sls_plan* plan, int on) {
@@ -180,9 +186,7 @@ int sls_plan_execute_dirty(sls_plan* plan, void* hip_stream, double* d_values, i
   if (!pt.ready || plan->kp.nsub == 0) return 0;          // tracking was never on: no mark exists
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   HIPCHK(plan->ctx, hipSetDevice(plan->dev));
-  if (int rc = execute_marked(plan, st, d_values, packed, pt.dirty, n_solved)) return rc;
-  HIPCHK(plan->ctx, hipMemsetAsync(pt.dirty, 0, (size_t)plan->kp.nsub, st));
-  return record_partial_done(plan, st);
+  return execute_marked(plan, st, d_values, packed, pt.dirty, true, n_solved);
 }
 
 int sls_plan_clear_dirty(sls_plan* plan, void* hip_stream) {

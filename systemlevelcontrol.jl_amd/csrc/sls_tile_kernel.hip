@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sls_device.h"
+#include "sls_launch.h"
 
 namespace sls {
 
@@ -1443,27 +1444,28 @@ __global__ __launch_bounds__(TB) void tile_invert_kernel(const double* __restric
 namespace sls {
 
 template <bool MLDS, int WPE, bool GW, bool BIG = false>
-static hipError_t launch_tile_v(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream) {
+static hipError_t launch_tile_v(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, const LaunchEvents* ev) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&h2_column_tile_kernel<MLDS, WPE, GW, BIG>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((h2_column_tile_kernel<MLDS, WPE, GW, BIG>), dim3(grid), dim3(TB), lds_bytes, stream, p);
+  if (ev) hipExtLaunchKernelGGL((h2_column_tile_kernel<MLDS, WPE, GW, BIG>), dim3(grid), dim3(TB), (uint32_t)lds_bytes, stream, ev->start, ev->stop, 0, p);
+  else hipLaunchKernelGGL((h2_column_tile_kernel<MLDS, WPE, GW, BIG>), dim3(grid), dim3(TB), lds_bytes, stream, p);
   return hipGetLastError();
 }
 // two_per_cu: the variant compiled for 4 waves per SIMD (≤ 128 VGPRs), two workgroups share a CU when LDS allows;
 // general_weights: the build with the projected-CG loop (one workgroup per CU)
 hipError_t launch_tile(const KernelParams& p, int grid, size_t lds_bytes, hipStream_t stream, bool mlds, bool two_per_cu,
-                       bool general_weights, bool big) {
+                       bool general_weights, bool big, const LaunchEvents* ev) {
   if (big) {          // carve in the global workspace (p.big_ws): index sets beyond what LDS holds
     if (mlds || !p.big_ws) return hipErrorInvalidValue;
-    return general_weights ? launch_tile_v<false, 2, true, true>(p, grid, lds_bytes, stream) : launch_tile_v<false, 2, false, true>(p, grid, lds_bytes, stream);
+    return general_weights ? launch_tile_v<false, 2, true, true>(p, grid, lds_bytes, stream, ev) : launch_tile_v<false, 2, false, true>(p, grid, lds_bytes, stream, ev);
   }
   if (general_weights) {
-    if (two_per_cu && mlds) return launch_tile_v<true, 4, true>(p, grid, lds_bytes, stream);      // small columns: two workgroups per CU
-    return mlds ? launch_tile_v<true, 2, true>(p, grid, lds_bytes, stream) : launch_tile_v<false, 2, true>(p, grid, lds_bytes, stream);
+    if (two_per_cu && mlds) return launch_tile_v<true, 4, true>(p, grid, lds_bytes, stream, ev);      // small columns: two workgroups per CU
+    return mlds ? launch_tile_v<true, 2, true>(p, grid, lds_bytes, stream, ev) : launch_tile_v<false, 2, true>(p, grid, lds_bytes, stream, ev);
   }
-  if (mlds) return two_per_cu ? launch_tile_v<true, 4, false>(p, grid, lds_bytes, stream) : launch_tile_v<true, 2, false>(p, grid, lds_bytes, stream);
-  return two_per_cu ? launch_tile_v<false, 4, false>(p, grid, lds_bytes, stream) : launch_tile_v<false, 2, false>(p, grid, lds_bytes, stream);
+  if (mlds) return two_per_cu ? launch_tile_v<true, 4, false>(p, grid, lds_bytes, stream, ev) : launch_tile_v<true, 2, false>(p, grid, lds_bytes, stream, ev);
+  return two_per_cu ? launch_tile_v<false, 4, false>(p, grid, lds_bytes, stream, ev) : launch_tile_v<false, 2, false>(p, grid, lds_bytes, stream, ev);
 }
 
 // d_A, d_out: device n×n row-major; d_ws: device scratch of tile_ht(nt)·256 doubles (global variant)

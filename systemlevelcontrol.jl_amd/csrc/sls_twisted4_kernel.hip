@@ -44,6 +44,7 @@
 #include <stdint.h>
 #include <utility>
 #include "sls_device.h"
+#include "sls_launch.h"
 #include "sls_wave_util.h"
 #include "sls_column_ops.h"
 
@@ -1480,27 +1481,29 @@ hipError_t launch_twisted4_prepare(int cls, const KernelParams& p, unsigned char
 }
 
 template <int NPL, int RPL>
-static hipError_t launch_one_twisted4(const KernelParams& p, int grid, size_t lds, hipStream_t st) {
+static hipError_t launch_one_twisted4(const KernelParams& p, int grid, size_t lds, hipStream_t st, const LaunchEvents* ev) {
   if (p.t4_static == nullptr) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&h2_column_twisted4_kernel<NPL, RPL, false>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((h2_column_twisted4_kernel<NPL, RPL, false>), dim3(grid), dim3(256), lds, st, p);
+    if (ev) hipExtLaunchKernelGGL((h2_column_twisted4_kernel<NPL, RPL, false>), dim3(grid), dim3(256), (uint32_t)lds, st, ev->start, ev->stop, 0, p);
+    else hipLaunchKernelGGL((h2_column_twisted4_kernel<NPL, RPL, false>), dim3(grid), dim3(256), lds, st, p);
     return hipGetLastError();
   }
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&h2_column_twisted4_kernel<NPL, RPL, true>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((h2_column_twisted4_kernel<NPL, RPL, true>), dim3(grid), dim3(256), lds, st, p);
+  if (ev) hipExtLaunchKernelGGL((h2_column_twisted4_kernel<NPL, RPL, true>), dim3(grid), dim3(256), (uint32_t)lds, st, ev->start, ev->stop, 0, p);
+  else hipLaunchKernelGGL((h2_column_twisted4_kernel<NPL, RPL, true>), dim3(grid), dim3(256), lds, st, p);
   return hipGetLastError();
 }
 
-hipError_t launch_twisted4(int cls, const KernelParams& p, int grid, size_t lds, hipStream_t st) {
+hipError_t launch_twisted4(int cls, const KernelParams& p, int grid, size_t lds, hipStream_t st, const LaunchEvents* ev) {
   switch (cls) {
-    case 2: return launch_one_twisted4<32, 10>(p, grid, lds, st);
-    case 3: return launch_one_twisted4<32, 12>(p, grid, lds, st);
-    case 4: return launch_one_twisted4<32, 14>(p, grid, lds, st);
-    case 5: return launch_one_twisted4<32, 16>(p, grid, lds, st);
+    case 2: return launch_one_twisted4<32, 10>(p, grid, lds, st, ev);
+    case 3: return launch_one_twisted4<32, 12>(p, grid, lds, st, ev);
+    case 4: return launch_one_twisted4<32, 14>(p, grid, lds, st, ev);
+    case 5: return launch_one_twisted4<32, 16>(p, grid, lds, st, ev);
     default: return hipErrorInvalidValue;
   }
 }

@@ -18,6 +18,7 @@
 #include <stdint.h>
 #include <utility>
 #include "sls_device.h"
+#include "sls_launch.h"
 #include "sls_wave_util.h"
 #include "sls_column_ops.h"
 
@@ -1766,69 +1767,72 @@ __global__ __launch_bounds__(128, 1) void h2_column_twisted_kernel(const KernelP
 }
 
 template <int NPL, int RPL, bool PL>
-static hipError_t launch_one_twisted_v(const KernelParams& p, int grid, size_t lds, hipStream_t st) {
+static hipError_t launch_one_twisted_v(const KernelParams& p, int grid, size_t lds, hipStream_t st, const LaunchEvents* ev) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&h2_column_twisted_kernel<NPL, RPL, PL>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((h2_column_twisted_kernel<NPL, RPL, PL>), dim3(grid), dim3(128), lds, st, p);
+  if (ev) hipExtLaunchKernelGGL((h2_column_twisted_kernel<NPL, RPL, PL>), dim3(grid), dim3(128), (uint32_t)lds, st, ev->start, ev->stop, 0, p);
+  else hipLaunchKernelGGL((h2_column_twisted_kernel<NPL, RPL, PL>), dim3(grid), dim3(128), lds, st, p);
   return hipGetLastError();
 }
 template <int NPL, int RPL>
-static hipError_t launch_one_twisted(const KernelParams& p, int grid, size_t lds, hipStream_t st) {
-  return p.w_pl_off > 0 ? launch_one_twisted_v<NPL, RPL, true>(p, grid, lds, st)
-                        : launch_one_twisted_v<NPL, RPL, false>(p, grid, lds, st);
+static hipError_t launch_one_twisted(const KernelParams& p, int grid, size_t lds, hipStream_t st, const LaunchEvents* ev) {
+  return p.w_pl_off > 0 ? launch_one_twisted_v<NPL, RPL, true>(p, grid, lds, st, ev)
+                        : launch_one_twisted_v<NPL, RPL, false>(p, grid, lds, st, ev);
 }
 
-hipError_t launch_twisted(int cls, const KernelParams& p, int grid, size_t lds, hipStream_t st) {
+hipError_t launch_twisted(int cls, const KernelParams& p, int grid, size_t lds, hipStream_t st, const LaunchEvents* ev) {
   switch (cls) {
-    case 0: return launch_one_twisted<16, 3>(p, grid, lds, st);
-    case 1: return launch_one_twisted<16, 4>(p, grid, lds, st);
-    case 2: return launch_one_twisted<32, 10>(p, grid, lds, st);
-    case 3: return launch_one_twisted<32, 12>(p, grid, lds, st);
-    case 4: return launch_one_twisted<32, 14>(p, grid, lds, st);
-    case 5: return launch_one_twisted<32, 16>(p, grid, lds, st);
+    case 0: return launch_one_twisted<16, 3>(p, grid, lds, st, ev);
+    case 1: return launch_one_twisted<16, 4>(p, grid, lds, st, ev);
+    case 2: return launch_one_twisted<32, 10>(p, grid, lds, st, ev);
+    case 3: return launch_one_twisted<32, 12>(p, grid, lds, st, ev);
+    case 4: return launch_one_twisted<32, 14>(p, grid, lds, st, ev);
+    case 5: return launch_one_twisted<32, 16>(p, grid, lds, st, ev);
     default: return hipErrorInvalidValue;
   }
 }
 
 template <int NPL, int RPL, bool VG>
-static hipError_t launch_one_v(const KernelParams& p, int grid, size_t lds, hipStream_t st) {
+static hipError_t launch_one_v(const KernelParams& p, int grid, size_t lds, hipStream_t st, const LaunchEvents* ev) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&h2_column_wave_kernel<NPL, RPL, VG>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((h2_column_wave_kernel<NPL, RPL, VG>), dim3(grid), dim3(64), lds, st, p);
+  if (ev) hipExtLaunchKernelGGL((h2_column_wave_kernel<NPL, RPL, VG>), dim3(grid), dim3(64), (uint32_t)lds, st, ev->start, ev->stop, 0, p);
+  else hipLaunchKernelGGL((h2_column_wave_kernel<NPL, RPL, VG>), dim3(grid), dim3(64), lds, st, p);
   return hipGetLastError();
 }
 template <int NPL, int RPL>
-static hipError_t launch_one(const KernelParams& p, int grid, size_t lds, hipStream_t st) {
+static hipError_t launch_one(const KernelParams& p, int grid, size_t lds, hipStream_t st, const LaunchEvents* ev) {
   if constexpr (NPL <= 32) {
     if (p.objective == 1) {                  // sum-of-norms build: ñx ≤ 32, vectors in the global workspace
       if (p.vec_in_lds != 0) return hipErrorInvalidValue;
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&h2_column_wave_kernel<NPL, RPL, true, true>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) return e;
-      hipLaunchKernelGGL((h2_column_wave_kernel<NPL, RPL, true, true>), dim3(grid), dim3(64), lds, st, p);
+      if (ev) hipExtLaunchKernelGGL((h2_column_wave_kernel<NPL, RPL, true, true>), dim3(grid), dim3(64), (uint32_t)lds, st, ev->start, ev->stop, 0, p);
+      else hipLaunchKernelGGL((h2_column_wave_kernel<NPL, RPL, true, true>), dim3(grid), dim3(64), lds, st, p);
       return hipGetLastError();
     }
-    if (p.vec_in_lds == 0) return launch_one_v<NPL, RPL, true>(p, grid, lds, st);
+    if (p.vec_in_lds == 0) return launch_one_v<NPL, RPL, true>(p, grid, lds, st, ev);
   }
   if (p.objective == 1) return hipErrorInvalidValue;
-  return launch_one_v<NPL, RPL, false>(p, grid, lds, st);
+  return launch_one_v<NPL, RPL, false>(p, grid, lds, st, ev);
 }
 
 // one kernel per size class (a merged multi-class kernel makes the register allocator spill: 604 B scratch per
 // lane measured); ragged batches run their classes concurrently on separate streams (sls_api.cpp)
-hipError_t launch_wave(int cls, const KernelParams& p, int grid, size_t lds, hipStream_t st) {
+hipError_t launch_wave(int cls, const KernelParams& p, int grid, size_t lds, hipStream_t st, const LaunchEvents* ev) {
   switch (cls) {
-    case 0: return launch_one<16, 3>(p, grid, lds, st);    // n ≤ 12
-    case 1: return launch_one<16, 4>(p, grid, lds, st);    // n ≤ 16
-    case 2: return launch_one<32, 10>(p, grid, lds, st);   // n ≤ 20
-    case 3: return launch_one<32, 12>(p, grid, lds, st);   // n ≤ 24
-    case 4: return launch_one<32, 14>(p, grid, lds, st);   // n ≤ 28
-    case 5: return launch_one<32, 16>(p, grid, lds, st);   // n ≤ 32
-    case 6: return launch_one<64, 40>(p, grid, lds, st);   // n ≤ 40
-    case 7: return launch_one<64, 48>(p, grid, lds, st);   // n ≤ 48
-    case 8: return launch_one<64, 64>(p, grid, lds, st);   // n ≤ 64
+    case 0: return launch_one<16, 3>(p, grid, lds, st, ev);    // n ≤ 12
+    case 1: return launch_one<16, 4>(p, grid, lds, st, ev);    // n ≤ 16
+    case 2: return launch_one<32, 10>(p, grid, lds, st, ev);   // n ≤ 20
+    case 3: return launch_one<32, 12>(p, grid, lds, st, ev);   // n ≤ 24
+    case 4: return launch_one<32, 14>(p, grid, lds, st, ev);   // n ≤ 28
+    case 5: return launch_one<32, 16>(p, grid, lds, st, ev);   // n ≤ 32
+    case 6: return launch_one<64, 40>(p, grid, lds, st, ev);   // n ≤ 40
+    case 7: return launch_one<64, 48>(p, grid, lds, st, ev);   // n ≤ 48
+    case 8: return launch_one<64, 64>(p, grid, lds, st, ev);   // n ≤ 64
     default: return hipErrorInvalidValue;
   }
 }
