@@ -59,12 +59,12 @@ def pick_columns(slc):
     return _pick["cols"]
 
 
-def _composite_masks(slc, A, B2, T=T, alpha=ALPHA):
-    picks = pick_columns(slc)
+def composite_masks(slc, A, B2, picks, T, alpha):
+    """[𝓢x, 𝓢u] of the mask whose columns c − 1, c, c + 1 carry d_c for every (ñx, c, d_c) of picks (shared with wave_cases.py)."""
     by_d = {}
     for _, c, d in picks:
         by_d.setdefault(d, []).extend([c - 1, c, c + 1])
-    owner = np.ones(NX, dtype=np.int64)                          # d of every column; 1 for those that no ladder column reads
+    owner = np.ones(A.shape[0], dtype=np.int64)                  # d of every column; 1 for those that no ladder column reads
     for d, cs in by_d.items():
         owner[cs] = d
     Sx, Su = [0] * T, [0] * T
@@ -83,6 +83,10 @@ def _composite_masks(slc, A, B2, T=T, alpha=ALPHA):
             ms.append(M)
         out.append(ms)
     return out
+
+
+def _composite_masks(slc, A, B2, T=T, alpha=ALPHA):
+    return composite_masks(slc, A, B2, pick_columns(slc), T, alpha)
 
 
 # ------------------------------------------------------------------ problems
@@ -159,9 +163,13 @@ def index_sets(slc, name):
 
 def library_index_sets(slc, name):
     """The same by the library's own host reduction (sls_sparsity_dim_reduction)."""
-    import ctypes as C
     pr = problem(slc, name)
-    P, S = pr["P"], pr["S"]
+    return library_index_sets_of(slc, pr["P"], pr["S"], pr["cols"])
+
+
+def library_index_sets_of(slc, P, S, cols):
+    """[(s_x, s_u)] of the given columns of (P, S) by sls_sparsity_dim_reduction (shared with wave_cases.py)."""
+    import ctypes as C
     lib, cap = slc.load_library(), slc._capi
     i64p = C.POINTER(C.c_int64)
     keep = []
@@ -176,7 +184,7 @@ def library_index_sets(slc, name):
     sxm = csc(S[0][-1], cap.sls_csc_bool, np.uint8); sum_ = csc(S[1][-1], cap.sls_csc_bool, np.uint8)
     dims = cap.sls_dims(P.Nx, P.Nu, P.Nz, P.Nw, 1, 0, 0)
     out = []
-    for c in pr["cols"]:
+    for c in cols:
         cj = np.asarray([c], dtype=np.int64)
         sx = np.zeros(P.Nx, dtype=np.int64); su = np.zeros(max(P.Nu, 1), dtype=np.int64)
         nsx, nsu = C.c_int64(), C.c_int64()
