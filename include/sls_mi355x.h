@@ -77,6 +77,13 @@ extern "C" {
                                     included; without the flag a plan is built exactly as before.  The one-shot and batch calls
                                     (sls_h2_sf_solve, _solve_batch, _solve_localized) ACCEPT the flag and apply the same shape
                                     rule and the same records — they keep no plan, so there is nothing to update afterwards. */
+#define SLS_PLAN_MULTIPLIERS 4u /* sls_h2_sf_plan / sls_h2_sf_plan_localized: every execute also keeps the multiplier of the
+                                    achievability constraints of every column, which sls_plan_gradient (below) turns into the
+                                    derivative of the 𝓗₂ cost in the stored entries of A and B2.  Every column then runs on the
+                                    one-wave kernel (no two-wave, no four-wave launch).  SLS_EUNSUPPORTED, with the reason, for a plan
+                                    with a column beyond the 32-lane one-wave classes (ñx > 32), a dense cost Hessian, a coupled
+                                    group or SLS_SOLVE_SUM_OF_NORMS, and from the one-shot calls (they keep no plan).  Without the
+                                    flag a plan is built, routed and sized exactly as before. */
 
 /* Julia SparseMatrixCSC{Float64,Int}  (reference src/types/GeneralizedPlant.jl:47-52) */
 typedef struct sls_csc_f64 {
@@ -419,6 +426,36 @@ int  sls_plan_residual(sls_plan* plan, void* hip_stream, const double* d_values,
                        double* d_res_inf, double* d_halo_inf, double* d_res_l1, double* d_totals);
 int  sls_plan_fetch_residual(sls_plan* plan, const double* d_values, int packed,
                              double* res_inf, double* halo_inf, double* res_l1, double* totals);
+/* ---- gradient of the 𝓗₂ cost in the stored entries of A and B2 (plans built with SLS_PLAN_MULTIPLIERS) ---------
+ * J = Σ_j c_j·J_j with J_j the number sls_plan_objective reports for subproblem j and c_j a caller-supplied column weight
+ * (default 1).  With μ_j the multiplier of subproblem j's achievability constraints (E_jᵀμ_j = ∇_z J_j on its free variables;
+ * block row 0 is x₀ = e, block row k is x_k − Ãx_{k−1} − B̃u_{k−1}; the kernel's iteration from λ = 0 gives the minimum-norm one
+ * where E_j is rank deficient) the envelope theorem gives, for stored entries, in the CSC order of sls_plan_update_plant:
+ *     ∂J/∂A[a,b]  = Σ_j c_j·[a ∈ s_x(j), b ∈ s_x(j)]·Σ_{k=1..T} μ_{j,k}[a]·x_{j,k−1}[b]
+ *     ∂J/∂B2[a,m] = Σ_j c_j·[a ∈ s_x(j), m ∈ s_u(j)]·Σ_{k=1..T} μ_{j,k}[a]·u_{j,k−1}[m]
+ * and, for a plan that also has SLS_PLAN_WEIGHTS_UPDATABLE, in the diagonals the plan holds now (sls_plan_fetch_weights):
+ *     ∂J/∂c1[i] = 2·c1[i]·Σ_j c_j·b_j²·Σ_t x_{j,t}[i]²,   ∂J/∂d12[m] = 2·d12[m]·Σ_j c_j·b_j²·Σ_t u_{j,t}[m]²      (b_j = B1[c_j,c_j]).
+ * x, u are read from d_values through the mask and the destination table (a fixed variable reads 0.0), μ from the buffer the
+ * LAST execute wrote: d_values must be what that execute (full or partial) produced.  A subproblem whose status is neither
+ * SLS_COL_OK nor SLS_COL_TRIVIAL contributes 0 (sls_plan_fetch_gradient counts them); so does a column with B1[c,c] = 0, whose cost
+ * is constant.  Every sum runs in a fixed order (k ascending, then subproblems ascending; no floating-point atomics): the result
+ * is bit-identical from call to call, between the two layouts, and whether the multipliers came from a full or a partial execute.
+ * sls_plan_gradient: enqueue on hip_stream behind the execute that wrote d_values and the plan's last update (the stream waits
+ *   for both); DEVICE outputs d_gA[nnz(A)], d_gB2[nnz(B2)], d_gc1[Nx], d_gd12[Nu], each may be NULL; d_col_weight: DEVICE
+ *   n_subproblems values or NULL.  Asynchronous like sls_plan_objective, EXCEPT on first use per plan: the entry tables are built
+ *   on the host from the index sets (read back from the device) and uploaded; their buffers and the multiplier buffer
+ *   ((T+1)·32 doubles per subproblem) are the feature's own and not part of workspace_bytes.
+ *   SLS_EINVAL without the flag, before the plan's first execute, and for d_gc1 / d_gd12 without SLS_PLAN_WEIGHTS_UPDATABLE.
+ * sls_plan_fetch_gradient: the same on the plan's stream with HOST arrays (col_weight included; each nullable), waits;
+ *   *n_skipped (nullable) = subproblems that contributed 0 because of their status.
+ * sls_plan_fetch_multipliers: μ of subproblem `sub` (col_status order) as the last execute left it, to the HOST array
+ *   mu[(T+1)·ñx], block-row major, rows in s_x order; len must be (T+1)·ñx.  mu = NULL with len = 0 is the size query: the
+ *   call returns (T+1)·ñx (positive; every error code is negative) and copies nothing.                                        */
+int  sls_plan_gradient(sls_plan* plan, void* hip_stream, const double* d_values, int packed, const double* d_col_weight,
+                       double* d_gA, double* d_gB2, double* d_gc1, double* d_gd12);
+int  sls_plan_fetch_gradient(sls_plan* plan, const double* d_values, int packed, const double* col_weight,
+                             double* gA, double* gB2, double* gc1, double* gd12, int64_t* n_skipped);
+int  sls_plan_fetch_multipliers(sls_plan* plan, int64_t sub, double* mu, int64_t len);
 /* One-shot calls: opt in per context (default off: the one-shot calls do exactly what they do today).  With the option on,
  * sls_h2_sf_solve, sls_h2_sf_solve_batch (composite order: plant 0's columns, then plant 1's, …) and
  * sls_h2_sf_solve_localized evaluate on each device after the last launch (refinement included) and before the download.

@@ -247,6 +247,22 @@ int sls_debug_margin_entry_signed(const sls_dims* dims, const sls_plant* P, cons
                                   const double* values, int64_t nscen, const double* A_nzval, const double* B2_nzval, int per_scenario,
                                   int64_t* n_entries, int64_t* n_mismatch, int64_t* n_negative);
 
+/* The entry tables of sls_plan_gradient and its host twin (csrc/sls_gradient.cpp) for the plan sls_h2_sf_plan would build from
+ * these inputs.  Call with every output NULL but n_slots to size the arrays.  Tables, each nullable: *n_slots = listed entries
+ * over all subproblems; ent_ptr [n_subproblems + 1]; ent [3·n_slots] = (position, local row, local column) per listed entry —
+ * position: CSC position in A's nzval, or nnz(A) + that in B2's; inv_ptr [nnz(A) + nnz(B2) + 1]; inv_slot / inv_sub [n_slots]:
+ * per stored entry its slots and their subproblems, ascending.  Twin, when mu is given: mu holds (T+1)·ñx doubles per
+ * subproblem, concatenated in col_status order, block-row major (what sls_plan_fetch_multipliers returns); phix_vals /
+ * phiu_vals as sls_plan_download gives them; col_status / col_weight nullable.  Accumulates in long double in the device's
+ * order: gA / gB2, per entry abs_A / abs_B2 = Σ|terms| and terms_A / terms_B2 = the number N of products — a double evaluation
+ * in any order lies within N·2⁻⁵³·Σ|terms| (first order) of the exact sum.  Needs no device. */
+int sls_debug_gradient_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                            int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, int64_t* n_slots,
+                            int64_t* ent_ptr, int32_t* ent, int64_t* inv_ptr, int64_t* inv_slot, int32_t* inv_sub,
+                            const double* mu, const double* const* phix_vals, const double* const* phiu_vals,
+                            const int32_t* col_status, const double* col_weight, double* gA, double* gB2, double* abs_A,
+                            double* abs_B2, int64_t* terms_A, int64_t* terms_B2);
+
 #ifdef __cplusplus
 }
 #endif

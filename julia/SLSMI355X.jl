@@ -11,7 +11,7 @@
 module SLSMI355X
 
 using SparseArrays
-export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, update_weights!, weights, SLS_PLAN_WEIGHTS_UPDATABLE, track_changes!, execute_dirty!, residual, Controller, load!, reset!, step!, Rollout, set_plant!, set_weights!, run!, stats, Margin, margins, set_radius!, box_margins, worst_plant, Norms, l1, hinf, h2, covariance_pattern!, covariance
+export SLS_𝓗₂_mi355x, SLS_𝓗₂_mi355x_localized, sls_context, sls_close, default_ctx, sls_ridge!, objective_values, last_objective, update_plant!, update_weights!, weights, SLS_PLAN_WEIGHTS_UPDATABLE, track_changes!, execute_dirty!, residual, gradient, multipliers, SLS_PLAN_MULTIPLIERS, Controller, load!, reset!, step!, Rollout, set_plant!, set_weights!, run!, stats, Margin, margins, set_radius!, box_margins, worst_plant, Norms, l1, hinf, h2, covariance_pattern!, covariance
 
 const LIB = get(ENV, "SLS_MI355X_LIB", "libsls_mi355x.so")
 
@@ -181,6 +181,47 @@ function residual(plan::Ptr{Cvoid}, d_values::Ptr{Cvoid}, nsub::Integer; packed:
                plan, d_values, packed ? 1 : 0, res_inf, halo_inf, res_l1, totals)
     rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
     return (res_inf=res_inf, halo_inf=halo_inf, res_l1=res_l1, max_inf=totals[1], e1_norm=totals[2])
+end
+
+const SLS_PLAN_MULTIPLIERS = UInt32(4)      # sls_dims.flags: the plan keeps the multipliers every execute ends with
+
+"""
+    g = gradient(plan, d_values, nnzA, nnzB2; packed=false, column_weights=nothing, Nx=0, Nu=0)
+
+`sls_plan_fetch_gradient` on a resident plan built with `SLS_PLAN_MULTIPLIERS` in `dims.flags`: the derivative of `Σ_j c_j J_j`
+(`J_j` as `objective_values` reports it, `c_j = column_weights`, default 1) in every stored entry of `A` and `B₂`, in the `nzval`
+order `update_plant!` takes, from the multipliers the last execute left and the values it wrote to `d_values`.  With `Nx`, `Nu`
+given (plans that also have `SLS_PLAN_WEIGHTS_UPDATABLE`) also the derivatives in the diagonals of `C₁` and `D₁₂`.  Returns a
+named tuple `gA`, `gB2`, `gc1`, `gd12` (the last two empty unless asked for) and `n_skipped`, the subproblems that contributed 0
+because they are neither solved nor trivial.  Waits for the plan's last execute and last update.
+"""
+function gradient(plan::Ptr{Cvoid}, d_values::Ptr{Cvoid}, nnzA::Integer, nnzB2::Integer; packed::Bool=false,
+                  column_weights::Union{Nothing,Vector{Float64}}=nothing, Nx::Integer=0, Nu::Integer=0)
+    gA = zeros(Float64, max(nnzA, 1));  gB2 = zeros(Float64, max(nnzB2, 1))
+    gc1 = zeros(Float64, max(Nx, 1));  gd12 = zeros(Float64, max(Nu, 1))
+    nskip = Ref{Int64}(0)
+    cw = column_weights === nothing ? Ptr{Float64}(C_NULL) : pointer(column_weights)
+    rc = GC.@preserve column_weights ccall((:sls_plan_fetch_gradient, LIB), Cint,
+               (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}),
+               plan, d_values, packed ? 1 : 0, cw, gA, gB2, Nx > 0 ? pointer(gc1) : Ptr{Float64}(C_NULL),
+               Nu > 0 ? pointer(gd12) : Ptr{Float64}(C_NULL), nskip)
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    return (gA=gA[1:nnzA], gB2=gB2[1:nnzB2], gc1=gc1[1:Nx], gd12=gd12[1:Nu], n_skipped=nskip[])
+end
+
+"""
+    μ = multipliers(plan, sub, T)
+
+`sls_plan_fetch_multipliers`: the multiplier of subproblem `sub` (0-based, `col_status` order) as the last execute left it, a
+`ñx × (T+1)` matrix — column `k+1` is block row `k` of the achievability constraints, rows in `sₓ` order.
+"""
+function multipliers(plan::Ptr{Cvoid}, sub::Integer, T::Integer)
+    len = ccall((:sls_plan_fetch_multipliers, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64), plan, sub, C_NULL, 0)
+    len < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    mu = zeros(Float64, max(len, 1))
+    rc = ccall((:sls_plan_fetch_multipliers, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64), plan, sub, mu, len)
+    rc < 0 && error(unsafe_string(ccall((:sls_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+    return reshape(mu[1:len], div(len, T + 1), T + 1)
 end
 
 """

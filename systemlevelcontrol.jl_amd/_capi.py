@@ -24,6 +24,7 @@ SLS_ABI_VERSION = 2
 SLS_EINVAL, SLS_ENOTSF, SLS_EUNSUPPORTED, SLS_EHIP, SLS_ENOMEM, SLS_ENODEVICE = -1, -2, -3, -4, -5, -6
 SLS_SOLVE_DEFAULT, SLS_SOLVE_SUM_OF_NORMS = 0, 1
 SLS_PLAN_WEIGHTS_UPDATABLE = 2
+SLS_PLAN_MULTIPLIERS = 4
 SLS_COL_OK, SLS_COL_INFEASIBLE, SLS_COL_NOTCONV, SLS_COL_TRIVIAL, SLS_COL_SKIPPED, SLS_COL_UNSUPPORTED = 0, 1, 2, 3, 4, 5
 
 ERROR_NAMES = {SLS_EINVAL: "SLS_EINVAL", SLS_ENOTSF: "SLS_ENOTSF", SLS_EUNSUPPORTED: "SLS_EUNSUPPORTED",
@@ -92,6 +93,7 @@ EXPORTS = [
     "sls_plan_update_weights", "sls_plan_update_weights_result", "sls_plan_fetch_weights",
     "sls_plan_execute_columns", "sls_plan_track_changes", "sls_plan_execute_dirty", "sls_plan_fetch_dirty", "sls_plan_clear_dirty",
     "sls_plan_residual", "sls_plan_fetch_residual",
+    "sls_plan_gradient", "sls_plan_fetch_gradient", "sls_plan_fetch_multipliers",
     "sls_controller_plan", "sls_controller_load", "sls_controller_reset", "sls_controller_step", "sls_controller_info",
     "sls_controller_destroy",
     "sls_rollout_plan", "sls_rollout_load", "sls_rollout_set_plant", "sls_rollout_set_weights", "sls_rollout_reset", "sls_rollout_run",
@@ -280,6 +282,11 @@ def load_library(path: str | None = None):
                                            dp, dp, dp, dp, dp, dp]
     lib.sls_debug_residual_host.restype = C.c_int
     lib.sls_debug_residual_host.argtypes = common + [dpp, dpp, dp, dp, dp, dp, i64p, dp, i64p, dp, i64p, i32p, C.c_int64]
+    lib.sls_plan_gradient.restype = C.c_int; lib.sls_plan_gradient.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    lib.sls_plan_fetch_gradient.restype = C.c_int; lib.sls_plan_fetch_gradient.argtypes = [vp, vp, C.c_int, dp, dp, dp, dp, dp, i64p]
+    lib.sls_plan_fetch_multipliers.restype = C.c_int; lib.sls_plan_fetch_multipliers.argtypes = [vp, C.c_int64, dp, C.c_int64]
+    lib.sls_debug_gradient_host.restype = C.c_int
+    lib.sls_debug_gradient_host.argtypes = common + [i64p, i64p, i32p, i64p, i64p, i32p, dp, dpp, dpp, i32p, dp, dp, dp, dp, dp, i64p, i64p]
     lib.sls_debug_objective_host.restype = C.c_int
     lib.sls_debug_objective_host.argtypes = common + [dp, dp, dpp, dpp, dp, dp, i64p, dp]
     lib.sls_debug_operator_update_host.restype = C.c_int

@@ -353,6 +353,7 @@ extern "C++" bool sls::one_kernel_run(const sls_plan* plan, hipStream_t st, cons
 
 extern "C++" int sls::enqueue_launches(sls_plan* plan, const KernelParams& kp, hipStream_t st, const SelectedRun* sel, const LaunchEvents* ev) {
   const bool multi = plan->launches.size() > 1;
+  if (plan->grad.d_mu) plan->grad.executed = true;      // every run of a flagged plan rewrites the multiplier slots it solves
   if (plan->has_tile) HIPCHK(plan->ctx, hipMemsetAsync(plan->d_counters, 0, plan->launches.size() * sizeof(int32_t), st));
   if (multi) HIPCHK(plan->ctx, hipEventRecord(plan->ev_fork, st));
   for (size_t li = 0; li < plan->launches.size(); ++li) {
@@ -686,6 +687,135 @@ int sls_plan_fetch_residual(sls_plan* plan, const double* d_values, int packed, 
   if (halo_inf) std::memcpy(halo_inf, stage + n, n * sizeof(double));
   if (res_l1) std::memcpy(res_l1, stage + 2 * n, n * sizeof(double));
   if (totals) std::memcpy(totals, stage + 3 * n, 2 * sizeof(double));
+  return 0;
+}
+
+// ---- gradient of the 𝓗₂ cost in A, B2 and the LQR diagonals: sls_plan_gradient, sls_plan_fetch_gradient ----
+
+// The tables and buffers of the gradient pass, made by the first call that needs them: like the residual's halo lists they
+// follow from the index sets, which are read back from the device once — a host wait, first use only.
+static int gradient_ensure(sls_plan* plan) {
+  sls_plan::Gradient& gr = plan->grad;
+  if (gr.ready) return 0;
+  const Symbolic& S = plan->sym;
+  const size_t ns = (size_t)plan->kp.nsub;
+  if (S.subs.size() != ns || S.b_zero.size() != ns) return fail(plan->ctx, SLS_EUNSUPPORTED, "sls_plan_gradient: this plan keeps no column list");
+  int64_t nidx = 0;
+  for (const SubDesc& sd : S.subs) nidx = std::max<int64_t>(nidx, std::max(sd.off_sx + sd.n, sd.off_su + sd.m));
+  std::vector<int32_t> idx((size_t)std::max<int64_t>(nidx, 1), 0);
+  if (nidx > 0) HIPCHK(plan->ctx, hipMemcpy(idx.data(), plan->kp.idx_pool, (size_t)nidx * sizeof(int32_t), hipMemcpyDeviceToHost));
+  GradientTables G;
+  build_gradient_tables(S.At_csr, S.Bt_csr, S.subs.data(), (int64_t)ns, idx.data(), G);
+  if (G.nnzA + G.nnzB > INT32_MAX) return fail(plan->ctx, SLS_EUNSUPPORTED, "sls_plan_gradient: more than 2³¹ − 1 stored entries");
+  int64_t need = 0;
+  for (const SubDesc& sd : S.subs) need = std::max<int64_t>(need, (int64_t)(S.T + 1) * sd.n + (int64_t)S.T * (sd.n + sd.m));
+  gr.lds_doubles = (int)std::min<int64_t>(need, 8000);                    // λ and z of a column in LDS when they fit 64 000 B
+  gr.nnzA = G.nnzA; gr.nnzB = G.nnzB;
+  const bool wu = S.wu.updatable;
+  Arena ar;
+  ar.table(S.b_zero, &gr.b_zero);
+  ar.table(G.ent_ptr, &gr.ent_ptr); ar.table(G.ent, &gr.ent); ar.table(G.inv_ptr, &gr.inv_ptr); ar.table(G.inv_slot, &gr.inv_slot);
+  if (wu) { ar.table(G.w_base, &gr.w_base); ar.table(G.winv_ptr, &gr.winv_ptr); ar.table(G.winv_slot, &gr.winv_slot); }
+  ar.buffer((size_t)std::max<int64_t>(G.ent_ptr[ns], 1), &gr.contrib);
+  if (wu) ar.buffer((size_t)std::max<int64_t>(G.w_base[ns], 1), &gr.wcontrib);
+  ar.buffer(ns, &gr.col_weight);
+  ar.buffer((size_t)(G.nnzA + G.nnzB + S.Nx + S.Nu + 1), &gr.out);
+  void* base = nullptr;
+  if (int rc = ar.commit(plan->ctx, &base, "hipMalloc (gradient tables)", "hipMemcpy H2D (gradient tables)")) return rc;
+  plan->dev_allocs.push_back(base);
+  gr.ready = true;
+  return 0;
+}
+
+int sls_plan_gradient(sls_plan* plan, void* hip_stream, const double* d_values, int packed, const double* d_col_weight,
+                      double* d_gA, double* d_gB2, double* d_gc1, double* d_gd12) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  if (!plan->grad.d_mu) return fail(plan->ctx, SLS_EINVAL, "sls_plan_gradient: the plan was built without SLS_PLAN_MULTIPLIERS");
+  if (!plan->grad.executed) return fail(plan->ctx, SLS_EINVAL, "sls_plan_gradient: no execute has run on this plan yet");
+  if ((d_gc1 || d_gd12) && !plan->sym.wu.updatable)
+    return fail(plan->ctx, SLS_EINVAL, "sls_plan_gradient: the weight derivatives need a plan built with SLS_PLAN_WEIGHTS_UPDATABLE");
+  if (!d_values && plan->info.n_packed > 0) return fail(plan->ctx, SLS_EINVAL, "null device value pointer");
+  if (packed && !plan->d_pdest) return fail(plan->ctx, SLS_EINVAL, "this plan was built without the packed layout");
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  if (plan->kp.nsub == 0) return 0;
+  if (int rc = gradient_ensure(plan)) return rc;
+  // behind the execute that wrote d_values and the multipliers, and behind the plan's last update (the diagonals, the records)
+  if (plan->last_done) HIPCHK(plan->ctx, hipStreamWaitEvent(st, plan->last_done, 0));
+  if (plan->upd_recorded || plan->w_upd_recorded) HIPCHK(plan->ctx, hipStreamWaitEvent(st, plan->ev_upd, 0));
+  const KernelParams& kp = plan->kp;
+  const sls_plan::Gradient& gr = plan->grad;
+  GradientParams gp{};
+  gp.subs = kp.subs; gp.nsub = kp.nsub; gp.T = kp.T;
+  gp.mask_pool = kp.mask_pool; gp.dest = packed ? plan->d_pdest : plan->d_dest; gp.values = d_values;
+  gp.mu = gr.d_mu; gp.obj_pool = plan->d_obj; gp.b_zero = gr.b_zero; gp.status = kp.status; gp.col_weight = d_col_weight;
+  gp.ent_ptr = gr.ent_ptr; gp.ent = gr.ent; gp.inv_ptr = gr.inv_ptr; gp.inv_slot = gr.inv_slot; gp.contrib = gr.contrib;
+  gp.nnzA = gr.nnzA; gp.nnzB = gr.nnzB; gp.gA = d_gA; gp.gB2 = d_gB2;
+  if (d_gc1 || d_gd12) {
+    gp.b2 = plan->d_w_b2; gp.diag = plan->d_w_diag; gp.w_base = gr.w_base; gp.winv_ptr = gr.winv_ptr; gp.winv_slot = gr.winv_slot;
+    gp.wcontrib = gr.wcontrib; gp.Nx = plan->sym.Nx; gp.Nu = plan->sym.Nu; gp.gc1 = d_gc1; gp.gd12 = d_gd12;
+  }
+  hipError_t e = launch_gradient(gp, gr.lds_doubles, st);
+  if (e != hipSuccess) return hipfail(plan->ctx, e, "launch gradient kernels");
+  return 0;
+}
+
+int sls_plan_fetch_gradient(sls_plan* plan, const double* d_values, int packed, const double* col_weight,
+                            double* gA, double* gB2, double* gc1, double* gd12, int64_t* n_skipped) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  if (!plan->grad.d_mu) return fail(plan->ctx, SLS_EINVAL, "sls_plan_gradient: the plan was built without SLS_PLAN_MULTIPLIERS");
+  if (!plan->grad.executed) return fail(plan->ctx, SLS_EINVAL, "sls_plan_gradient: no execute has run on this plan yet");
+  if ((gc1 || gd12) && !plan->sym.wu.updatable)
+    return fail(plan->ctx, SLS_EINVAL, "sls_plan_gradient: the weight derivatives need a plan built with SLS_PLAN_WEIGHTS_UPDATABLE");
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  if (n_skipped) *n_skipped = 0;
+  const size_t n = (size_t)plan->kp.nsub;
+  if (n == 0) return 0;
+  if (int rc = gradient_ensure(plan)) return rc;
+  hipStream_t st = plan->stream;
+  sls_plan::Gradient& gr = plan->grad;
+  if (col_weight) {
+    if (int rc = stage_to_device(plan->ctx, plan->slot, st, gr.col_weight, col_weight, n, nullptr, 0)) return rc;
+  }
+  const size_t nA = (size_t)gr.nnzA, nB = (size_t)gr.nnzB, Nx = (size_t)plan->sym.Nx, Nu = (size_t)plan->sym.Nu;
+  double* o = gr.out;
+  if (int rc = sls_plan_gradient(plan, st, d_values, packed, col_weight ? gr.col_weight : nullptr, gA ? o : nullptr, gB2 ? o + nA : nullptr,
+                                 gc1 ? o + nA + nB : nullptr, gd12 ? o + nA + nB + Nx : nullptr)) return rc;
+  std::vector<double> host(nA + nB + Nx + Nu + 1);
+  if (int rc = fetch_to_host(plan->ctx, plan->slot, st, host.data(), o, host.size() * sizeof(double))) return rc;
+  if (gA) std::memcpy(gA, host.data(), nA * sizeof(double));
+  if (gB2) std::memcpy(gB2, host.data() + nA, nB * sizeof(double));
+  if (gc1) std::memcpy(gc1, host.data() + nA + nB, Nx * sizeof(double));
+  if (gd12) std::memcpy(gd12, host.data() + nA + nB + Nx, Nu * sizeof(double));
+  if (n_skipped) {
+    std::vector<int32_t> stt(n);
+    if (int rc = fetch_status_raw(plan, stt.data(), nullptr, nullptr)) return rc;
+    for (int32_t s : stt) *n_skipped += (s != SLS_COL_OK && s != SLS_COL_TRIVIAL);
+  }
+  return 0;
+}
+
+int sls_plan_fetch_multipliers(sls_plan* plan, int64_t sub, double* mu, int64_t len) {
+  if (!plan) return fail(nullptr, SLS_EINVAL, "null plan");
+  if (!plan->grad.d_mu) return fail(plan->ctx, SLS_EINVAL, "sls_plan_fetch_multipliers: the plan was built without SLS_PLAN_MULTIPLIERS");
+  if (!plan->grad.executed) return fail(plan->ctx, SLS_EINVAL, "sls_plan_fetch_multipliers: no execute has run on this plan yet");
+  if (sub < 0 || sub >= plan->kp.nsub || (size_t)sub >= plan->sym.subs.size()) return fail(plan->ctx, SLS_EINVAL, "sls_plan_fetch_multipliers: sub out of range");
+  const SubDesc& sd = plan->sym.subs[(size_t)sub];
+  const int64_t T = plan->kp.T, n = sd.n;
+  if (!mu && len == 0) return (int)((T + 1) * n);                       // the size query
+  if (!mu || len != (T + 1) * n) return fail(plan->ctx, SLS_EINVAL, "sls_plan_fetch_multipliers: mu must hold (T+1)·ñx doubles");
+  HIPCHK(plan->ctx, hipSetDevice(plan->dev));
+  if (int rc = wait_plan_done(plan)) return rc;
+  hipStream_t st = plan->stream;
+  if (plan->w_upd_recorded) HIPCHK(plan->ctx, hipStreamWaitEvent(st, plan->ev_upd, 0));
+  const size_t slot = (size_t)mu_slot_doubles((int)T);
+  std::vector<double> lam(slot);
+  double scale[2] = {1.0, 0.0};
+  if (int rc = fetch_to_host(plan->ctx, plan->slot, st, lam.data(), plan->grad.d_mu + (size_t)sub * slot, slot * sizeof(double))) return rc;
+  if (int rc = fetch_to_host(plan->ctx, plan->slot, st, scale, plan->d_obj + 2 * (size_t)sub, sizeof scale)) return rc;
+  const double f = column_factor(sd.has_w, scale[0]);
+  for (int64_t k = 0; k <= T; ++k)
+    for (int64_t a = 0; a < n; ++a) mu[k * n + a] = f * lam[(size_t)(k * kMuLd + a)];
   return 0;
 }
 

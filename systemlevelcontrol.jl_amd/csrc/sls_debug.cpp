@@ -12,6 +12,7 @@
 
 #include "../../include/sls_mi355x.h"
 #include "../../include/sls_mi355x_debug.h"
+#include "sls_gradient.h"
 #include "sls_margin.h"
 #include "sls_margin_box.h"
 #include "sls_norms.h"
@@ -513,6 +514,46 @@ int sls_debug_margin_entry_signed(const sls_dims* dims, const sls_plant* P, cons
   int rc = build_margin_tables(dims, P, Sx, Su, Tb, msg);
   if (!rc) rc = margin_entry_signed_check(Tb, values, nscen, A_nzval, B2_nzval, per_scenario != 0, n_entries, n_mismatch, n_negative, msg);
   if (rc) return fail(nullptr, rc, "sls_debug_margin_entry_signed: " + msg);
+  return 0;
+}
+
+/* diagnostics (include/sls_mi355x_debug.h): the entry tables of sls_plan_gradient and the host twin of its two kernels
+   (csrc/sls_gradient.cpp).  Needs no device. */
+int sls_debug_gradient_host(const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx, const sls_csc_bool* Su,
+                            int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols, int64_t* n_slots,
+                            int64_t* ent_ptr, int32_t* ent, int64_t* inv_ptr, int64_t* inv_slot, int32_t* inv_sub,
+                            const double* mu, const double* const* phix_vals, const double* const* phiu_vals,
+                            const int32_t* col_status, const double* col_weight, double* gA, double* gB2, double* abs_A,
+                            double* abs_B2, int64_t* terms_A, int64_t* terms_B2) {
+  Inputs in{dims, P, Sx, Su, ngroups, group_ptr, group_cols};
+  std::string msg;
+  int rc = validate_inputs(in, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  Symbolic S;
+  S.want_packed = false; S.compact = false;
+  std::vector<int64_t> gptr, gcols;
+  normalise_groups(in, gptr, gcols);
+  rc = build_symbolic(in, 0, (int64_t)gptr.size() - 1, S, msg);
+  if (rc) return fail(nullptr, rc, msg);
+  GradientTables G;
+  build_gradient_tables(S.At_csr, S.Bt_csr, S.subs.data(), (int64_t)S.subs.size(), S.idx_pool.data(), G);
+  if (n_slots) *n_slots = G.ent_ptr.back();
+  if (ent_ptr) std::copy(G.ent_ptr.begin(), G.ent_ptr.end(), ent_ptr);
+  if (ent) std::copy(G.ent.begin(), G.ent.end(), ent);
+  if (inv_ptr) std::copy(G.inv_ptr.begin(), G.inv_ptr.end(), inv_ptr);
+  if (inv_slot) std::copy(G.inv_slot.begin(), G.inv_slot.end(), inv_slot);
+  if (inv_sub) std::copy(G.inv_sub.begin(), G.inv_sub.end(), inv_sub);
+  if (!mu) return 0;
+  if (!phix_vals || !phiu_vals) return fail(nullptr, SLS_EINVAL, "null value arrays");
+  std::vector<double> vals((size_t)std::max<int64_t>(S.n_values, 1), 0.0);
+  for (int64_t t = 0; t < S.T; ++t) {
+    const int64_t nx = S.off_x[t + 1] - S.off_x[t], nu = S.off_u[t + 1] - S.off_u[t];
+    if ((nx > 0 && !phix_vals[t]) || (nu > 0 && !phiu_vals[t])) return fail(nullptr, SLS_EINVAL, "null phix_vals[t]/phiu_vals[t]");
+    if (nx > 0) std::copy(phix_vals[t], phix_vals[t] + nx, vals.begin() + S.off_x[t]);
+    if (nu > 0) std::copy(phiu_vals[t], phiu_vals[t] + nu, vals.begin() + S.off_u[t]);
+  }
+  rc = gradient_host(S, G, mu, vals.data(), col_status, col_weight, S.b_zero.data(), gA, gB2, abs_A, abs_B2, terms_A, terms_B2, msg);
+  if (rc) return fail(nullptr, rc, "sls_debug_gradient_host: " + msg);
   return 0;
 }
 

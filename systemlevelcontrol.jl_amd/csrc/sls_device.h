@@ -91,7 +91,12 @@ struct KernelParams {
   // the setup images of THIS launch's columns (twisted4_image_doubles below), indexed like the records; NULL together with t4_static
   double* t4_images;
   int64_t t4_images_stride;   // doubles per column
+  // multiplier export (plans built with SLS_PLAN_MULTIPLIERS, one-wave kernel only): λ of subproblem q goes to
+  // mu[q·mu_stride + k·kMuLd + a] after the pass whose z(λ) is written out (sls_gradient.h); NULL = no export
+  double* mu;
+  int64_t mu_stride;
 };
+constexpr int kMuLd = 32;             // leading dimension of a multiplier slot (the widest class that exports: NPL = 32)
 
 // LDS bytes the general kernel needs for given caps (must match the carve in the kernel).
 // one of the two ñx×ñx block images; outside the factorisation the pair doubles as the staging area of the residual pass

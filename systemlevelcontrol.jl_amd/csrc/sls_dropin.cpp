@@ -142,6 +142,7 @@ int sls_h2_sf_solve(sls_ctx* ctx, const sls_dims* dims, const sls_plant* P, cons
                     double* const* phix_vals, double* const* phiu_vals, int32_t* col_status, sls_stats* stats) {
   if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
   if (!phix_vals || !phiu_vals) return fail(ctx, SLS_EINVAL, "null output arrays");
+  if (dims && (dims->flags & SLS_PLAN_MULTIPLIERS)) return fail(ctx, SLS_EUNSUPPORTED, "SLS_PLAN_MULTIPLIERS: a one-shot call keeps no plan; build one with sls_h2_sf_plan");
   // anything else that is missing or malformed is left to the regular path to report
   if (dims && ngroups > 0 && group_ptr && group_cols && Sx && Su && dims->Nx > 0 && dims->T > 0) {
     std::vector<int32_t> layer_of;
@@ -201,6 +202,7 @@ int sls_h2_sf_solve_localized(sls_ctx* ctx, const sls_dims* dims, const sls_plan
                               double* const* phix_vals, double* const* phiu_vals, int32_t* col_status, sls_stats* stats) {
   if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
   if (!phix_vals || !phiu_vals) return fail(ctx, SLS_EINVAL, "null output arrays");
+  if (dims && (dims->flags & SLS_PLAN_MULTIPLIERS)) return fail(ctx, SLS_EUNSUPPORTED, "SLS_PLAN_MULTIPLIERS: a one-shot call keeps no plan; build one with sls_h2_sf_plan_localized");
   std::vector<sls_plan*> plans(1, nullptr);
   std::vector<double*> dvals(1, nullptr);
   int rc = sls_h2_sf_plan_localized(ctx, 0, dims, P, d, alpha, &plans[0]);
@@ -222,6 +224,8 @@ int sls_h2_sf_solve_batch(sls_ctx* ctx, int nplants, const sls_dims* dims, const
                           int32_t* const* col_status, sls_stats* stats) {
   if (!ctx) return fail(nullptr, SLS_EINVAL, "null context");
   if (nplants <= 0 || !dims || !P || !Sx || !Su || !phix_vals || !phiu_vals) return fail(ctx, SLS_EINVAL, "null argument");
+  for (int i = 0; i < nplants; ++i)
+    if (dims[i].flags & SLS_PLAN_MULTIPLIERS) return fail(ctx, SLS_EUNSUPPORTED, "SLS_PLAN_MULTIPLIERS: a one-shot call keeps no plan; build one with sls_h2_sf_plan");
   if (nplants == 1) return sls_h2_sf_solve(ctx, &dims[0], &P[0], Sx[0], Su[0], 0, nullptr, nullptr, phix_vals[0], phiu_vals[0],
                                            col_status ? col_status[0] : nullptr, stats);
   BatchComposite C;

@@ -10,6 +10,7 @@
 #include "sls_device.h"
 #include "sls_launch.h"
 #include "sls_objective.h"
+#include "sls_gradient.h"
 #include "sls_residual.h"
 
 struct sls_ctx {
@@ -81,6 +82,7 @@ hipError_t launch_level_prefix(const int32_t* cntx, const int32_t* cntu, int Nx,
                                int64_t* totu, hipStream_t stream);
 hipError_t launch_objective(const ObjectiveParams& p, int lds_doubles, double* d_total, hipStream_t stream);
 hipError_t launch_residual(const ResidualParams& p, double* d_totals, hipStream_t stream);
+hipError_t launch_gradient(const GradientParams& p, int lds_doubles, hipStream_t stream);
 hipError_t launch_tile_invert(const double* d_A, int n, double* d_ws, double* d_out, bool mlds, hipStream_t stream);
 hipError_t launch_operator_update(const OperatorUpdateParams& p, hipStream_t stream);
 hipError_t launch_weights_update(const WeightsUpdateParams& p, hipStream_t stream);

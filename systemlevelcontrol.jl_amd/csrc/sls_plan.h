@@ -129,6 +129,24 @@ struct sls_plan {
     const int32_t* halo_rows = nullptr;
     double* out = nullptr;            // [3 · nsub + 2]
   } resid;
+  // multipliers and gradient (SLS_PLAN_MULTIPLIERS; sls_plan_gradient).  d_mu — an allocation of its own, made
+  // with the plan, n_subproblems slots of mu_slot_doubles(T) — is kp.mu of every execute; the rest is one device allocation
+  // made by the first gradient call (gradient_ensure).  Neither is counted in workspace_bytes.  Layouts: sls_gradient.h.
+  struct Gradient {
+    double* d_mu = nullptr;
+    bool executed = false;            // some execute has written multipliers
+    bool ready = false;
+    int lds_doubles = 0;
+    int64_t nnzA = 0, nnzB = 0;
+    const uint8_t* b_zero = nullptr;
+    const int64_t* ent_ptr = nullptr;  const int32_t* ent = nullptr;
+    const int64_t* inv_ptr = nullptr;  const int64_t* inv_slot = nullptr;
+    const int64_t* w_base = nullptr;   const int64_t* winv_ptr = nullptr;  const int64_t* winv_slot = nullptr;
+    double* contrib = nullptr;        // one per listed entry
+    double* wcontrib = nullptr;       // Σ(ñx+ñu), plans with updatable weights only
+    double* col_weight = nullptr;     // [nsub] staging of sls_plan_fetch_gradient's host weights
+    double* out = nullptr;            // [nnzA + nnzB + Nx + Nu] results of sls_plan_fetch_gradient
+  } grad;
 };
 
 namespace sls {
@@ -140,6 +158,7 @@ struct PlanOpts {
   bool force_tile = false;                          // every column on the tile kernel (the refinement pass)
   const std::vector<int64_t>* pk_override = nullptr; // with force_tile: packed bases of the subproblems inside the refined plan's packed array
   int host_tables = -1;                             // mask / destination tables: 1 built on the host, 0 expanded on the device, -1 = SLS_HOST_TABLES decides
+  bool multipliers = false;                         // SLS_PLAN_MULTIPLIERS: every column on the one-wave kernel, which exports λ
 };
 
 // sls_api.cpp

@@ -83,7 +83,7 @@ int select_kernels(sls_plan* pl, const sls_dims* dims, const PlanOpts& opt, cons
   knobs.apply(kp);
   std::string msg;
   int rc = kp.objective == 1 ? check_sum_of_norms_weights(S, msg) : 0;
-  if (!rc) rc = build_launch_list(S, kp.T, kp.objective, pl->ctx->ncu[pl->slot], opt.force_tile, RoutingKnobs::from_env(), route, msg);
+  if (!rc) rc = build_launch_list(S, kp.T, kp.objective, pl->ctx->ncu[pl->slot], opt.force_tile, RoutingKnobs::from_env(), route, msg, opt.multipliers);
   if (rc) return fail(pl->ctx, rc, msg);
   pl->launches = std::vector<sls_plan::Launch>(route.launches.begin(), route.launches.end());
   pl->has_tile = route.has_tile;
@@ -271,6 +271,21 @@ int run_setup_kernels(sls_plan* pl, const CompactTables& ct) {
   return 0;
 }
 
+// SLS_PLAN_MULTIPLIERS: the buffer every execute exports λ into — an allocation of its own, not part of workspace_bytes;
+// cleared once, so that a slot no execute has written yet (and the lanes beyond a 16-lane class's rows) reads as 0
+int take_multiplier_buffer(sls_plan* pl) {
+  const size_t bytes = (size_t)std::max(pl->kp.nsub, 1) * (size_t)mu_slot_doubles(pl->kp.T) * sizeof(double);
+  void* d = nullptr;
+  hipError_t e = hipMalloc(&d, bytes);
+  if (e != hipSuccess) return hipfail(pl->ctx, e, "hipMalloc (multiplier buffer)");
+  pl->dev_allocs.push_back(d);
+  e = hipMemsetAsync(d, 0, bytes, pl->stream);
+  if (e != hipSuccess) return hipfail(pl->ctx, e, "hipMemsetAsync (multiplier buffer)");
+  pl->grad.d_mu = static_cast<double*>(d);
+  pl->kp.mu = pl->grad.d_mu; pl->kp.mu_stride = mu_slot_doubles(pl->kp.T);
+  return 0;
+}
+
 // sls_plan_info, and the big host pools go: nothing reads them after the upload
 void fill_info_and_drop_pools(sls_plan* pl, double t_symbolic_s, double t_upload_s) {
   Symbolic& S = pl->sym;
@@ -362,6 +377,7 @@ int sls::plan_finish(sls_ctx* ctx, int dev_slot, const sls_dims* dims, sls_plan*
   tick("launch list + requests");
   if ((rc = commit_plan_arena(pl, ar))) return bail(rc);
   tick("arena commit (malloc+H2D)");
+  if (opt.multipliers && (rc = take_multiplier_buffer(pl))) return bail(rc);
   if ((rc = run_setup_kernels(pl, ct))) return bail(rc);
   const double t2 = now_s();
   tick("set-up stream synchronize");
@@ -426,7 +442,9 @@ extern "C" {
 int sls_h2_sf_plan(sls_ctx* ctx, int dev_slot, const sls_dims* dims, const sls_plant* P, const sls_csc_bool* Sx,
                    const sls_csc_bool* Su, int64_t ngroups, const int64_t* group_ptr, const int64_t* group_cols,
                    int64_t group_begin, int64_t group_end, sls_plan** plan_out) {
-  return plan_create(ctx, dev_slot, dims, P, Sx, Su, ngroups, group_ptr, group_cols, group_begin, group_end, true, PlanOpts{}, plan_out);
+  PlanOpts opt;
+  opt.multipliers = dims && (dims->flags & SLS_PLAN_MULTIPLIERS) != 0;
+  return plan_create(ctx, dev_slot, dims, P, Sx, Su, ngroups, group_ptr, group_cols, group_begin, group_end, true, opt, plan_out);
 }
 
 void sls_plan_destroy(sls_plan* plan) {
@@ -468,6 +486,7 @@ int sls_plan_refine(sls_plan* plan, const sls_dims* dims, const sls_plant* P, co
   if (dims->flags & SLS_SOLVE_SUM_OF_NORMS) return fail(plan->ctx, SLS_EUNSUPPORTED, "sls_plan_refine: 𝓗₂ objective only");
   if (plan->kp.objective != 0) return fail(plan->ctx, SLS_EUNSUPPORTED, "sls_plan_refine: 𝓗₂ objective only");
   if (ngroups != plan->ngroups_in) return fail(plan->ctx, SLS_EINVAL, "sls_plan_refine: the group list does not match the one this plan was built from");
+  if (plan->grad.d_mu) return fail(plan->ctx, SLS_EUNSUPPORTED, "sls_plan_refine: a plan built with SLS_PLAN_MULTIPLIERS takes no refinement (the tile pass would leave stale multipliers)");
   HIPCHK(plan->ctx, hipSetDevice(plan->dev));
   int64_t nr = 0;
   std::vector<int32_t> stt, its; std::vector<double> res;

@@ -108,8 +108,22 @@ T4Pools t4_pool_layout(const std::vector<LaunchSpec>& launches, int T, bool pres
 // small wave classes (0..5) → ONE multi-class launch; mid classes (6..8) → one launch each;
 // everything else (ñx > 64, ñu > 64, or LDS over budget) → the tile kernel (or the round-1 workgroup kernel, SLS_TILE).
 int build_launch_list(Symbolic& S, int T, int objective, int ncu, bool force_tile, const RoutingKnobs& K, RoutingResult& out,
-                      std::string& err) {
+                      std::string& err, bool one_wave_only) {
   const bool force_general = force_tile || K.force_general;
+  if (one_wave_only) {
+    // SLS_PLAN_MULTIPLIERS: only the one-wave kernel of the 16- and 32-lane classes exports its multipliers
+    if (objective == 1) { err = "SLS_PLAN_MULTIPLIERS: the sum-of-norms objective keeps no multiplier of the 𝓗₂ cost"; return SLS_EUNSUPPORTED; }
+    if (force_tile) { err = "SLS_PLAN_MULTIPLIERS: the tile kernel holds no accumulated multiplier"; return SLS_EUNSUPPORTED; }
+    for (const SubDesc& sd : S.subs) {
+      if (sd.has_w == 3 || sd.has_w == 4) { err = "SLS_PLAN_MULTIPLIERS: coupled column groups (non-diagonal B1[c_j,c_j]) are not supported"; return SLS_EUNSUPPORTED; }
+      if (sd.has_w == 2) { err = "SLS_PLAN_MULTIPLIERS: a dense cost Hessian is not supported (diagonal weights only)"; return SLS_EUNSUPPORTED; }
+      if (sd.cls < 0 || sd.cls >= kNumSmallWaveClasses) {
+        err = "SLS_PLAN_MULTIPLIERS: a column with ñx = " + std::to_string(sd.n) + " (ñu = " + std::to_string(sd.m) +
+              ") runs on the tile kernel, which holds no accumulated multiplier (one-wave classes only: ñx ≤ 32, ñu ≤ 64)";
+        return SLS_EUNSUPPORTED;
+      }
+    }
+  }
   const int capA = S.max_row_A, capAc = S.max_row_At, capB = S.max_row_B, capBc = S.max_row_Bt;
   std::vector<int32_t> bins[kNumWaveClasses + 1];   // [c] wave class c, [kNumWaveClasses] general
   std::vector<int32_t>& too_large = out.too_large;  // beyond the LDS budget of every kernel of this build
@@ -370,7 +384,7 @@ int build_launch_list(Symbolic& S, int T, int objective, int ncu, bool force_til
       L.mcap = mcap; L.nm_max = nm_max;
       L.fac_stride = (int64_t)(T + 1) * rpl_max * 64;
       // latency regime: two waves per column (twisted factorisation) when there are far fewer columns than SIMDs
-      if (!K.no_twisted && !vg && merge_cls >= 0 && cls == merge_cls && cls < kNumSmallWaveClasses && T >= 3 &&
+      if (!K.no_twisted && !one_wave_only && !vg && merge_cls >= 0 && cls == merge_cls && cls < kNumSmallWaveClasses && T >= 3 &&
           (int64_t)v.size() <= 2LL * ncu) {
         const int64_t tl = twisted_kernel_lds_bytes(cls, T, mcap, capA, capAc, capB, capBc, nm_max);
         if (tl <= kMaxLds) {
@@ -482,6 +496,13 @@ int build_launch_list(Symbolic& S, int T, int objective, int ncu, bool force_til
       err = "internal: a launch needs " + std::to_string(L.lds) + " B of LDS (160 KiB available)";
       return SLS_EUNSUPPORTED;
     }
+  if (one_wave_only)
+    for (const auto& L : launches)
+      if (L.kind != LaunchKind::OneWave || L.cls >= kNumSmallWaveClasses) {
+        err = "SLS_PLAN_MULTIPLIERS: a column's working set is beyond the one-wave kernel's LDS (it would run on another kernel)";
+        return SLS_EUNSUPPORTED;
+      }
+  if (one_wave_only && !out.too_large.empty()) { err = "SLS_PLAN_MULTIPLIERS: a column is beyond every kernel's LDS budget"; return SLS_EUNSUPPORTED; }
   // launches of one execute run CONCURRENTLY: disjoint workspace regions
   for (auto& L : launches) {
     L.fac_stride = (L.fac_stride + 31) / 32 * 32;        // every workgroup's region starts on a 256-B boundary

@@ -74,8 +74,10 @@ struct RoutingResult {
 
 // Bins the subproblems by size class and builds the launch list.  Rewrites S.order (launch by launch) and S.subs[].cls (the
 // class a column runs in, -1 outside the one-wave classes).  0, or SLS_EUNSUPPORTED with `err` filled.
+// one_wave_only (plans built with SLS_PLAN_MULTIPLIERS): every column on the one-wave kernel of the 16- and 32-lane classes — no
+// two-wave and no four-wave launch; SLS_EUNSUPPORTED, naming the reason, when some column cannot run there.
 int build_launch_list(Symbolic& S, int T, int objective, int ncu, bool force_tile, const RoutingKnobs& knobs, RoutingResult& out,
-                      std::string& err);
+                      std::string& err, bool one_wave_only = false);
 
 // one launch as sls_plan_describe prints it
 std::string describe_launch(const LaunchSpec& L);

@@ -546,7 +546,7 @@ int localized_layout(const sls_dims* dims, const sls_csc_f64* B1, const Localize
   S.pk_base.assign((size_t)Nx + 1, 0);
   // objective records: this route only takes the default cost, so the constant is 0 and the scale is B1[c,c]² (1 for the
   // minimum-norm point of a b = 0 column), as the host pass leaves them
-  S.obj_pool.resize(2 * (size_t)Nx);
+  S.obj_pool.resize(2 * (size_t)Nx); S.b_zero.resize((size_t)Nx);
   int64_t& idx_tot = lay.idx_total = 0; int64_t& cw_tot = lay.cw_total = 0; int64_t md_tot = 0;
   for (int64_t c = 0; c < Nx; ++c) {
     const int32_t* ci = col_info + 6 * c;
@@ -564,6 +564,7 @@ int localized_layout(const sls_dims* dims, const sls_csc_f64* B1, const Localize
     add_column_cost(n, m, ci[3], ci[4], T, ci[5], S.flops_alg, S.bytes_alg);
     const double bd = b1_diagonal(B1, dims->index_base, c);
     S.obj_pool[2 * (size_t)c] = bd != 0.0 ? bd * bd : 1.0; S.obj_pool[2 * (size_t)c + 1] = 0.0;
+    S.b_zero[(size_t)c] = bd == 0.0;
   }
   S.md_total = md_tot; S.n_packed = S.pk_base[(size_t)Nx];
   // processing order, as build_symbolic: descending ñx, stable — it is the plan's launch order
@@ -1023,6 +1024,7 @@ static int fill_range(const Inputs& in, const std::vector<int64_t>& gptr, const 
           cst *= (double)T;
         }
         S.obj_pool[2 * sd.out_index] = scale; S.obj_pool[2 * sd.out_index + 1] = cst;
+        S.b_zero[(size_t)sd.out_index] = !coupled && bdiag[q] == 0.0;
       }
       S.subs[sd.out_index] = sd;
       S.sub_col[sd.out_index] = (int32_t)c;
@@ -1109,7 +1111,7 @@ int build_symbolic(const Inputs& in, int64_t gbeg, int64_t gend, Symbolic& S, st
   S.md_total = md_tot;
   if (S.want_packed) S.compact = false;
   S.idx_pool.resize(idx_tot);
-  S.subs.resize(sub_tot); S.sub_col.resize(sub_tot); S.obj_pool.resize(2 * sub_tot);
+  S.subs.resize(sub_tot); S.sub_col.resize(sub_tot); S.obj_pool.resize(2 * sub_tot); S.b_zero.resize(sub_tot);
   if (S.wu.updatable) S.wu.b2.assign((size_t)sub_tot, 0.0);
   std::vector<int32_t> nfree_of((size_t)sub_tot, 0);
   auto pass_b = [&]() -> int {

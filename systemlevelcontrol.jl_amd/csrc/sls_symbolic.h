@@ -80,6 +80,7 @@ struct Symbolic {
   // weights h and b = B1[c,c], 1 for the minimum-norm point of a b = 0 column.  [1] obj_const: T·‖D̃11[[s_x; Nx+s_u], c]‖²
   // (src/reduction.jl:15 keeps only those z-rows); a coupled group's Σ_w over its columns sits on its first column.
   pool_vec<double> obj_pool;
+  pool_vec<uint8_t> b_zero;             // per subproblem (by out_index): 1 = B1[c,c] = 0, the cost is constant (sls_gradient.h)
   pool_vec<int32_t> sub_col;            // global column of each subproblem
   int64_t n_packed = 0;
   std::vector<int64_t> pk_base;         // n_subs+1: first packed index of each subproblem (its free variables are contiguous)

@@ -298,7 +298,9 @@ int sls_h2_sf_plan_localized(sls_ctx* ctx, int dev_slot, const sls_dims* dims, c
   else pl->dev_allocs.push_back(a2);
   hold.own2 = nullptr; hold.pl = nullptr;
   const DeviceTables dt{cp.idx_pool, cp.cmask, cp.cbase, cp.cw_off};
-  return plan_finish(ctx, dev_slot, dims, pl, t0, false, PlanOpts{}, &dt, plan_out);
+  PlanOpts opt;
+  opt.multipliers = (dims->flags & SLS_PLAN_MULTIPLIERS) != 0;
+  return plan_finish(ctx, dev_slot, dims, pl, t0, false, opt, &dt, plan_out);
 }
 
 }  // extern "C"

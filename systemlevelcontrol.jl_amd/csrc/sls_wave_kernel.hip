@@ -248,10 +248,13 @@ __device__ __forceinline__ void gauss_jordan_tiled(double (&M)[RPL], double* mat
 // VG = true: λ and r/q/Δλ (the two T-sized vectors) live in a per-workgroup global workspace (L2-resident) instead of
 // LDS — the throughput-regime variant: LDS drops from ≈39 KB to ≈18 KB per wave (8 resident waves per CU instead of 4);
 // P_k is fetched from global memory in every sweep step anyway, so the extra row per step adds no latency chain.
-template <int NPL, int RPL, bool VG, bool SON = false>
+// MU = true (plans built with SLS_PLAN_MULTIPLIERS): λ of the pass whose z(λ) is written out goes to the subproblem's own slot of
+// p.mu — instantiations of their own, so that the others keep their code and registers.
+template <int NPL, int RPL, bool VG, bool SON = false, bool MU = false>
 __device__ __forceinline__ void wave_solve_column(const KernelParams& p, const SubDesc& sd, double* __restrict__ fac,
                                                   double* __restrict__ gvec, unsigned char* lds_raw) {
   static_assert(!SON || VG, "the sum-of-norms build keeps its vectors in the global workspace");
+  static_assert(!MU || (!SON && NPL <= kMuLd), "multipliers are exported by the 𝓗₂ builds of the 16- and 32-lane classes");
   constexpr int HS = 64 / NPL;          // row groups
   constexpr int NP = HS * RPL;          // rows held (≥ n)
   constexpr int LDM = NPL + 1;          // padded leading dimension of the LDS matrix image
@@ -1119,6 +1122,12 @@ __device__ __forceinline__ void wave_solve_column(const KernelParams& p, const S
   }
   iters += iters_first;
   output_pass();
+  if constexpr (MU) {
+    // λ has not moved since the residual pass whose z(λ) the output pass just wrote.  Indexed by subproblem, not by workgroup:
+    // a workgroup solves several columns in a row, and a partial re-solve rewrites exactly the slots it solves.
+    double* __restrict__ mu = p.mu + sd.out_index * p.mu_stride;
+    for (int i = lane; i < (T + 1) * NPL; i += 64) mu[(i / NPL) * kMuLd + (i % NPL)] = lam[i];
+  }
   if (sd.pos < 0 && status == 0) status = 3;
   if (p.dbg && lane == 0) {
     for (int q = 0; q < 8; ++q) p.dbg[sd.out_index * 8 + q] = tc[q];
@@ -1132,7 +1141,7 @@ __device__ __forceinline__ void wave_solve_column(const KernelParams& p, const S
 
 // register budget: 256 VGPRs (2 waves/SIMD) for NPL ≤ 32, 512 (1 wave/SIMD) for the NPL = 64 classes whose pivot block
 // alone takes 2·RPL = 80..128 registers
-template <int NPL, int RPL, bool VG, bool SON = false>
+template <int NPL, int RPL, bool VG, bool SON = false, bool MU = false>
 #ifndef SLS_WAVE_OCC
 #define SLS_WAVE_OCC 2          // experiments: 1 = a whole SIMD's registers per wave (no scratch), four waves per CU
 #endif
@@ -1149,12 +1158,12 @@ __global__ __launch_bounds__(64, (NPL == 64 ? 1 : SLS_WAVE_OCC)) void h2_column_
       s = __builtin_amdgcn_readfirstlane(s);
       if (s >= p.nsub) break;
       const SubDesc sd = p.subs[p.order[p.order_off + s]];
-      wave_solve_column<NPL, RPL, VG, SON>(p, sd, fac, gvec, lds_raw);
+      wave_solve_column<NPL, RPL, VG, SON, MU>(p, sd, fac, gvec, lds_raw);
     }
   } else {
     for (int s = blockIdx.x; s < p.nsub; s += gridDim.x) {
       const SubDesc sd = p.subs[p.order[p.order_off + s]];
-      wave_solve_column<NPL, RPL, VG, SON>(p, sd, fac, gvec, lds_raw);
+      wave_solve_column<NPL, RPL, VG, SON, MU>(p, sd, fac, gvec, lds_raw);
     }
   }
 }
@@ -1793,20 +1802,24 @@ hipError_t launch_twisted(int cls, const KernelParams& p, int grid, size_t lds, 
   }
 }
 
-template <int NPL, int RPL, bool VG>
+template <int NPL, int RPL, bool VG, bool MU = false>
 static hipError_t launch_one_v(const KernelParams& p, int grid, size_t lds, hipStream_t st, const LaunchEvents* ev) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&h2_column_wave_kernel<NPL, RPL, VG>),
+  if constexpr (!MU && NPL <= kMuLd) {
+    if (p.mu) return launch_one_v<NPL, RPL, VG, true>(p, grid, lds, st, ev);      // the build that exports λ
+  }
+  if (!MU && p.mu) return hipErrorInvalidValue;                                   // (a 64-lane class: plan creation refuses it)
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&h2_column_wave_kernel<NPL, RPL, VG, false, MU>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  if (ev) hipExtLaunchKernelGGL((h2_column_wave_kernel<NPL, RPL, VG>), dim3(grid), dim3(64), (uint32_t)lds, st, ev->start, ev->stop, 0, p);
-  else hipLaunchKernelGGL((h2_column_wave_kernel<NPL, RPL, VG>), dim3(grid), dim3(64), lds, st, p);
+  if (ev) hipExtLaunchKernelGGL((h2_column_wave_kernel<NPL, RPL, VG, false, MU>), dim3(grid), dim3(64), (uint32_t)lds, st, ev->start, ev->stop, 0, p);
+  else hipLaunchKernelGGL((h2_column_wave_kernel<NPL, RPL, VG, false, MU>), dim3(grid), dim3(64), lds, st, p);
   return hipGetLastError();
 }
 template <int NPL, int RPL>
 static hipError_t launch_one(const KernelParams& p, int grid, size_t lds, hipStream_t st, const LaunchEvents* ev) {
   if constexpr (NPL <= 32) {
     if (p.objective == 1) {                  // sum-of-norms build: ñx ≤ 32, vectors in the global workspace
-      if (p.vec_in_lds != 0) return hipErrorInvalidValue;
+      if (p.vec_in_lds != 0 || p.mu) return hipErrorInvalidValue;
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&h2_column_wave_kernel<NPL, RPL, true, true>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) return e;

@@ -92,13 +92,17 @@ def default_context():
 class Plan:
     """Symbolic pass + device-resident tables for a shard of the groups (sls_h2_sf_plan)."""
 
-    def __init__(self, ctx: Context, P, S, groups=None, group_range=None, dev_slot=0, objective="h2", updatable_weights=False):
+    def __init__(self, ctx: Context, P, S, groups=None, group_range=None, dev_slot=0, objective="h2", updatable_weights=False,
+                 multipliers=False):
         """updatable_weights=True builds the plan with SLS_PLAN_WEIGHTS_UPDATABLE: `update_weights` can then give it new LQR
-        weights (C1 = [diag(q); 0], D12 = [0; diag(r)], D11 = 0 on the selected rows, no coupled group: SLSError otherwise)."""
+        weights (C1 = [diag(q); 0], D12 = [0; diag(r)], D11 = 0 on the selected rows, no coupled group: SLSError otherwise).
+        multipliers=True builds it with SLS_PLAN_MULTIPLIERS: every execute keeps the multipliers of the achievability
+        constraints, which `gradient` turns into the derivative of the 𝓗₂ cost in the stored entries of A and B2 (every column
+        then runs on the one-wave kernel; SLSError for ñx > 32, dense Hessians, coupled groups and the sum-of-norms objective)."""
         Sx, Su = S
         self.ctx = ctx
         self._lib = ctx._lib
-        self.m = _capi.Marshalled(P, Sx, Su, groups, flags=_plan_flags(objective, updatable_weights))
+        self.m = _capi.Marshalled(P, Sx, Su, groups, flags=_plan_flags(objective, updatable_weights, multipliers))
         ng = self.m.ngroups if groups is not None else P.Nx
         gb, ge = (0, ng) if group_range is None else group_range
         h = C.c_void_p()
@@ -116,16 +120,16 @@ class Plan:
         self._owned_values = []
 
     @classmethod
-    def localized(cls, ctx, P, d, T, alpha, dev_slot=0, objective="h2", index_base=0, updatable_weights=False):
+    def localized(cls, ctx, P, d, T, alpha, dev_slot=0, objective="h2", index_base=0, updatable_weights=False, multipliers=False):
         """sls_h2_sf_plan_localized: the plan of the README's (d, T, α) localization built from the plant alone — level sets,
         index sets, mask slices and destinations computed on the device, no mask array crosses PCIe.  Values come back in the
         CSC order of `workloads.localization_masks_native(P.A, P.B2, d, T, alpha)`.  updatable_weights=True: as in `Plan`; the
-        plant may then carry LQR weights other than the identity (D11 must be zero)."""
+        plant may then carry LQR weights other than the identity (D11 must be zero).  multipliers=True: as in `Plan`."""
         self = cls.__new__(cls)
         self.ctx = ctx
         self._lib = ctx._lib
         empty = [sp.csc_matrix((P.Nx, P.Nx), dtype=bool)] * 0
-        self.m = _capi.Marshalled(P, empty, empty, None, index_base=index_base, flags=_plan_flags(objective, updatable_weights))
+        self.m = _capi.Marshalled(P, empty, empty, None, index_base=index_base, flags=_plan_flags(objective, updatable_weights, multipliers))
         self.m.dims.T = int(T)
         h = C.c_void_p()
         _capi.check(self._lib.sls_h2_sf_plan_localized(ctx.handle, dev_slot, C.byref(self.m.dims), C.byref(self.m.plant), int(d),
@@ -384,6 +388,58 @@ class Plan:
         _capi.check(self._lib.sls_plan_residual(self.handle, stream, d_values, int(packed), *[a.data_ptr() for a in out],
                                                 tot.data_ptr()), self.ctx.handle)
         return out[0][:n], out[1][:n], out[2][:n], tot
+
+    # -- gradient of the 𝓗₂ cost in A, B2 and the LQR diagonals, for a plan built with multipliers=True --
+    def gradient(self, d_values, packed=False, column_weights=None, stream=None, weights=False):
+        """sls_plan_gradient into fresh torch tensors on the plan's device: (gA[nnz(A)], gB2[nnz(B2)]) — the derivative of
+        Σ_j c_j·J_j (J_j: what `objective_values` reports, c_j = column_weights, default 1) in the stored entries of A and B2, in
+        the CSC order of `update_plant` — from the multipliers the last execute left and the values it wrote to `d_values`.
+        weights=True (plans with updatable_weights=True) appends (gc1[Nx], gd12[Nu]), the derivatives in the two diagonals.
+        column_weights: None, or a float64 tensor on the plan's device with n_subproblems values.  Enqueued on `stream` (None =
+        the null stream) behind the plan's last execute and update; nothing waits for the device (the plan's first call
+        builds the entry tables on the host and does wait)."""
+        import torch
+        dev = torch.device("cuda", self.info["device"])
+        cw = None
+        if column_weights is not None:
+            if not _is_device_tensor(column_weights) or column_weights.dtype != torch.float64 or column_weights.dim() != 1 or \
+                    not column_weights.is_contiguous() or column_weights.numel() != self.info["n_subproblems"]:
+                raise ValueError("gradient: column_weights must be a contiguous float64 tensor of n_subproblems values on the plan's device")
+            cw = column_weights.data_ptr()
+        sizes = [self.m.nnz("A"), self.m.nnz("B2")] + ([int(self.m.dims.Nx), int(self.m.dims.Nu)] if weights else [])
+        out = [torch.empty(max(n, 1), dtype=torch.float64, device=dev) for n in sizes]
+        ptrs = [a.data_ptr() for a in out] + [None] * (4 - len(out))
+        _capi.check(self._lib.sls_plan_gradient(self.handle, stream, d_values, int(packed), cw, *ptrs), self.ctx.handle)
+        return tuple(a[:n] for a, n in zip(out, sizes))
+
+    def gradient_values(self, d_values, packed=False, column_weights=None, weights=False):
+        """sls_plan_fetch_gradient: the same on the plan's own stream into host arrays — (gA, gB2, n_skipped), with weights=True
+        (gA, gB2, gc1, gd12, n_skipped); n_skipped counts the subproblems that contributed 0 because their status is neither
+        SLS_COL_OK nor SLS_COL_TRIVIAL.  column_weights: None or n_subproblems host values."""
+        dp = C.POINTER(C.c_double)
+        cw = None
+        if column_weights is not None:
+            cw = np.ascontiguousarray(column_weights, dtype=np.float64)
+            if cw.ndim != 1 or cw.size != self.info["n_subproblems"]:
+                raise ValueError("gradient_values: column_weights needs n_subproblems values")
+        sizes = [self.m.nnz("A"), self.m.nnz("B2")] + ([int(self.m.dims.Nx), int(self.m.dims.Nu)] if weights else [])
+        out = [np.zeros(max(n, 1)) for n in sizes]
+        ptrs = [a.ctypes.data_as(dp) for a in out] + [None] * (4 - len(out))
+        ns = C.c_int64()
+        _capi.check(self._lib.sls_plan_fetch_gradient(self.handle, d_values, int(packed), None if cw is None else cw.ctypes.data_as(dp),
+                                                      *ptrs, C.byref(ns)), self.ctx.handle)
+        return tuple(a[:n] for a, n in zip(out, sizes)) + (ns.value,)
+
+    def multipliers(self, sub):
+        """sls_plan_fetch_multipliers: μ of subproblem `sub` (col_status order) as the last execute left it, shape (T + 1, ñx):
+        block row k of the achievability constraints, rows in s_x order; Eᵀμ = ∇J on the subproblem's free variables."""
+        T = self.info["T"]
+        n = self._lib.sls_plan_fetch_multipliers(self.handle, int(sub), None, 0)       # the length the call wants, or an error
+        if n < 0:
+            _capi.check(n, self.ctx.handle)
+        buf = np.zeros(max(n, 1))
+        _capi.check(self._lib.sls_plan_fetch_multipliers(self.handle, int(sub), buf.ctypes.data_as(C.POINTER(C.c_double)), n), self.ctx.handle)
+        return buf[:n].reshape(T + 1, n // (T + 1)).copy()
 
     def describe(self):
         buf = C.create_string_buffer(4096)
@@ -750,8 +806,9 @@ def SLS_H2_localized(P, d, T, alpha, *, ctx: Context | None = None, return_info=
     return Phix, Phiu
 
 
-def _plan_flags(objective, updatable_weights):
-    return _objective_flags(objective) | (_capi.SLS_PLAN_WEIGHTS_UPDATABLE if updatable_weights else 0)
+def _plan_flags(objective, updatable_weights, multipliers=False):
+    return _objective_flags(objective) | (_capi.SLS_PLAN_WEIGHTS_UPDATABLE if updatable_weights else 0) | \
+        (_capi.SLS_PLAN_MULTIPLIERS if multipliers else 0)
 
 
 def _objective_flags(objective):
